@@ -22,6 +22,9 @@ The JSON line also carries
                   per launch from the committed rocprofv3 PMC pass (profiles/), null if absent;
   cpu_baseline -- the unmodified reference (oracle/_ref/rtl_wmbus) timed on this host's cores on a
                   bounded sample of the same captures (rank 0, N = 1 only).
+
+--dump-outputs DIR writes the datagram lines of the last timed step as .npy files (dump_outputs()); the captures are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import os
 
@@ -81,7 +84,13 @@ def parse():
                     help="A/B runs: a tuning field of wmbus_cfg for the main batch (k1_small_tile=1, rssi_full=1, rssi_dense_pm=500, rounds_on_host=1 ...); repeatable")
     ap.add_argument("--details", default=os.path.join(ROOT, "gpurun_out", "bench_details.json"),
                     help="where the full record goes (per-context stage times, every leg with its sub-measurements); the stdout line is the compact one")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed its caller in its last step (every capture's datagram "
+                         "lines) as DIR/<name>.npy, float64 / float32, at most 64 MB; same arguments, same inputs: two builds compare file for file")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def cpu_baseline(caps, n_samples):
@@ -138,6 +147,49 @@ def last_pass_picks(contexts, world, per_wave=8):
             w = min(64, cnt - w0)
             picks += sorted({first + w0 + (j * (w - 1)) // max(1, k - 1) for j in range(k)} if w > 1 and k > 1 else {first + w0})
     return picks
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0xD0D0
+
+
+def dump_outputs(batch, S, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the lines every context's LAST push handed wmbus_batch_run's sink (stream, chain, algorithm, CRC flag,
+    sample index, datagram text), grouped by capture in print order.  Per line: datagram_{capture,chain,algo,crc_ok,sample}.npy
+    (float64) and its text as byte codes in datagram_text.npy (float32, concatenated; line k is
+    text[text_offset[k]:text_offset[k + 1]]).  When everything would exceed `budget`, captures are taken in a fixed seeded
+    order until it is met; captures.npy (float64) lists the captures written."""
+    per = [[] for _ in range(S)]
+    for rx, first, _cnt in batch.contexts:
+        for ln in rx.lines():
+            per[first + ln["stream"]].append(ln)
+    budget -= 8 * 128                                   # the .npy headers
+    cost = [sum(6 * 8 + 4 * len(ln["text"].encode()) for ln in lines) + 8 for lines in per]   # 5 fields + offset (f64), text (f32)
+    if sum(cost) + 8 <= budget:
+        keep = list(range(S))
+    else:
+        keep, used = [], 8
+        for s_ in np.random.default_rng(DUMP_SAMPLE_SEED).permutation(S):
+            if used + cost[s_] <= budget:
+                keep.append(int(s_))
+                used += cost[s_]
+        keep.sort()
+    lines = [(s_, ln) for s_ in keep for ln in per[s_]]
+    text = [ln["text"].encode() for _s, ln in lines]
+    arrays = {
+        "captures": np.array(keep, np.float64),
+        "datagram_capture": np.array([s_ for s_, _ln in lines], np.float64),
+        "datagram_chain": np.array([ln["chain"] for _s, ln in lines], np.float64),
+        "datagram_algo": np.array([ln["algo"] for _s, ln in lines], np.float64),
+        "datagram_crc_ok": np.array([ln["crc_ok"] for _s, ln in lines], np.float64),
+        "datagram_sample": np.array([ln["sample"] for _s, ln in lines], np.float64),
+        "datagram_text_offset": np.concatenate([[0], np.cumsum([len(t) for t in text])]).astype(np.float64),
+        "datagram_text": np.frombuffer(b"".join(text), np.uint8).astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "captures": len(keep), "of": S, "lines": len(lines), "bytes": int(sum(v.nbytes for v in arrays.values()))}
 
 
 def oracle_estimate_s(n_captures, n_samples, passes, threads, per_core_msamples_s=16.0, usable_cores=16):
@@ -470,6 +522,10 @@ def main():
     shard.barrier(group)
     elapsed = time.perf_counter() - t0
     passes_done += a.steps
+    dumped = None
+    if a.dump_outputs:                                  # before anything else runs the contexts again: they still hold the last timed push
+        dumped = dump_outputs(batch, S, a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, f"rank{rank}"),
+                              DUMP_BUDGET_BYTES // world)
     try:
         n_threads = len(os.listdir("/proc/self/task"))        # this rank's threads right behind the timed region (workers, decoder pools, runtime)
     except OSError:
@@ -690,6 +746,8 @@ def main():
             "input": "staged from pinned host memory inside every step (PCIe-inclusive, informational)" if a.from_host else "resident in HBM",
             "tolerance_mode": bool(a.tolerance_mode),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if tol is not None:
             out["tolerance_mode_leg"] = tol
         for key in ("c2_single_stream", "c3_single_stream", "live_latency", "c3_batch", "cli", "cli_1024"):
@@ -779,6 +837,8 @@ def main():
             sm["cli_1024"] = legs["cli_1024"].get("value"); sm["cli_1024_setup"] = legs["cli_1024"].get("with_setup_msamples_s")
         line["summary"] = sm
         line["details"] = details
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line, separators=(",", ":")), flush=True)
     elif parity is not None:
         ok = bool(parity["ok"]) or a.tolerance_mode

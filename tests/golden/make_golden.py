@@ -4,6 +4,8 @@ Run in the build container (needs /root/reference to have been compiled by `make
     python tests/golden/make_golden.py
 The JSON files map "<capture>|<switches>" -> stdout of the reference with the wall-clock timestamp
 field replaced by TS.  Synthetic captures are regenerated from (seed, config) by the test itself.
+reference_outputs.json (the probe's answers, test_oracle_units.py) is rewritten by the tests themselves:
+    WMBUS_RECORD_REFERENCE=1 python -m pytest tests/test_oracle_units.py tests/test_oracle_golden.py
 """
 import importlib
 import json

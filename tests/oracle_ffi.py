@@ -3,6 +3,8 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
 import ctypes
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -178,6 +180,37 @@ def run_reference(cu8, argv):
 
 def have_reference():
     return os.path.exists(REF_BIN)
+
+
+# ---- the reference's answers, recorded (tests/golden/reference_outputs.json) -----------------------------------------------
+REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "reference_outputs.json")
+_ref_outputs = None
+
+
+def sha256(data):
+    return hashlib.sha256(np.ascontiguousarray(data).tobytes() if isinstance(data, np.ndarray) else data).hexdigest()
+
+
+def reference_answer(key, live):
+    """What the unmodified reference answers under `key` (one ref_probe or rtl_wmbus run on a test's input), so that the tests
+    holding the oracle against the reference run where the reference was never built.  The record is
+    tests/golden/reference_outputs.json.  Where oracle/_ref exists, live() -- the same run, made now -- must give the
+    recorded answer; with WMBUS_RECORD_REFERENCE=1 it replaces the record instead (tests/README.md)."""
+    global _ref_outputs
+    if _ref_outputs is None:
+        with open(REF_OUTPUTS) as f:
+            _ref_outputs = json.load(f)
+    if os.path.exists(REF_BIN) and os.path.exists(REF_PROBE):
+        got = live()
+        if os.environ.get("WMBUS_RECORD_REFERENCE") == "1":
+            _ref_outputs[key] = got
+            with open(REF_OUTPUTS, "w") as f:
+                json.dump(_ref_outputs, f, indent=1, sort_keys=True)
+                f.write("\n")
+            return got
+        assert got == _ref_outputs.get(key), f"the reference's answer for {key!r} is not the one in {os.path.relpath(REF_OUTPUTS, ROOT)}"
+    assert key in _ref_outputs, f"no recorded answer of the reference for {key!r}: record it with WMBUS_RECORD_REFERENCE=1 where oracle/_ref is built"
+    return _ref_outputs[key]
 
 
 # ---- the two low-pass filters alone (oracle: wmo_fir; reference: ref_probe fir) ---------------------------------------------

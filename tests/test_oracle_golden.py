@@ -1,5 +1,5 @@
 """The oracle (oracle/wmbus_oracle.c) against the reference: committed golden stdout of the
-unmodified reference binary, and -- when oracle/_ref exists -- the binary itself."""
+unmodified reference binary, and -- when oracle/_ref exists -- the binary itself as well."""
 import json
 import os
 
@@ -59,11 +59,14 @@ def test_partial_tail_block_is_dropped(oracle, samples):
     assert a == b
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "rtl_wmbus")),
-                    reason="reference binary not built (no /root/reference on this box)")
 def test_oracle_matches_live_reference_binary(oracle, wm):
+    """The reference binary's stdout on these captures is recorded (tests/golden/reference_outputs.json, with the sha256 of each
+    capture); where oracle/_ref exists the binary runs live and must print the recorded text."""
     for seed in range(6):
         amp = [60, 20, 10, 8, 7, 12][seed]
         cu8, _ = wm.synth_capture(seed=500 + seed, n_samples=1 << 20, kinds=15, frames_per_s=60.0, amplitude=amp)
         for flags in (["-v"], ["-v", "-o"], ["-v", "-a"]):
-            assert oracle.run(cu8, flags_to_oracle_opts(oracle, flags))["text"] == oracle.run_reference(cu8, flags)
+            want = oracle.reference_answer(f"rtl_wmbus seed={500 + seed} {' '.join(flags)}",
+                                           lambda: {"input": oracle.sha256(cu8), "text": oracle.run_reference(cu8, flags)})
+            assert want["input"] == oracle.sha256(cu8), "the capture is not the one the reference's stdout was recorded for"
+            assert oracle.run(cu8, flags_to_oracle_opts(oracle, flags))["text"] == want["text"]

@@ -1,5 +1,5 @@
 import importlib, os, sys, subprocess, tempfile, re
-ROOT="/root/repo"; sys.path.insert(0, ROOT); sys.path.insert(0, ROOT+"/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, ROOT+"/tests")
 wm = importlib.import_module("rtl-wmbus_amd")
 tmp = tempfile.mkdtemp(dir="/dev/shm")
 caps = [wm.synth_capture(seed=9500 + i, n_samples=1 << 23, kinds=7, frames_per_s=20.0)[0] for i in range(8)]

@@ -1,5 +1,5 @@
 import importlib, os, sys, time
-ROOT = "/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 wm = importlib.import_module("rtl-wmbus_amd")
 n = 1 << 22
