@@ -510,7 +510,12 @@ __device__ __forceinline__ void clock_sys_group(const K2Args &a, const uint32_t 
                             sr = hs ? sr_new : sr;
                         }
                     }
-                    if (m + 32u == G.mb) stS[G.sidx] = gather(0);                  /* state the segment proper starts from */
+                    if (m + 32u == G.mb) {                                         /* state the segment proper starts from */
+                        /* fewer than 32 samples after the warm-up: this block is also the last one (roles 0 .. 2 posted it in slot 1),
+                         * and all of the segment is the ragged tail */
+                        stS[G.sidx] = gather(last ? 1 : 0);
+                        if (last) how = 1u;
+                    }
                 } else {
                     /* ---- block of the segment proper: chips into the staging ring, whole groups to memory ---- */
                     uint32_t cnt = 0;

@@ -45,6 +45,10 @@ extern "C" {
 
 int wm_emu_sys = 0;                       /* 1: the systolic form (wm_k2_clock_sys.h): every 64 lanes a block of four waves on the block emulator */
 void *wm_emu_states_out = nullptr;        /* optional: receives st_start then st_final ([2][S][nseg] WmClkState each) after the last round */
+/* optional: what the FIRST PASS left, before k2_verify (uint32 words, in this order): st_start, st_final ([2][S][nseg] WmClkState
+ * each), counts [2][S][nseg], slicer words [2][S][Mcap/32], chip regions [2][S][nseg][cap], checkpoint records [2][S][nseg][nck][16],
+ * then the round-0 re-run list: its length and [2][S][nseg] lane ids (unused entries 0) */
+uint32_t *wm_emu_first_out = nullptr;
 
 int wm_emu_descending = 1;
 int wm_emu_s1_span = 0;                   /* WmPush.s1_span of the next calls */
@@ -110,6 +114,16 @@ long wm_emu_clock(const float *dphi, uint32_t S, uint32_t M, uint32_t Mcap, uint
         }
     };
     launch(nullptr, lanes);
+    if (wm_emu_first_out) {
+        uint32_t *o = wm_emu_first_out;
+        auto put = [&](const void *src, size_t words) { std::memcpy(o, src, words * 4u); o += words; };
+        put(st_start.data(), st_start.size() * sizeof(WmClkState) / 4u);
+        put(st_final.data(), st_final.size() * sizeof(WmClkState) / 4u);
+        put(counts, lanes);
+        put(bits, (size_t)rows * (Mcap / 32u));
+        put(chips, (size_t)lanes * cap);
+        put(ckpt.data(), (size_t)lanes * nck * 16u);
+    }
     long reruns = 0;
     uint32_t round = 0;
     for (;; round++) {
@@ -125,6 +139,12 @@ long wm_emu_clock(const float *dphi, uint32_t S, uint32_t M, uint32_t Mcap, uint
              * so the predecessor's verdict of this round is there already) */
             const bool walks = wm_emu_chains && round >= 1;
             if (differs && !(walks && seg > 1 && bad[((size_t)ch * nseg + seg - 1) * S + stream])) list.push_back(lane);
+        }
+        if (wm_emu_first_out && round == 0) {
+            uint32_t *o = wm_emu_first_out + (size_t)lanes * (2u * sizeof(WmClkState) / 4u + 1u + cap + nck * 16u) + (size_t)rows * (Mcap / 32u);
+            o[0] = (uint32_t)list.size();
+            std::memset(o + 1, 0, (size_t)lanes * 4u);
+            if (!list.empty()) std::memcpy(o + 1, list.data(), list.size() * 4u);
         }
         if (list.empty()) break;
         if (round > nseg + 1) return -1;
@@ -145,5 +165,6 @@ long wm_emu_clock(const float *dphi, uint32_t S, uint32_t M, uint32_t Mcap, uint
 }
 
 unsigned wm_emu_clock_state_bytes(void) { return sizeof(WmClkState); }
+unsigned wm_emu_ck_samples(void) { return WM_CK_SAMPLES; }
 
 }

@@ -29,12 +29,14 @@ def emu():
     L.wm_emu_clock.restype = ctypes.c_long
     L.wm_emu_clock.argtypes = [ctypes.c_void_p] + [ctypes.c_uint] * 8 + [ctypes.c_void_p] * 6
     L.wm_emu_clock_state_bytes.restype = ctypes.c_uint
+    L.wm_emu_ck_samples.restype = ctypes.c_uint
     return L
 
 
-def run_emulated(emu, soft_rows, pushes, seg_len, warm, dc=False, descending=True, s1_span=None, chains=True, sys=False, states=None):
+def run_emulated(emu, soft_rows, pushes, seg_len, warm, dc=False, descending=True, s1_span=None, chains=True, sys=False, states=None, first=None):
     """soft_rows: [2][M] float32 FIR outputs of one capture; pushes: decimated samples per push.  sys: the systolic form (four
-    coroutines per lane on the block emulator).  states: a list that receives every push's start / end state records."""
+    coroutines per lane on the block emulator).  states: a list that receives every push's start / end state records.  first: a
+    list that receives every push's first-pass records and round-0 re-run list (clock_emu.cpp's wm_emu_first_out)."""
     ctypes.c_int.in_dll(emu, "wm_emu_sys").value = int(sys)
     if sys:
         s1_span = 1                                          # the systolic form has no two-segment S1 lanes (the product never used them)
@@ -58,12 +60,18 @@ def run_emulated(emu, soft_rows, pushes, seg_len, warm, dc=False, descending=Tru
         err, rounds = ctypes.c_uint(0), ctypes.c_uint(0)
         st = np.zeros(2 * 2 * nseg * sb, np.uint8)
         ctypes.c_void_p.in_dll(emu, "wm_emu_states_out").value = st.ctypes.data if states is not None else None
+        nck = max(seg_len // emu.wm_emu_ck_samples() - 1, 0)
+        fp = np.zeros(2 * nseg * (2 * sb // 4 + 1 + cap + 16 * nck + 1) + 2 * (Mcap // 32) + 1, np.uint32)
+        ctypes.c_void_p.in_dll(emu, "wm_emu_first_out").value = fp.ctypes.data if first is not None else None
         r = emu.wm_emu_clock(x.ctypes.data, 1, M, Mcap, flags, seg_len, warm[0], warm[1], cap, carry.ctypes.data, bits.ctypes.data,
                              chips.ctypes.data, counts.ctypes.data, ctypes.byref(err), ctypes.byref(rounds))
         ctypes.c_void_p.in_dll(emu, "wm_emu_states_out").value = None
+        ctypes.c_void_p.in_dll(emu, "wm_emu_first_out").value = None
         assert r >= 0 and err.value == 0
         if states is not None:
             states.append((st.copy(), counts.copy()))
+        if first is not None:
+            first.append(split_first_pass(fp, nseg, sb, Mcap, cap, nck))
         reruns += r
         max_rounds = max(max_rounds, rounds.value)
         for ch in range(2):
@@ -74,6 +82,18 @@ def run_emulated(emu, soft_rows, pushes, seg_len, warm, dc=False, descending=Tru
         m0 += M
     return ([np.concatenate(o) if o else np.zeros((0, 2), np.uint32) for o in chips_out], [np.concatenate(b) for b in bits_out],
             reruns, max_rounds)
+
+
+def split_first_pass(fp, nseg, sb, Mcap, cap, nck):
+    """The words clock_emu.cpp's wm_emu_first_out receives, by name (one capture: [2][nseg] lanes).  Chip regions are cut to
+    their counts: the slots beyond are scratch."""
+    lanes, sw, o, out = 2 * nseg, sb // 4, 0, {}
+    for name, n in (("st_start", lanes * sw), ("st_final", lanes * sw), ("counts", lanes), ("bits", 2 * (Mcap // 32)),
+                    ("chips", lanes * cap), ("ckpt", lanes * nck * 16)):
+        out[name], o = fp[o:o + n].copy(), o + n
+    out["chips"] = [out["chips"][i * cap: i * cap + min(int(out["counts"][i]), cap)] for i in range(lanes)]
+    out["list"] = fp[o + 1: o + 1 + int(fp[o])].copy()
+    return out
 
 
 def oracle_t2a_chips(ref, ch):
@@ -136,6 +156,94 @@ def test_device_source_on_host_matches_oracle_randomised(emu, oracle, wm):
     assert multi[False] > 0                                    # cascading re-run rounds (where the checkpoint bug lived) occurred
     assert walked > 0 and multi[True] <= multi[False]          # the chain walk ran, and never needs more rounds than lone segments do
     assert sys_reruns > 0
+
+
+# Segment tails.  A push's last segment ends r samples past its start; below 32 the systolic form's lane has only warm-up blocks
+# (its last block ends the warm-up), from 32 on a whole block of the segment proper and perhaps a ragged tail.  The product's pushes
+# (whole 4096-byte blocks at d <= 16) never leave r in 1 .. 62 at these segment lengths, so only this emulation reaches them.
+TAIL_RESIDUES = (1, 2, 31, 32, 33, 63, 64, 255, 256, 257, 2047, 2048, 2049)
+_tail_refs = {}
+
+
+def tail_capture(wm, oracle, kind):
+    """2^18 bytes of cu8 and the oracle's answer: exact silence at either mid-level, signal that falls silent, signal."""
+    if kind not in _tail_refs:
+        if kind in ("silence127", "silence128"):
+            cu8 = np.full(1 << 18, int(kind[-3:]), np.uint8)
+        else:
+            cu8 = wm.synth_capture(seed=0x7A11, n_samples=1 << 17, kinds=15, frames_per_s=300.0, amplitude=60.0)[0]
+            if kind == "signal_silence":
+                cu8[cu8.size // 2:] = 127
+        _tail_refs[kind] = oracle.run(cu8, flags_to_oracle_opts(oracle, ["-v"]), taps=True, chips=True)
+    return _tail_refs[kind]
+
+
+def tail_pushes(residues, seg_len, M):
+    """One push per residue r: 1 or 2 whole segments, then r samples; then the rest of the capture."""
+    pushes = [(1 + k % 2) * seg_len + r for k, r in enumerate(residues)]
+    assert sum(pushes) < M
+    return pushes + [M - sum(pushes)]
+
+
+def check_both_forms(emu, ref, pushes, seg_len, warm, chains, what):
+    """Both clock forms against the oracle, and against each other: their first passes (records, chips, slicer words, checkpoints,
+    the round-0 re-run list) word for word -- the first pass walks no chain, so nothing in it depends on the form -- and the re-run
+    totals."""
+    out = {}
+    for sys in (False, True):
+        first = []
+        chips, bits, reruns, _ = run_emulated(emu, ref["dphi_fir"], pushes, seg_len, warm, s1_span=1, chains=chains, sys=sys, first=first)
+        form = "systolic" if sys else "one-wave"
+        for ch in (0, 1):
+            assert np.array_equal(bits[ch], ref["bit"][ch]), (what, form, "slicer bits", ch,
+                                                              np.flatnonzero(bits[ch] != ref["bit"][ch])[:8])
+            assert np.array_equal(chips[ch], oracle_t2a_chips(ref, ch)), (what, form, "chips", ch)
+        out[sys] = (first, reruns)
+    (f1, r1), (fs, rs) = out[False], out[True]
+    for p, (a, b) in enumerate(zip(f1, fs)):
+        for name in ("st_start", "st_final", "counts", "bits", "ckpt", "list"):
+            assert np.array_equal(a[name], b[name]), (what, "first pass", "push", p, pushes[p], name)
+        assert all(np.array_equal(x, y) for x, y in zip(a["chips"], b["chips"])), (what, "first pass", "push", p, pushes[p], "chips")
+    assert r1 == rs, (what, "re-runs", r1, rs)
+
+
+@pytest.mark.parametrize("chains", [False, True])
+@pytest.mark.parametrize("warm_kind", ["short", "long"])
+@pytest.mark.parametrize("seg_len", [1024, 4096])
+@pytest.mark.parametrize("kind", ["silence127", "silence128", "signal_silence", "signal"])
+def test_segment_tails_both_clock_forms(emu, oracle, wm, kind, seg_len, warm_kind, chains):
+    """Every residue of TAIL_RESIDUES and seg_len - 1, each at the end of some push (in two schedules: the first push ends at a
+    different residue in each), warm-ups shorter than the segment's start (cold, speculative) or longer (an exact walk from the push
+    start)."""
+    ref = tail_capture(wm, oracle, kind)
+    warm = (512, 512) if warm_kind == "short" else (3 * seg_len, 6 * seg_len)
+    res = [r for r in TAIL_RESIDUES if r < seg_len] + [seg_len - 1]
+    for residues in (res[0::2], res[1::2][::-1]):
+        pushes = tail_pushes(residues, seg_len, ref["m"])
+        check_both_forms(emu, ref, pushes, seg_len, warm, chains, (kind, seg_len, warm, chains, pushes))
+
+
+def test_segment_tails_randomised(emu, oracle, wm):
+    """Random push schedules ending at random residues (most of them small), both forms, on random captures that fall silent."""
+    rng = np.random.default_rng(31 + int(os.environ.get("WMBUS_EMU_SEED", "0")))
+    for k in range(int(os.environ.get("WMBUS_EMU_N", "8"))):
+        cu8 = wm.synth_capture(seed=int(rng.integers(1, 1 << 30)), n_samples=1 << 16, kinds=int(rng.choice([15, 8, 7])), frames_per_s=200.0,
+                               amplitude=float(rng.choice([8.0, 60.0])), noise_sigma=float(rng.choice([0.5, 3.0])))[0]
+        if k % 2 == 0:
+            a = int(rng.integers(0, cu8.size // 2)) & ~1
+            cu8[a:] = int(rng.choice([127, 128]))
+        ref = oracle.run(cu8, flags_to_oracle_opts(oracle, ["-v"]), taps=True, chips=True)
+        seg_len = int(rng.choice([1024, 2048, 4096]))
+        warm = (int(rng.choice([256, 512, 4096, 12288])), int(rng.choice([256, 512, 8192, 24576])))
+        pushes, left = [], ref["m"]
+        while True:
+            r = int(rng.choice([int(rng.integers(1, 33)), int(rng.integers(33, 300)), int(rng.integers(1, seg_len))]))
+            p = int(rng.integers(0, 3)) * seg_len + r
+            if p >= left:
+                break
+            pushes.append(p)
+            left -= p
+        check_both_forms(emu, ref, pushes + [left], seg_len, warm, bool(k % 3), (k, seg_len, warm, pushes))
 
 
 @pytest.mark.parametrize("sys", [0, 1])

@@ -20,7 +20,7 @@ SRC = os.path.join(HERE, "emu", "k1_emu.cpp")
 CLANG = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"      # needs clang (ext_vector_type)
 HIST, SLACK = 4096, 256
 F_SHIFT, F_ACCURATE, F_T1C1, F_S1 = 1, 2, 8, 16                        # WM_F_* of wm_dev.h
-FS = {1: 800, 2: 1600, 3: 2400, 4: 3200, 5: 4000, 6: 4800, 8: 6400}
+FS = {d: 800 * d for d in range(1, 17)}                                # kHz: 800 kS/s after decimation d
 
 
 @pytest.fixture(scope="module")
@@ -88,7 +88,8 @@ def test_device_source_on_host_matches_oracle_bundled_capture(emu, oracle, sampl
     check(emu, oracle, cu8, flags_cli, 2, [cu8.size])
 
 
-@pytest.mark.parametrize("d,extra", [(3, []), (4, ["-s"]), (5, ["-s"]), (6, []), (2, [])])
+@pytest.mark.parametrize("d,extra", [(3, []), (4, ["-s"]), (5, ["-s"]), (6, []), (2, []),
+                                     (7, []), (9, ["-s"]), (11, []), (12, ["-s"]), (13, []), (15, ["-s"]), (16, [])])     # run-time D (k1_demod2<0, ...>)
 def test_device_source_on_host_matches_oracle_decimations_and_pushes(emu, oracle, wm, d, extra):
     kw = dict(t1c1_center_khz=325.0, s1_center_khz=-325.0) if "-s" in extra else {}
     cu8 = wm.synth_capture(seed=400 + d, n_samples=3 << 16, fs_khz=FS[d], kinds=15, frames_per_s=150.0, amplitude=40.0, **kw)[0]
