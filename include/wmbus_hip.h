@@ -110,6 +110,14 @@ typedef struct wmbus_cfg {
     unsigned clock_waves;       /* how a clock-recovery lane group's filter cascade (iir.h:49-77 behind rtl_wmbus.c:1089-1111) is laid onto
                                    waves: 4 = systolic, the sections on the four waves of a block (round 6; 0: the default); 1 = one wave,
                                    software-pipelined across the sections (rounds 1-5).  Same records in memory, same datagrams; A/B */
+    /* 0 (default): the input is at decimation x 800 kHz, as the reference demands ("use a multiple of 800kHz", rtl_wmbus.c:1274-1292).
+     * Otherwise the rate of the cu8 input in Hz (>= 800000): the context resamples it on the GPU to decimation x 800 kHz with the exact
+     * integer polyphase filter of wmbus_resampler_design() and decodes that stream.  wmbus_stage / wmbus_device_input /
+     * wmbus_process then take RAW bytes (max_push_bytes counts them); resampled bytes enter the pipeline in whole 4096-byte blocks,
+     * the rest waits for the next push (a push that completes no block yields no lines) and is dropped at the end of the input, as
+     * the reference drops a partial block.  wmbus_line.sample counts decimated samples of the resampled stream.  A rate equal to
+     * decimation x 800 kHz is the same as 0. */
+    unsigned input_rate_hz;
 } wmbus_cfg;
 
 enum { WMBUS_PREFILTER_BOXCAR = 0, WMBUS_PREFILTER_POLYPHASE = 1 };
@@ -128,7 +136,7 @@ typedef struct wmbus_line {
 
 /* Per-push timings measured with HIP events on the library's own stream (ms). */
 typedef struct wmbus_timing {
-    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel      */
+    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it */
     float clock_ms;             /* IIR clock recovery + time2 framer (incl. re-runs)  */
     float rla_ms;               /* run-length framer (incl. re-runs)                  */
     float gather_ms;            /* burst extraction (and, without debug views, the RSSI of the tiles the bursts touch) */
@@ -228,6 +236,21 @@ int  wmbus_selftest_fir(int device, const float *x, float *out, size_t n);
  * t1_c1_packet_decoder.h:671-699 / s1_packet_decoder.h:248-269) over the records of the context's last push again, `reps` times, without
  * any GPU work.  Returns the lines of one repetition; *seconds receives the wall clock of all of them. */
 long wmbus_debug_replay_decode(wmbus_ctx *ctx, unsigned reps, double *seconds);
+
+/* The resampler behind cfg.input_rate_hz; host only, no device needed.  out_hz / in_hz = L / M in lowest terms (L <= 32, M <= 1024,
+ * in_hz >= 800000, out_hz a multiple of 800000; else WMBUS_EINVAL).  taps (may be NULL: geometry only; cap = its int16 capacity,
+ * >= L * T) receives L phases of T = 16 * max(1, ceil(M / L)) taps, taps[p * T + k]: a Kaiser-windowed sinc (beta 8, cut-off
+ * 0.45 * min(in_hz, out_hz)) in Q14, every phase summing to exactly 16384.  With x = 2 * byte - 255 (0 before the stream starts),
+ * output n of a stream is, for I and Q alike,
+ *     acc  = sum over k < T of taps[((n * M) % L) * T + k] * x[floor(n * M / L) - k]
+ *     byte = clamp((acc + 255 * 16384 + 16384) >> 15, 0, 255)
+ * and exists once input floor(n * M / L) has been pushed: integers only, so the bytes do not depend on how the input is cut into pushes. */
+int  wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsigned *M, unsigned *T, int16_t *taps, size_t cap);
+/* Debug read (requires cfg.keep_taps and cfg.input_rate_hz): the resampled cu8 bytes the last push handed to the pipeline
+ * for one stream.  Returns the number of bytes written (0 for a push that completed no block), or a negative error. */
+long wmbus_read_resampled(wmbus_ctx *ctx, unsigned stream, uint8_t *out, size_t cap);
+/* Pushes of this context that launched the resampler kernel (0 for ever without cfg.input_rate_hz). */
+unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx);
 
 /* Number of visible HIP devices (0 if none). */
 int  wmbus_device_count(void);

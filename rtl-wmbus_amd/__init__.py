@@ -46,7 +46,8 @@ class Cfg(ctypes.Structure):
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
-                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint)]
+                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
+                ("input_rate_hz", ctypes.c_uint)]
 
 
 class Line(ctypes.Structure):
@@ -96,7 +97,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
-           "wmbus_debug_replay_decode"]
+           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches"]
 
 _lib = None
 
@@ -124,6 +125,9 @@ def lib():
         L.wmbus_read_tap.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, u, vp, sz]; L.wmbus_read_tap.restype = ctypes.c_long
         L.wmbus_read_chips.argtypes = [vp, ctypes.c_int, ctypes.c_int, u, vp, vp, sz]; L.wmbus_read_chips.restype = ctypes.c_long
         L.wmbus_device_count.restype = ctypes.c_int
+        L.wmbus_resampler_design.argtypes = [u, u, ctypes.POINTER(u), ctypes.POINTER(u), ctypes.POINTER(u), vp, sz]
+        L.wmbus_read_resampled.argtypes = [vp, u, vp, sz]; L.wmbus_read_resampled.restype = ctypes.c_long
+        L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
         L.wmbus_selftest_math.argtypes = [ctypes.c_int] + [vp] * 6 + [sz]
@@ -144,6 +148,20 @@ def lib():
 
 def device_count():
     return int(lib().wmbus_device_count())
+
+
+def resampler_design(in_hz, out_hz):
+    """wmbus_resampler_design (host only): (L, M, T, taps int16 [L, T]) of the exact integer resampler behind
+    Receiver(input_rate_hz=...); raises WmbusError for a ratio the library does not take."""
+    L_, M_, T_ = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+    rc = lib().wmbus_resampler_design(int(in_hz), int(out_hz), ctypes.byref(L_), ctypes.byref(M_), ctypes.byref(T_), None, 0)
+    if rc:
+        raise WmbusError(f"wmbus_resampler_design({in_hz}, {out_hz}) failed: {rc}")
+    taps = np.zeros((L_.value, T_.value), np.int16)
+    rc = lib().wmbus_resampler_design(int(in_hz), int(out_hz), ctypes.byref(L_), ctypes.byref(M_), ctypes.byref(T_), taps.ctypes.data, taps.size)
+    if rc:
+        raise WmbusError(f"wmbus_resampler_design({in_hz}, {out_hz}) failed: {rc}")
+    return L_.value, M_.value, T_.value, taps
 
 
 def pinned_array(nbytes):
@@ -186,7 +204,8 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               remove_dc=False, t1c1=True, s1=True, rla=True, time2=True, show_algorithm=True, device=0,
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
-              rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0):
+              rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
+              input_rate_hz=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -204,6 +223,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.rounds_on_host, c.rssi_full, c.rssi_dense_pm, c.bursts_to_host, c.k1_small_tile = int(rounds_on_host), int(rssi_full), int(rssi_dense_pm), int(bursts_to_host), int(k1_small_tile)
     c.k1_tiles_per_block = int(k1_tiles_per_block)
     c.clock_waves = int(clock_waves)
+    c.input_rate_hz = int(input_rate_hz)     # 0: the input is at decimation x 800 kHz; else the library resamples it on the GPU
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
     return c
@@ -412,6 +432,18 @@ class Receiver:
         if r < 0:
             raise WmbusError(f"read_tap({what}) failed: {r}")
         return out[:r]
+
+    def read_resampled(self, stream, cap=None):
+        """The resampled cu8 bytes the last push handed to the pipeline (input_rate_hz and keep_taps)."""
+        cap = cap or (int(self.cfg.max_push_bytes) * 2 + 8192 if self.cfg is not None else 1 << 24)
+        out = np.zeros(cap, np.uint8)
+        r = lib().wmbus_read_resampled(self._h, stream, out.ctypes.data, cap)
+        if r < 0:
+            raise WmbusError(f"read_resampled failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
+        return out[:r]
+
+    def resampler_launches(self):
+        return int(lib().wmbus_resampler_launches(self._h))
 
     def read_chips(self, chain, algo, stream, cap=1 << 22):
         w = np.zeros(cap, np.uint32)

@@ -19,6 +19,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -29,6 +30,7 @@
 #include "wm_decoder.h"
 #include "wm_dev.h"
 #include "wm_kernels.hip"
+#include "wm_resample_design.h"
 
 namespace {
 
@@ -124,6 +126,22 @@ struct wmbus_ctx {
     uint32_t cap[2] = {0, 0}, flags = 0;
     uint64_t in_stride = 0, n0 = 0;
     size_t staged = 0;
+    size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
+    /* cfg.input_rate_hz: the resampler in front of the demodulation kernel (wm_k0_resample.h).  wmbus_stage fills the RAW windows; K0
+     * writes the window of d_in the pipeline reads.  hist / rem are double-buffered like every carried state (a push reads half
+     * `cur`, writes the other).  Every capture advances in lock step, so the counters live here and travel as launch arguments. */
+    struct {
+        bool on = false;
+        uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
+        size_t raw_cap = 0; uint64_t raw_stride = 0;
+        uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
+        int16_t *d_taps = nullptr;                     /* [L][T] */
+        uint32_t *d_hist = nullptr;                    /* [2][S][T - 1] {I, Q} int16 */
+        uint8_t *d_rem = nullptr;                      /* [2][S][4096] */
+        uint64_t n_in = 0, n_out = 0;                  /* raw samples pushed / outputs produced so far */
+        size_t last_bytes = 0; uint32_t last_win = 0;  /* what the last push handed to the pipeline, and in which window */
+        unsigned long long launches = 0;
+    } k0;
     /* device buffers */
     uint8_t *d_in = nullptr;                           /* [n_win][S][in_stride] */
     uint8_t *d_hist = nullptr;                         /* [S][4096] the input history of the next push (see k_copy_hist) */
@@ -396,6 +414,13 @@ int wmbus_device_count(void)
     return n;
 }
 
+int wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsigned *M, unsigned *T, int16_t *taps, size_t cap)
+{
+    return k0_design(in_hz, out_hz, L, M, T, taps, cap) ? WMBUS_EINVAL : WMBUS_OK;
+}
+
+unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx) { return ctx ? ctx->k0.launches : 0ull; }
+
 const char *wmbus_last_error(const wmbus_ctx *ctx) { return ctx ? ctx->err : "null context"; }
 
 void wmbus_close(wmbus_ctx *c)
@@ -409,7 +434,7 @@ void wmbus_close(wmbus_ctx *c)
         std::lock_guard<std::mutex> lk(kc.m);
         if (kc.owner == c) { kc.last = nullptr; kc.owner = nullptr; }      /* nobody may wait on an event that is about to go */
     }
-    void *dev[] = {c->d_plans, c->d_rs_flags, c->d_rs_list, c->d_bad, c->d_bad_clk, c->d_hist, c->d_list_ema, c->d_spill, c->d_chain, c->d_list2, c->d_first_bad, c->d_ckpt, c->d_in, c->d_dphi, c->d_rssi, c->d_bits, c->d_lut, c->d_ema_head, c->d_ema_tail, c->d_ema_carry,
+    void *dev[] = {c->k0.d_raw, c->k0.d_taps, c->k0.d_hist, c->k0.d_rem, c->d_plans, c->d_rs_flags, c->d_rs_list, c->d_bad, c->d_bad_clk, c->d_hist, c->d_list_ema, c->d_spill, c->d_chain, c->d_list2, c->d_first_bad, c->d_ckpt, c->d_in, c->d_dphi, c->d_rssi, c->d_bits, c->d_lut, c->d_ema_head, c->d_ema_tail, c->d_ema_carry,
                    c->d_chips[0], c->d_chips[1], c->d_counts[0], c->d_counts[1], c->d_st_start[0], c->d_st_start[1],
                    c->d_st_final[0], c->d_st_final[1], c->d_st_carry[0], c->d_st_carry[1], c->d_list, c->d_scalars,
                    c->d_hits, c->d_pending};
@@ -441,6 +466,23 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
         return bail(fail(c, WMBUS_EINVAL, "atan_mode must be WMBUS_ATAN_LIBM, WMBUS_ATAN_APPROX1 or WMBUS_ATAN_APPROX2"));
     if (cfg->prefilter == WMBUS_PREFILTER_POLYPHASE && (cfg->decimation != 2 || cfg->simultaneous))
         return bail(fail(c, WMBUS_EINVAL, "the polyphase pre-filter is the 1.6 MS/s design of rtl_wmbus.c:258-294: decimation 2, no -s"));
+    c->push_cap = cfg->max_push_bytes;
+    std::vector<int16_t> k0_taps;
+    if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
+        unsigned L = 0, M = 0, T = 0;
+        k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
+        const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
+        if (why) return bail(fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u));
+        c->k0.on = true; c->k0.L = L; c->k0.M = M; c->k0.T = T;
+        c->k0.raw_cap = cfg->max_push_bytes;
+        c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
+        /* the pipeline behind K0 is sized for what a full raw push resamples to, plus the remainder in front of it */
+        const uint64_t most = ((uint64_t)(cfg->max_push_bytes / 2u) * L + M - 1u) / M * 2u;
+        c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
+        const uint32_t tile = k0_pick_tile(L, M, T);
+        if (!tile) return bail(fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T));
+        c->k0.tile = tile; c->k0.lds = k0_lds_bytes(L, M, T, tile);
+    }
     if (cfg->device < 0 || cfg->device >= WM_MAX_DEVICES) return bail(fail(c, WMBUS_EINVAL, "device must be 0..%d", WM_MAX_DEVICES - 1));
     if (wmbus_device_count() <= cfg->device) return bail(fail(c, WMBUS_ENODEVICE, "no HIP device %d (this library has no CPU fallback)", cfg->device));
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(fail(c, WMBUS_EDEVICE, "hipSetDevice(%d) failed", cfg->device));
@@ -467,7 +509,7 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
          * segments is as long as its one lane with a full warm-up, 57 344 samples; with 16384 that lane is 40 960 (one capture, ms per push of
          * 2^17 / 2^18 / 2^19 input samples: 5.1 / 4.6 / 3.9 -> 2.8 / 3.4 / 3.4; 2^22: 4.3 against 4.8, so long pushes keep 32768) */
         {
-            const uint64_t mp = cfg->max_push_bytes / 2u / std::max(1u, cfg->decimation);      /* a push's decimated samples at most */
+            const uint64_t mp = c->push_cap / 2u / std::max(1u, cfg->decimation);      /* a push's decimated samples at most */
             if (c->clk_form == 4u && c->S < 64u && mp > 32768u && mp <= (1u << 19)) c->C[1] = 16384u;      /* <= 32768: one segment from its exact start */
         }
         if (cfg->seg_len) c->C[1] = cfg->seg_len;
@@ -500,7 +542,7 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     if (cfg->simultaneous) c->rla_rounds = std::min<unsigned>(c->rla_rounds + 1u, WM_MAX_ROUNDS + 1u);
     c->T = (uint32_t)WM_K1_TILE2;
     const uint32_t T = c->T;
-    const uint64_t max_samples = cfg->max_push_bytes / 2;
+    const uint64_t max_samples = c->push_cap / 2;
     c->ntiles_cap = (uint32_t)((max_samples / c->d + 1 + 8 + T - 1) / T);
     c->Mcap = (c->ntiles_cap * T + 255) / 256 * 256;     /* whole tiles (partial tiles still store full runs); slicer-word rows 32-byte aligned */
     for (int a = 0; a < 2; a++) c->nseg_cap[a] = (c->Mcap + c->C[a] - 1) / c->C[a];
@@ -513,7 +555,7 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     c->cap[0] = (c->C[0] / 2 + 8 + 7) / 8 * 8;
     /* K1 stages whole tiles: the partial last tile of a push reads up to (tile + halo) x d input samples past the
      * staged bytes (never used: they only feed outputs beyond M) -- the row must hold them */
-    c->in_stride = (WM_HIST_BYTES + cfg->max_push_bytes + 2ull * (WM_K1_TILE2 + WM_K1_HALO + 16) * WM_MAX_DECIM + WM_IN_SLACK + 255) / 256 * 256;
+    c->in_stride = (WM_HIST_BYTES + c->push_cap + 2ull * (WM_K1_TILE2 + WM_K1_HALO + 16) * WM_MAX_DECIM + WM_IN_SLACK + 255) / 256 * 256;
 
     const uint64_t rows = 2ull * c->S;
     hipError_t e = hipSuccess;
@@ -529,6 +571,12 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     A(hipEventCreateWithFlags(&c->ev_turn, hipEventDisableTiming));
     A(dalloc(&c->d_in, (size_t)c->in_stride * c->S * c->n_win));
     A(dalloc(&c->d_hist, (size_t)WM_HIST_BYTES * c->S));
+    if (c->k0.on) {
+        A(dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->S * c->n_win));
+        A(dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
+        A(dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
+        A(dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
+    }
     A(dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
     A(dalloc(&c->d_bits, (size_t)rows * (c->Mcap / 32)));
@@ -612,6 +660,12 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     }
     if (e != hipSuccess) return bail(fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e)));
 
+    if (c->k0.on) {                                          /* history before a stream's first sample: x = 0 */
+        A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
+        A(hipMemsetAsync(c->k0.d_rem, 128, (size_t)2 * c->S * WMBUS_BLOCK_BYTES, c->stream));
+        A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+        A(hipStreamSynchronize(c->stream));                  /* k0_taps leaves with this function */
+    }
     /* initial state = the reference's zero-initialised statics */
     A(hipMemsetAsync(c->d_ema_carry, 0, 2 * rows * sizeof(float), c->stream));
     /* a disabled chain (-p T / -p S) never writes its hand-off records: they must compare equal, not hold what an
@@ -673,13 +727,14 @@ static int wm_stage_all(wmbus_ctx *c, const uint8_t *slab, size_t pitch, size_t 
     if (nbytes > c->cfg.max_push_bytes || nbytes % WMBUS_BLOCK_BYTES || pitch < nbytes) return fail(c, WMBUS_EINVAL, "stage: nbytes must be a multiple of 4096 and <= max_push_bytes");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->in_flight && c->n_win == 1) return fail(c, WMBUS_EINVAL, "stage: a push is in flight and the context has one input window (cfg.input_windows = 2 overlaps them)");
-    HIPCHK(c, hipMemcpy2DAsync(wmbus_device_input(c, 0), c->in_stride, slab, pitch, nbytes, c->S, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipMemcpy2DAsync(wmbus_device_input(c, 0), c->k0.on ? c->k0.raw_stride : c->in_stride, slab, pitch, nbytes, c->S, hipMemcpyHostToDevice, c->copy_stream));
     return WMBUS_OK;
 }
 
 void *wmbus_device_input(wmbus_ctx *c, unsigned stream)
 {
     if (!c || stream >= c->S) return nullptr;
+    if (c->k0.on) return c->k0.d_raw + ((size_t)c->fill * c->S + stream) * c->k0.raw_stride;      /* raw bytes: K0 fills the pipeline's window */
     return c->d_in + ((size_t)c->fill * c->S + stream) * c->in_stride + WM_HIST_BYTES;
 }
 
@@ -873,6 +928,37 @@ static int launch_k3(wmbus_ctx *c, bool again)
     return 0;
 }
 
+/* cfg.input_rate_hz: the launch arguments of K0 for a push of `raw_bytes`, and the host's copy of the counters moved on.  Returns the
+ * bytes the pipeline gets from this push: the whole 4096-byte blocks of (remainder + what this push produces); may be 0. */
+static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
+{
+    auto &k = c->k0;
+    const uint32_t n_in = (uint32_t)(raw_bytes / 2u);
+    const uint64_t out_end = ((k.n_in + n_in) * (uint64_t)k.L + k.M - 1u) / k.M;      /* output n exists once input floor(n M / L) is in: n M < pushed L */
+    const uint32_t n_out = (uint32_t)(out_end - k.n_out);
+    const size_t total = (size_t)k.rem + 2u * (size_t)n_out, whole = total / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES;
+    *ka = K0Args{};
+    ka->raw = k.d_raw + (size_t)c->fill * c->S * k.raw_stride; ka->raw_stride = k.raw_stride;
+    ka->out = c->d_in + (size_t)c->fill * c->S * c->in_stride + WM_HIST_BYTES; ka->out_stride = c->in_stride;
+    ka->taps = k.d_taps;
+    ka->hist_in = k.d_hist + (size_t)k.cur * c->S * (k.T - 1u); ka->hist_out = k.d_hist + (size_t)(k.cur ^ 1u) * c->S * (k.T - 1u);
+    ka->rem_in = k.d_rem + (size_t)k.cur * c->S * WMBUS_BLOCK_BYTES; ka->rem_out = k.d_rem + (size_t)(k.cur ^ 1u) * c->S * WMBUS_BLOCK_BYTES;
+    ka->n_first = k.n_out; ka->in_first = k.n_in; ka->n_in = n_in; ka->n_out = n_out;
+    ka->rem_prev = k.rem; ka->keep_from = (uint32_t)whole;
+    ka->L = k.L; ka->M = k.M; ka->T = k.T; ka->tile = k.tile;
+    k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
+    k.last_bytes = whole; k.last_win = c->fill;
+    return whole;
+}
+
+static int k0_launch(wmbus_ctx *c, const K0Args &ka)
+{
+    hipLaunchKernelGGL(k0_resample, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS), c->k0.lds, c->stream, ka);
+    HIPCHK(c, hipGetLastError());
+    c->k0.launches++;
+    return WMBUS_OK;
+}
+
 static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
 {
     if (nbytes == 0 || nbytes > c->cfg.max_push_bytes || nbytes % WMBUS_BLOCK_BYTES)
@@ -880,6 +966,8 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "process: previous push not collected");
     HIPCHK(c, hipSetDevice(c->cfg.device));            /* HIP's current device is per host thread; a context may be driven from any */
     if (c->poisoned) return fail(c, WMBUS_EDEVICE, "process: an earlier internal error left this context unusable; close it");
+    K0Args k0a{};
+    if (c->k0.on) nbytes = k0_plan(c, nbytes, &k0a);   /* from here on nbytes counts RESAMPLED bytes: what the pipeline sees (0: no whole block yet) */
     gettimeofday(&c->arrival, nullptr);
     if (c->committed) { c->carry_in ^= 1u; c->committed = false; }     /* the previous push's end state is this one's start state */
     const uint32_t n_new = (uint32_t)(nbytes / 2);
@@ -908,6 +996,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     hipLaunchKernelGGL(k_copy_hist, dim3(c->S), dim3(256), 0, c->stream, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint64_t)0, win, c->in_stride);
+    if (c->k0.on && g.M == 0) { const int rc0 = k0_launch(c, k0a); if (rc0) return rc0; }      /* a push that completes no block: the resampler alone */
     if (g.M > 0) {
         HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, c->zero_words * sizeof(uint32_t), c->stream));     /* scalars, region flags, spill chains */
         /* K1 */
@@ -928,6 +1017,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             std::lock_guard<std::mutex> lk(kc.m);
             if (kc.last && kc.owner != c) HIPCHK(c, hipStreamWaitEvent(c->stream, kc.last, 0));
             HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+            if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
             /* The hand-over of the turn costs 0.15-0.2 ms (the next context's stream sits in an event wait on another
              * hardware queue; r03 trace: median 128 us between one K1 and the next, eight times per step = 5 % of it).
              * So the turn is handed over EARLY: a push's tiles leave in two launches, the event the next context waits for
@@ -1499,6 +1589,17 @@ long wmbus_read_tap(wmbus_ctx *c, const char *what, int chain, unsigned stream, 
         if (hipMemcpy(w.data(), c->d_bits + row * (c->Mcap / 32), w.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return WMBUS_EDEVICE;
         for (size_t k = 0; k < n; k++) ((uint8_t *)dst)[k] = (w[k >> 5] >> (k & 31)) & 1u;
     } else return WMBUS_EINVAL;
+    return (long)n;
+}
+
+long wmbus_read_resampled(wmbus_ctx *c, unsigned stream, uint8_t *out, size_t cap)
+{
+    if (!c || !out || stream >= c->S) return WMBUS_EINVAL;
+    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and cfg.input_rate_hz");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_resampled: collect the push first");
+    const size_t n = std::min(cap, c->k0.last_bytes);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n) HIPCHK(c, hipMemcpy(out, c->d_in + ((size_t)c->k0.last_win * c->S + stream) * c->in_stride + WM_HIST_BYTES, n, hipMemcpyDeviceToHost));
     return (long)n;
 }
 

@@ -1,0 +1,228 @@
+/*
+ * wm_k0_resample.h -- K0: exact integer rational resampler in front of the demodulation kernel (cfg.input_rate_hz).
+ *
+ * The reference takes captures at a multiple of 800 kHz only (rtl_wmbus.c:1274-1292: "use a multiple of 800kHz").  K0 turns a cu8
+ * capture at any rate Fin with Fout / Fin = L / M (L <= 32, M <= 1024) into an ordinary cu8 stream at Fout = decimation x 800 kHz in
+ * the context's device input window; K1 and everything behind it run unchanged on that stream.
+ *
+ * The arithmetic is the definition (include/wmbus_hip.h, wmbus_resampler_design; tests/resample_ref.py restates it in numpy):
+ *   x = 2u - 255 per byte; history before the stream's first sample is x = 0
+ *   output n: phase p = (n M) mod L, newest input b = floor(n M / L), acc = sum_{k < T} taps[p][k] x[b - k]      (int32, exact)
+ *   byte = clamp((acc + 255 * 16384 + 16384) >> 15, 0, 255)
+ * Pure integers: nothing here depends on a float, so the bytes do not depend on tile, block or push boundaries.
+ *
+ * Shape: block = (tile of consecutive outputs, capture).  The input span of the tile (tile M / L + T samples) goes once into LDS
+ * as one dword per sample, {I, Q} as two int16, loaded with aligned dword loads of two samples; the L x T int16 taps sit beside
+ * it.  A lane owns K0_OPL outputs of ONE phase (n, n + L, n + 2L, ...: their newest inputs lie exactly M apart), so a dword of two
+ * taps is read once for all of them; per tap pair and output two sample dwords are read, V_PERM_B32 regroups them into {I, I'} and
+ * {Q, Q'} and V_DOT2_I32_I16 does the two multiply-adds of each.  The bytes are gathered in LDS and leave as 16-bit vector stores
+ * of consecutive lanes (the window position of a push's first byte is even, not dword aligned: it follows the remainder).
+ *
+ * Carried from push to push, per capture, all on the device and double-buffered like every other carried state: the last T - 1
+ * samples (as {I, Q} int16 pairs) and the bytes behind the last whole 4096-byte block (the pipeline takes whole blocks, as the
+ * reference's fread does).  The output counter is the same for every capture of a context (they advance in lock step) and
+ * travels as a launch argument, like WmPush.n0.
+ */
+#ifndef WM_K0_RESAMPLE_H
+#define WM_K0_RESAMPLE_H
+
+#include <stdint.h>
+
+#define WM_K0_THREADS   256u
+#define WM_K0_OPL       4u         /* outputs of one phase per lane */
+#define WM_K0_MAX_L     32u
+#define WM_K0_MAX_M     1024u
+#define WM_K0_MAX_T     512u
+#define WM_K0_OUT_BIAS  (255 * 16384 + 16384)
+
+struct K0Args {
+    const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
+    uint64_t raw_stride;
+    uint8_t *out;                /* [S][out_stride] first byte behind the window's history                    */
+    uint64_t out_stride;
+    const int16_t *taps;         /* [L][T]                                                                    */
+    const uint32_t *hist_in;     /* [S][T - 1] the T - 1 samples in front of this push, {I, Q} int16          */
+    uint32_t *hist_out;          /* the same for the next push                                                */
+    const uint8_t *rem_in;       /* [S][4096] bytes produced by earlier pushes and not yet handed on          */
+    uint8_t *rem_out;
+    uint64_t n_first;            /* output counter at the start of this push                                  */
+    uint64_t in_first;           /* input samples of earlier pushes                                           */
+    uint32_t n_in, n_out;        /* input samples / outputs of this push                                      */
+    uint32_t rem_prev;           /* bytes in rem_in                                                           */
+    uint32_t keep_from;          /* window bytes from here on wait for the next push: they go to rem_out too  */
+    uint32_t L, M, T, tile;      /* tile: outputs per block (even)                                            */
+};
+
+/* samples of LDS a block needs for its input span: every lane computes WM_K0_OPL outputs, so a partial last group reads
+ * (and discards) up to WM_K0_OPL * L outputs past the tile */
+__host__ __device__ __forceinline__ uint32_t k0_span(uint32_t L, uint32_t M, uint32_t T, uint32_t tile)
+{
+    const uint32_t groups = (tile + WM_K0_OPL * L - 1u) / (WM_K0_OPL * L);
+    const uint32_t t_max = groups * WM_K0_OPL * L - 1u;
+    return (T + 1u + (L - 1u + t_max * M) / L + 1u + 1u) & ~1u;
+}
+/* a phase's taps in LDS: T / 2 dwords and one of padding -- the lanes of a wave read the same tap pair of up to L different
+ * phases at once, and rows T / 2 = 16, 32, ... dwords apart would all start in the same few of the 64 banks */
+__host__ __device__ __forceinline__ uint32_t k0_row(uint32_t T) { return T / 2u + 1u; }
+/* dynamic LDS of a block, bytes: span dwords | taps | out bytes */
+__host__ __device__ __forceinline__ uint32_t k0_lds_bytes(uint32_t L, uint32_t M, uint32_t T, uint32_t tile)
+{
+    return 4u * k0_span(L, M, T, tile) + 4u * L * k0_row(T) + 2u * tile;
+}
+/* Outputs per block.  A lane's work item is WM_K0_OPL outputs of one phase, so a tile of WM_K0_OPL * L * g outputs is g * L items:
+ * g = floor(512 / L) gives the 256 threads two full trips (481 ... 512 items); fewer where the block's LDS would pass 64 KiB
+ * (two blocks and more in a CU's 160 KiB).  0: not even one group fits. */
+__host__ __device__ __forceinline__ uint32_t k0_pick_tile(uint32_t L, uint32_t M, uint32_t T)
+{
+    uint32_t g = 2u * WM_K0_THREADS / L;
+    while (g > 1u && k0_lds_bytes(L, M, T, WM_K0_OPL * L * g) > 65536u) g--;
+    return k0_lds_bytes(L, M, T, WM_K0_OPL * L * g) > 65536u ? 0u : WM_K0_OPL * L * g;
+}
+
+__device__ __forceinline__ uint32_t k0_pack(uint32_t byte_pair)        /* cu8 {I, Q} -> {2I - 255, 2Q - 255} as two int16 */
+{
+    const int32_t i = 2 * (int32_t)(byte_pair & 0xFFu) - 255, q = 2 * (int32_t)((byte_pair >> 8) & 0xFFu) - 255;
+    return ((uint32_t)i & 0xFFFFu) | ((uint32_t)q << 16);
+}
+
+/* a.lo * b.lo + a.hi * b.hi + c on int16 halves, exact in int32 */
+__device__ __forceinline__ int32_t k0_dot2(uint32_t a, uint32_t b, int32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short k0_s2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(k0_s2, a), __builtin_bit_cast(k0_s2, b), c, false);
+#else
+    return c + (int32_t)(int16_t)(a & 0xFFFFu) * (int32_t)(int16_t)(b & 0xFFFFu) + (int32_t)(int16_t)(a >> 16) * (int32_t)(int16_t)(b >> 16);
+#endif
+}
+/* {lo16(s0), lo16(s1)} and {hi16(s0), hi16(s1)} */
+__device__ __forceinline__ uint32_t k0_lo_pair(uint32_t s0, uint32_t s1)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(s1, s0, 0x05040100u);
+#else
+    return (s0 & 0xFFFFu) | (s1 << 16);
+#endif
+}
+__device__ __forceinline__ uint32_t k0_hi_pair(uint32_t s0, uint32_t s1)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(s1, s0, 0x07060302u);
+#else
+    return (s0 >> 16) | (s1 & 0xFFFF0000u);
+#endif
+}
+__device__ __forceinline__ uint32_t k0_byte(int32_t acc)
+{
+    const int32_t v = (acc + WM_K0_OUT_BIAS) >> 15;
+    return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+
+/* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
+__device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds)
+{
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
+    const uint32_t L = a.L, M = a.M, T = a.T;
+    const uint32_t span = k0_span(L, M, T, a.tile);
+    uint32_t *xs = lds;                                          /* [span] {I, Q} */
+    const uint32_t *tp = lds + span;                             /* [L][k0_row(T)] tap pairs */
+    uint16_t *ob = (uint16_t *)(lds + span + L * k0_row(T));     /* [tile] output {I, Q} bytes */
+    const uint8_t *raw = a.raw + (uint64_t)s * a.raw_stride;
+    uint8_t *out = a.out + (uint64_t)s * a.out_stride;
+    const uint32_t *hist_in = a.hist_in + (uint64_t)s * (T - 1u);
+
+    const uint32_t t_first = blockIdx.x * a.tile;                /* first output of the tile within the push */
+    if (t_first >= a.n_out) return;
+    const uint32_t ntile = a.n_out - t_first < a.tile ? a.n_out - t_first : a.tile;
+    const uint64_t nm = (a.n_first + t_first) * (uint64_t)M;
+    const uint64_t q0 = nm / L;                                  /* newest input of the tile's first output, index within the stream */
+    const uint32_t r0 = (uint32_t)(nm - q0 * L);                 /* its phase */
+    /* LDS sample 0 is input (q0 - (T - 1) - sh) of the stream, sh in {0, 1} so that its index within the push is even */
+    const int64_t rel = (int64_t)(q0 - a.in_first) - (int64_t)(T - 1u);     /* within the push; negative: history */
+    const uint32_t sh = (uint32_t)(rel & 1);
+    const int64_t base = rel - (int64_t)sh;
+
+    for (uint32_t j = 2u * tid; j < span; j += 2u * nthr) {      /* two samples per lane and trip: one aligned dword of the push */
+        const int64_t r = base + (int64_t)j;
+        uint32_t v0 = 0u, v1 = 0u;
+        if (r >= 0) {
+            if (r < (int64_t)a.n_in) {                           /* n_in is even: r + 1 lies inside too */
+                const uint32_t w = *(const uint32_t *)(raw + 2u * (uint64_t)r);
+                v0 = k0_pack(w); v1 = k0_pack(w >> 16);
+            }
+        } else {                                                 /* r <= -2: both samples are history (the oldest slot, index -T, is never read) */
+            const int64_t h = r + (int64_t)(T - 1u);
+            if (h >= 0) v0 = hist_in[h];
+            if (h + 1 >= 0) v1 = hist_in[h + 1];
+        }
+        xs[j] = v0; xs[j + 1u] = v1;
+    }
+    {
+        const uint32_t *tg = (const uint32_t *)a.taps;           /* T is a multiple of 16: rows are dword aligned */
+        uint32_t *tl = lds + span;
+        for (uint32_t j = tid; j < L * T / 2u; j += nthr) tl[j / (T / 2u) * k0_row(T) + j % (T / 2u)] = tg[j];
+    }
+    if (blockIdx.x == 0) {
+        /* the next push's history: the last T - 1 samples of this one (a push is at least 2048 samples) */
+        uint32_t *hist_out = a.hist_out + (uint64_t)s * (T - 1u);
+        for (uint32_t j = tid; j < T - 1u; j += nthr) {
+            const uint32_t r = a.n_in - (T - 1u) + j;
+            hist_out[j] = k0_pack(*(const uint16_t *)(raw + 2u * (uint64_t)r));
+        }
+        /* the bytes earlier pushes left: in front of this push's in the window */
+        const uint16_t *rin = (const uint16_t *)(a.rem_in + (uint64_t)s * 4096u);
+        uint16_t *rout = (uint16_t *)(a.rem_out + (uint64_t)s * 4096u);
+        for (uint32_t j = tid; j < a.rem_prev / 2u; j += nthr) {
+            const uint16_t v = rin[j];
+            *(uint16_t *)(out + 2u * j) = v;
+            if (2u * j >= a.keep_from) rout[(2u * j - a.keep_from) / 2u] = v;
+        }
+    }
+    __syncthreads();
+
+    const uint32_t groups = (ntile + WM_K0_OPL * L - 1u) / (WM_K0_OPL * L);
+    for (uint32_t w = tid; w < groups * L; w += nthr) {
+        const uint32_t t0 = (w / L) * WM_K0_OPL * L + w % L;     /* this lane's outputs: t0 + i L */
+        const uint32_t v = r0 + t0 * M;
+        const uint32_t p = v % L;
+        const uint32_t b0 = sh + (T - 1u) + v / L;               /* LDS index of the newest input of output t0; output t0 + i L: + i M */
+        const uint32_t *row = tp + p * k0_row(T);
+        int32_t ai[WM_K0_OPL], aq[WM_K0_OPL];
+#pragma unroll
+        for (uint32_t i = 0; i < WM_K0_OPL; i++) { ai[i] = 0; aq[i] = 0; }
+        for (uint32_t k = 0; k < T; k += 2u) {
+            const uint32_t h2 = row[k / 2u];                     /* {taps[p][k], taps[p][k + 1]} */
+#pragma unroll
+            for (uint32_t i = 0; i < WM_K0_OPL; i++) {
+                const uint32_t s0 = xs[b0 + i * M - k], s1 = xs[b0 + i * M - k - 1u];
+                ai[i] = k0_dot2(k0_lo_pair(s0, s1), h2, ai[i]);
+                aq[i] = k0_dot2(k0_hi_pair(s0, s1), h2, aq[i]);
+            }
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < WM_K0_OPL; i++) {
+            const uint32_t t = t0 + i * L;
+            if (t < ntile) ob[t] = (uint16_t)(k0_byte(ai[i]) | (k0_byte(aq[i]) << 8));
+        }
+    }
+    __syncthreads();
+
+    const uint32_t o0 = a.rem_prev + 2u * t_first;               /* window byte of the tile's first output */
+    uint16_t *rout = (uint16_t *)(a.rem_out + (uint64_t)s * 4096u);
+    for (uint32_t t = tid; t < ntile; t += nthr) {
+        const uint16_t v = ob[t];
+        const uint32_t o = o0 + 2u * t;
+        *(uint16_t *)(out + o) = v;
+        if (o >= a.keep_from) rout[(o - a.keep_from) / 2u] = v;
+    }
+}
+
+#if defined(__HIPCC__)
+__global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block(a, k0_lds);
+}
+#endif
+
+#endif

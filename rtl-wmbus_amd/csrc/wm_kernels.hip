@@ -1,6 +1,8 @@
 /*
  * wm_kernels.hip -- gfx950 kernels for the rtl-wmbus hot path.
  *
+ *   k0_resample  option (cfg.input_rate_hz): exact integer polyphase resampler, cu8 at any rate -> cu8 at decimation x 800 kHz
+ *                in the input window; everything below runs unchanged behind it.    (no counterpart: rtl_wmbus.c:1274-1292)
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.
@@ -31,6 +33,7 @@
 #include "wm_dev.h"
 #include "wm_exact.h"
 
+#include "wm_k0_resample.h"
 #include "wm_k1_demod.h"
 #include "wm_k2_common.h"
 #include "wm_k2_clock.h"

@@ -46,12 +46,14 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-r 0 to disable run length algorithm\n");
     fprintf(stdout, "\t-t 0 to disable time2 algorithm\n");
     fprintf(stdout, "\t-d 2 set decimation rate to 2 (defaults to 2 if omitted)\n");
+    fprintf(stdout, "\t   (this back end decimates by 1 ... 16: -d 17 and beyond, which the reference accepts, are refused)\n");
     fprintf(stdout, "\t-v show used algorithm in the output\n");
     fprintf(stdout, "\t-V show version\n");
     fprintf(stdout, "\t-s receive S1 and T1/C1 datagrams simultaneously. rtl_sdr _MUST_ be set to 868.625MHz (-f 868.625M)\n");
     fprintf(stdout, "\t-p [T,S] to disable processing T1/C1 or S1 mode\n");
     fprintf(stdout, "\t-f exit if flow of incoming data stops\n");
-    fprintf(stdout, "\t   (this back end decimates by 1 ... 16: -d 17 and beyond, which the reference accepts, are refused)\n");
+    fprintf(stdout, "\t-R rate of the input in samples/s when it is not -d x 800 kHz (2048000, 2.048M, 2048k): resampled on the GPU to -d x 800 kHz\n");
+    fprintf(stdout, "\t   (output rate / input rate = L / M in lowest terms with L <= 32, M <= 1024; at least 800k; with -P only to 1.6 MS/s)\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -318,6 +320,22 @@ static void finish(int rc)
     _exit(rc);
 }
 
+/* -R: "2048000" | "2.048M" | "2048k" -> Hz; 0 if it is not a rate */
+static unsigned parse_rate(const char *arg)
+{
+    char *end;
+    const double v = strtod(arg, &end);
+    double mul = 1.;
+    if (end == arg || !(v > 0.)) return 0;
+    if (*end == 'M' || *end == 'm') { mul = 1e6; end++; }
+    else if (*end == 'k' || *end == 'K') { mul = 1e3; end++; }
+    if (*end) return 0;
+    const double hz = v * mul + 0.5;
+    if (hz < 1. || hz > 4294967295.) return 0;
+    const unsigned r = (unsigned)hz;
+    return (double)r - v * mul > 1e-3 || v * mul - (double)r > 1e-3 ? 0 : r;      /* a whole number of Hz */
+}
+
 /* -G: "3" | "all" | "0,2,5" -> device list; returns the count or -1 */
 static int parse_devices(const char *arg, int *devs, int cap)
 {
@@ -369,7 +387,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SF")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -401,6 +419,10 @@ int main(int argc, char **argv)
         case 'L': max_latency_ms = (unsigned)strtoul(optarg, NULL, 10); break;
         case 'S': stats = 1; break;
         case 'F': cfg.tolerance_mode = 1; break;
+        case 'R':
+            cfg.input_rate_hz = parse_rate(optarg);
+            if (!cfg.input_rate_hz) { print_usage(argv[0]); return EXIT_FAILURE; }
+            break;
         default: print_usage(argv[0]); return EXIT_FAILURE;
         }
     }
@@ -412,6 +434,11 @@ int main(int argc, char **argv)
     if (cfg.decimation == 0 && !cfg.simultaneous) cfg.decimation = 1;
     if (cfg.decimation == 0 || cfg.decimation > 16) {
         fprintf(stderr, "rtl_wmbus_hip: -d %u: this back end decimates by 1..16 (-d 0 without -s is -d 1)\n", cfg.decimation);
+        return EXIT_FAILURE;
+    }
+    /* -R: a ratio the resampler does not take is a bad option (usage text), decided here without a device */
+    if (cfg.input_rate_hz && wmbus_resampler_design(cfg.input_rate_hz, cfg.decimation * 800000u, NULL, NULL, NULL, NULL, 0)) {
+        print_usage(argv[0]);
         return EXIT_FAILURE;
     }
 

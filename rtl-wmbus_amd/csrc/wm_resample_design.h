@@ -1,0 +1,73 @@
+/* wm_resample_design.h -- host side of K0 (wm_k0_resample.h): the polyphase taps, designed in double by the library.
+ * Part of wm_api.hip's translation unit; needs no device.
+ *
+ * L / M = out_hz / in_hz reduced.  Prototype: Kaiser-windowed sinc (beta 8) of N = L T taps at the rate L in_hz, cut-off
+ * 0.45 min(in_hz, out_hz), T = 16 max(1, ceil(M / L)).  Phase p owns prototype taps p, p + L, p + 2L, ...; every phase is scaled
+ * to sum 1, multiplied by 16384 and rounded to int16, then its largest tap (first index of the largest magnitude) takes the
+ * rest so that EVERY phase sums to exactly 16384: no phase-dependent gain, and the half-LSB offset of the output stays exact. */
+#ifndef WM_RESAMPLE_DESIGN_H
+#define WM_RESAMPLE_DESIGN_H
+
+namespace {
+
+double k0_bessel_i0(double x)
+{
+    double sum = 1., term = 1.;
+    const double q = x * x / 4.;
+    for (int k = 1; k < 200; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < sum * 1e-18) break;
+    }
+    return sum;
+}
+
+/* 0, or a message for WMBUS_EINVAL.  taps may be NULL (geometry only). */
+const char *k0_design(unsigned in_hz, unsigned out_hz, unsigned *pL, unsigned *pM, unsigned *pT, int16_t *taps, size_t cap)
+{
+    if (in_hz < 800000u) return "input_rate_hz must be at least 800000";
+    if (out_hz == 0u || out_hz % 800000u) return "the output rate must be a multiple of 800000";
+    const unsigned g = std::gcd(in_hz, out_hz);
+    const unsigned L = out_hz / g, M = in_hz / g;
+    if (L > WM_K0_MAX_L || M > WM_K0_MAX_M) return "input_rate_hz: output rate / input rate = L / M in lowest terms needs L <= 32 and M <= 1024";
+    const unsigned T = 16u * std::max(1u, (M + L - 1u) / L);
+    if (T > WM_K0_MAX_T) return "input_rate_hz: more than 32 input samples per output sample";
+    if (pL) *pL = L;
+    if (pM) *pM = M;
+    if (pT) *pT = T;
+    if (!taps) return nullptr;
+    if (cap < (size_t)L * T) return "resampler design: tap buffer too small";
+    const size_t N = (size_t)L * T;
+    std::vector<double> h(N);
+    const double fc = 0.45 * (double)std::min(in_hz, out_hz), fs = (double)L * (double)in_hz, mid = ((double)N - 1.) / 2.;
+    const double i0b = k0_bessel_i0(8.);
+    for (size_t i = 0; i < (N + 1) / 2; i++) {                  /* one half computed, the other mirrored: exactly symmetric */
+        const double t = (double)i - mid, a = 2. * fc / fs * t;
+        const double sinc = a == 0. ? 1. : sin(M_PI * a) / (M_PI * a);
+        const double r = t / mid;
+        h[i] = h[N - 1 - i] = sinc * k0_bessel_i0(8. * sqrt(std::max(0., 1. - r * r))) / i0b;
+    }
+    for (unsigned p = 0; p < L; p++) {
+        /* phases p and L - 1 - p are mirror images: one sum serves both, so that they round alike */
+        const unsigned pa = std::min(p, L - 1u - p);
+        double sum = 0.;
+        for (unsigned k = 0; k < T; k++) sum += h[pa + (size_t)L * k];
+        long total = 0, abs_total = 0; unsigned big = 0; long big_mag = -1;
+        for (unsigned k = 0; k < T; k++) {
+            const long v = lround(h[p + (size_t)L * k] / sum * 16384.);
+            taps[(size_t)p * T + k] = (int16_t)v;
+            total += v;
+            if (labs(v) > big_mag) { big_mag = labs(v); big = k; }
+        }
+        const long fixed = (long)taps[(size_t)p * T + big] + (16384 - total);
+        if (fixed > 32767 || fixed < -32768) return "resampler design: a tap leaves int16";
+        taps[(size_t)p * T + big] = (int16_t)fixed;
+        for (unsigned k = 0; k < T; k++) abs_total += labs((long)taps[(size_t)p * T + k]);
+        /* |acc| <= 255 sum|taps|: far inside int32 (the kernel's accumulator) and, with the output bias, inside 2^31 */
+        if (255l * abs_total + WM_K0_OUT_BIAS >= (1l << 30)) return "resampler design: accumulator bound exceeded";
+    }
+    return nullptr;
+}
+
+}  // namespace
+#endif
