@@ -118,7 +118,20 @@ typedef struct wmbus_cfg {
      * the reference drops a partial block.  wmbus_line.sample counts decimated samples of the resampled stream.  A rate equal to
      * decimation x 800 kHz is the same as 0. */
     unsigned input_rate_hz;
+    /* Sample format of the input, WMBUS_FMT_* (0 = cu8, what an RTL-SDR delivers and the reference reads), and a linear input gain in
+     * Q8, 1 ... 65535 = x 1/256 ... x 256 (0 means 256 = x 1).  The arithmetic is defined below, next to wmbus_resampler_design().
+     * With a format other than cu8 or a gain other than x 1 the context converts on the GPU, inside the resampler where cfg.input_rate_hz
+     * asks for one, else in a conversion kernel of its own; the semantics follow input_rate_hz: wmbus_stage / wmbus_device_input /
+     * wmbus_process and max_push_bytes count RAW bytes (2, 2, 4, 8 per sample; still multiples of 4096), converted bytes enter the
+     * pipeline in whole 4096-byte blocks, the rest waits for the next push, wmbus_line.sample counts decimated samples of the converted
+     * stream.  cu8 with gain 0 or 256 at the native rate is the path it always was: no extra kernel, no extra buffer. */
+    unsigned input_format;
+    unsigned input_gain_q8;
 } wmbus_cfg;
+
+/* cs8: int8 I, Q (HackRF).  cs16: little-endian int16 I, Q (Airspy, SDRplay, SoapySDR).  cf32: little-endian IEEE float I, Q, full
+ * scale +-1.0 (GNU Radio, SigMF). */
+enum { WMBUS_FMT_CU8 = 0, WMBUS_FMT_CS8 = 1, WMBUS_FMT_CS16 = 2, WMBUS_FMT_CF32 = 3 };
 
 enum { WMBUS_PREFILTER_BOXCAR = 0, WMBUS_PREFILTER_POLYPHASE = 1 };
 enum { WMBUS_ATAN_LIBM = 0, WMBUS_ATAN_APPROX1 = 1, WMBUS_ATAN_APPROX2 = 2 };
@@ -154,6 +167,10 @@ typedef struct wmbus_timing {
     unsigned rssi_mode;         /* WMBUS_RSSI_*: how this push got its RSSI */
     unsigned rssi_tiles;        /* RSSI on demand: (tile, capture) pairs listed in this push */
     unsigned clock_round[4], rla_round[4];   /* segments re-run in the unattended rounds, round by round (beyond the rounds enqueued: 0) */
+    /* a context that resamples or converts (cfg.input_rate_hz, input_format, input_gain_q8): the cu8 bytes this push's input became,
+     * all streams (whether the pipeline took them in this push or they wait for the next block to fill), and how many of them the
+     * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path. */
+    uint64_t input_bytes_out, input_clipped;
 } wmbus_timing;
 
 /* wmbus_timing.rssi_mode.  EVERY_SAMPLE: in the demodulation kernel (contexts with debug views, option kernels, cfg.rssi_full).
@@ -237,7 +254,21 @@ int  wmbus_selftest_fir(int device, const float *x, float *out, size_t n);
  * any GPU work.  Returns the lines of one repetition; *seconds receives the wall clock of all of them. */
 long wmbus_debug_replay_decode(wmbus_ctx *ctx, unsigned reps, double *seconds);
 
-/* The resampler behind cfg.input_rate_hz; host only, no device needed.  out_hz / in_hz = L / M in lowest terms (L <= 32, M <= 1024,
+/* SAMPLE FORMATS, GAIN AND RESAMPLER: the arithmetic (tests/format_ref.py and tests/resample_ref.py restate it in numpy).
+ * Every format yields an int16 sample x per I and per Q, and a shift F:
+ *     cu8   x = 2 u - 255                                                            F = 15
+ *     cs8   x = 2 s + 1                       (the cu8 rule on s ^ 0x80)             F = 15
+ *     cs16  x = s                                                                    F = 22
+ *     cf32  x = clamp(rint(f * 32768), -32768, 32767), round half even, NaN -> 0     F = 22
+ * With acc = the resampler's sum below (for an input already at decimation x 800 kHz: acc = 16384 * x[n]) and g = cfg.input_gain_q8
+ * (256 if 0), the byte the pipeline gets is
+ *     byte = clamp((acc * g + (128 << (F + 8))) >> (F + 8), 0, 255)                  (product in int64)
+ * For cu8 with g = 256 that is (acc + 255 * 16384 + 16384) >> 15.  A cu8 byte u written as cs8 u - 128, as cs16 128 * (2 u - 255) or as
+ * cf32 (2 u - 255) / 256 gives, at g = 256, the byte stream of the cu8 capture: byte = u at the native rate.  Integers only behind the
+ * one rounding of cf32, so the bytes do not depend on tile, block or push boundaries.  |acc| <= 32768 * sum|taps| < 2^31 is checked
+ * when a context with a 16-bit format is opened.
+ *
+ * The resampler behind cfg.input_rate_hz; host only, no device needed.  out_hz / in_hz = L / M in lowest terms (L <= 32, M <= 1024,
  * in_hz >= 800000, out_hz a multiple of 800000; else WMBUS_EINVAL).  taps (may be NULL: geometry only; cap = its int16 capacity,
  * >= L * T) receives L phases of T = 16 * max(1, ceil(M / L)) taps, taps[p * T + k]: a Kaiser-windowed sinc (beta 8, cut-off
  * 0.45 * min(in_hz, out_hz)) in Q14, every phase summing to exactly 16384.  With x = 2 * byte - 255 (0 before the stream starts),
@@ -246,10 +277,11 @@ long wmbus_debug_replay_decode(wmbus_ctx *ctx, unsigned reps, double *seconds);
  *     byte = clamp((acc + 255 * 16384 + 16384) >> 15, 0, 255)
  * and exists once input floor(n * M / L) has been pushed: integers only, so the bytes do not depend on how the input is cut into pushes. */
 int  wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsigned *M, unsigned *T, int16_t *taps, size_t cap);
-/* Debug read (requires cfg.keep_taps and cfg.input_rate_hz): the resampled cu8 bytes the last push handed to the pipeline
- * for one stream.  Returns the number of bytes written (0 for a push that completed no block), or a negative error. */
+/* Debug read (requires cfg.keep_taps and a context that resamples or converts: cfg.input_rate_hz, input_format, input_gain_q8): the
+ * cu8 bytes the last push handed to the pipeline for one stream.  Returns the number of bytes written (0 for a push that completed no
+ * block), or a negative error. */
 long wmbus_read_resampled(wmbus_ctx *ctx, unsigned stream, uint8_t *out, size_t cap);
-/* Pushes of this context that launched the resampler kernel (0 for ever without cfg.input_rate_hz). */
+/* Pushes of this context that launched the resampler or the conversion kernel (0 for ever on the plain cu8 path). */
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx);
 
 /* Number of visible HIP devices (0 if none). */
@@ -269,8 +301,9 @@ typedef struct wmbus_batch_io {
     /* SOURCE.  fill != NULL (needs cfg.input_windows = 2): called on a worker thread whenever streams
      * [first_stream, first_stream + n_streams) need their next push.  Write the bytes of stream s at
      * slab + (s - first_stream) * pitch (page-locked memory, `cap` bytes per stream) and return the byte count EVERY
-     * stream of the group advances by (a multiple of 4096, <= cap; pad ended streams with 128 = no signal), or 0 when
-     * the group's input has ended.  Calls for different groups may run concurrently.
+     * stream of the group advances by (a multiple of 4096, <= cap; pad ended streams with no signal), or 0 when
+     * the group's input has ended.  The bytes are RAW bytes of cfg.input_format; no signal is the byte 128 for cu8, 0 for cs8 and
+     * cs16, 0.0f (all bytes 0) for cf32.  Calls for different groups may run concurrently.
      * fill == NULL: the input is resident in the device windows (wmbus_batch_stage / wmbus_batch_device_input):
      * every context makes `passes` pushes of `resident_bytes`. */
     size_t (*fill)(void *user, unsigned first_stream, unsigned n_streams, uint8_t *slab, size_t pitch, size_t cap);
@@ -287,7 +320,7 @@ typedef struct wmbus_batch_io {
 } wmbus_batch_io;
 
 typedef struct wmbus_batch_stats {
-    uint64_t samples;           /* input IQ samples consumed, all streams        */
+    uint64_t samples;           /* input IQ samples consumed, all streams (raw bytes / bytes per sample of cfg.input_format) */
     uint64_t lines;             /* datagram lines produced                       */
     double   seconds;           /* wall clock of wmbus_batch_run                 */
     unsigned pushes;            /* context pushes                                */

@@ -47,7 +47,7 @@ class Cfg(ctypes.Structure):
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
-                ("input_rate_hz", ctypes.c_uint)]
+                ("input_rate_hz", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
 
 
 class Line(ctypes.Structure):
@@ -63,18 +63,21 @@ class Timing(ctypes.Structure):
                 ("ema_retries", ctypes.c_uint), ("chips", (ctypes.c_uint64 * 2) * 2), ("bursts", ctypes.c_uint64),
                 ("turn_wait_ms", ctypes.c_float), ("warnings", ctypes.c_uint), ("slow_path", ctypes.c_uint),
                 ("rssi_ms", ctypes.c_float), ("rssi_mode", ctypes.c_uint), ("rssi_tiles", ctypes.c_uint),
-                ("clock_round", ctypes.c_uint * 4), ("rla_round", ctypes.c_uint * 4)]
+                ("clock_round", ctypes.c_uint * 4), ("rla_round", ctypes.c_uint * 4),
+                ("input_bytes_out", ctypes.c_uint64), ("input_clipped", ctypes.c_uint64)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k in ("demod_ms", "clock_ms", "rla_ms", "gather_ms", "d2h_ms", "gpu_total_ms",
                                            "host_decode_ms", "clock_reruns", "rla_reruns", "ema_retries", "bursts", "turn_wait_ms", "warnings", "slow_path",
-                                           "rssi_ms", "rssi_mode", "rssi_tiles")}
+                                           "rssi_ms", "rssi_mode", "rssi_tiles", "input_bytes_out", "input_clipped")}
         d["chips"] = [[int(self.chips[ch][al]) for al in range(2)] for ch in range(2)]      # [chain][algo]
         d["clock_round"] = [int(v) for v in self.clock_round]; d["rla_round"] = [int(v) for v in self.rla_round]
         return d
 
 
 RSSI_EVERY_SAMPLE, RSSI_ON_DEMAND, RSSI_PAUSED, RSSI_FELL_BACK = 0, 1, 2, 3            # wmbus_timing.rssi_mode
+FMT_CU8, FMT_CS8, FMT_CS16, FMT_CF32 = 0, 1, 2, 3                                      # wmbus_cfg.input_format
+FMT_BYTES_PER_SAMPLE = {FMT_CU8: 2, FMT_CS8: 2, FMT_CS16: 4, FMT_CF32: 8}
 
 
 FILL_FN = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t)
@@ -205,7 +208,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
-              input_rate_hz=0):
+              input_rate_hz=0, input_format=0, input_gain_q8=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -224,6 +227,8 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.k1_tiles_per_block = int(k1_tiles_per_block)
     c.clock_waves = int(clock_waves)
     c.input_rate_hz = int(input_rate_hz)     # 0: the input is at decimation x 800 kHz; else the library resamples it on the GPU
+    # raw sample format (FMT_*) and linear gain in Q8 (0: x 1); stage / process / max_push_bytes then count RAW bytes
+    c.input_format, c.input_gain_q8 = int(input_format), int(input_gain_q8)
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
     return c
@@ -400,7 +405,8 @@ class Receiver:
         return t.as_dict()
 
     def push(self, streams):
-        """Stage one equally long cu8 array per stream, process, decode; returns the text."""
+        """Stage one equally long array of raw bytes (uint8; cu8 unless input_format says otherwise) per stream, process, decode;
+        returns the text."""
         n = None
         for s, a in enumerate(streams):
             a = np.ascontiguousarray(a, dtype=np.uint8)
@@ -434,7 +440,7 @@ class Receiver:
         return out[:r]
 
     def read_resampled(self, stream, cap=None):
-        """The resampled cu8 bytes the last push handed to the pipeline (input_rate_hz and keep_taps)."""
+        """The cu8 bytes the last push handed to the pipeline (keep_taps and a context that resamples or converts)."""
         cap = cap or (int(self.cfg.max_push_bytes) * 2 + 8192 if self.cfg is not None else 1 << 24)
         out = np.zeros(cap, np.uint8)
         r = lib().wmbus_read_resampled(self._h, stream, out.ctypes.data, cap)

@@ -127,11 +127,14 @@ struct wmbus_ctx {
     uint64_t in_stride = 0, n0 = 0;
     size_t staged = 0;
     size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
-    /* cfg.input_rate_hz: the resampler in front of the demodulation kernel (wm_k0_resample.h).  wmbus_stage fills the RAW windows; K0
+    /* cfg.input_rate_hz / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) -- the resampler
+     * (`resample`), which also reads every format and applies the gain, or for an input at the native rate the conversion kernel
+     * alone (L = M = 1, no taps, no history).  wmbus_stage fills the RAW windows; K0
      * writes the window of d_in the pipeline reads.  hist / rem are double-buffered like every carried state (a push reads half
      * `cur`, writes the other).  Every capture advances in lock step, so the counters live here and travel as launch arguments. */
     struct {
-        bool on = false;
+        bool on = false, resample = false;
+        uint32_t fmt = WMBUS_FMT_CU8, bps = 2, gain = 0;   /* cfg.input_format, its raw bytes per sample, cfg.input_gain_q8 */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
         size_t raw_cap = 0; uint64_t raw_stride = 0;
         uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
@@ -140,6 +143,7 @@ struct wmbus_ctx {
         uint8_t *d_rem = nullptr;                      /* [2][S][4096] */
         uint64_t n_in = 0, n_out = 0;                  /* raw samples pushed / outputs produced so far */
         size_t last_bytes = 0; uint32_t last_win = 0;  /* what the last push handed to the pipeline, and in which window */
+        uint64_t last_out = 0;                         /* bytes the last push produced, all captures (wmbus_timing.input_bytes_out) */
         unsigned long long launches = 0;
     } k0;
     /* device buffers */
@@ -248,6 +252,7 @@ enum { WM_RS_BLOCKS = 2048 };
 enum { WM_K1_TPB_DEFAULT = 2 };                /* tiles per block of the demodulation kernel's first pass (RSSI on demand), see enqueue_front_impl */
 enum { SC_ERR = 0, SC_NHITS = 1, SC_NHDR = 2, SC_NWORDS = 3, SC_NPKTS = 4, SC_NBYTES = 5, SC_SLOW = 6, SC_CHIPS = 8 /* [algo][chain] */,
        SC_RS_N = 12 /* tiles listed for the RSSI-on-demand launch */, SC_RS_FAIL = 13 /* a lane that is read could not prove its value */,
+       SC_CLIP = 14 /* K0: output bytes the clamp changed (wmbus_timing.input_clipped) */,
        SC_EMA = 16 /* [ema_rounds + 1] */, SC_CLK = 24 /* [fr_rounds + 1] */, SC_RLA = 32 /* [rla_rounds + 1] */, SC_COUNT = 40 };
 static_assert(WM_MAX_ROUNDS + 2 <= 8 && SC_RLA + WM_MAX_ROUNDS + 2 <= SC_COUNT, "every kind of round keeps its counters inside its eight SC_* slots");
 
@@ -466,22 +471,38 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
         return bail(fail(c, WMBUS_EINVAL, "atan_mode must be WMBUS_ATAN_LIBM, WMBUS_ATAN_APPROX1 or WMBUS_ATAN_APPROX2"));
     if (cfg->prefilter == WMBUS_PREFILTER_POLYPHASE && (cfg->decimation != 2 || cfg->simultaneous))
         return bail(fail(c, WMBUS_EINVAL, "the polyphase pre-filter is the 1.6 MS/s design of rtl_wmbus.c:258-294: decimation 2, no -s"));
+    if (cfg->input_format > WMBUS_FMT_CF32) return bail(fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format));
+    if (cfg->input_gain_q8 > 65535u) return bail(fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8));
     c->push_cap = cfg->max_push_bytes;
+    c->k0.fmt = cfg->input_format; c->k0.bps = k0_bps((int)cfg->input_format); c->k0.gain = cfg->input_gain_q8;
+    const bool converts = cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u);
     std::vector<int16_t> k0_taps;
     if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
         unsigned L = 0, M = 0, T = 0;
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
         const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
         if (why) return bail(fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u));
-        c->k0.on = true; c->k0.L = L; c->k0.M = M; c->k0.T = T;
+        if (c->k0.fmt == WMBUS_FMT_CS16 || c->k0.fmt == WMBUS_FMT_CF32)
+            for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples: |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
+                int64_t abs_total = 0;
+                for (unsigned k = 0; k < T; k++) abs_total += std::abs((int)k0_taps[(size_t)p * T + k]);
+                if (32768ll * abs_total >= (1ll << 31)) return bail(fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's accumulator bound for 16-bit input is exceeded (phase %u)", p));
+            }
+        c->k0.on = true; c->k0.resample = true; c->k0.L = L; c->k0.M = M; c->k0.T = T;
         c->k0.raw_cap = cfg->max_push_bytes;
         c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
         /* the pipeline behind K0 is sized for what a full raw push resamples to, plus the remainder in front of it */
-        const uint64_t most = ((uint64_t)(cfg->max_push_bytes / 2u) * L + M - 1u) / M * 2u;
+        const uint64_t most = ((uint64_t)(cfg->max_push_bytes / c->k0.bps) * L + M - 1u) / M * 2u;
         c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
         const uint32_t tile = k0_pick_tile(L, M, T);
         if (!tile) return bail(fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T));
         c->k0.tile = tile; c->k0.lds = k0_lds_bytes(L, M, T, tile);
+    } else if (converts) {                                   /* the native rate in another format or with a gain: the conversion kernel alone */
+        c->k0.on = true; c->k0.L = c->k0.M = c->k0.T = 1u;
+        c->k0.raw_cap = cfg->max_push_bytes;
+        c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
+        c->push_cap = (size_t)((cfg->max_push_bytes / c->k0.bps * 2u + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
+        c->k0.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / c->k0.bps); c->k0.lds = 0u;
     }
     if (cfg->device < 0 || cfg->device >= WM_MAX_DEVICES) return bail(fail(c, WMBUS_EINVAL, "device must be 0..%d", WM_MAX_DEVICES - 1));
     if (wmbus_device_count() <= cfg->device) return bail(fail(c, WMBUS_ENODEVICE, "no HIP device %d (this library has no CPU fallback)", cfg->device));
@@ -573,8 +594,10 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     A(dalloc(&c->d_hist, (size_t)WM_HIST_BYTES * c->S));
     if (c->k0.on) {
         A(dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->S * c->n_win));
-        A(dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
-        A(dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
+        if (c->k0.resample) {
+            A(dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
+            A(dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
+        }
         A(dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
     }
     A(dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
@@ -660,9 +683,9 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     }
     if (e != hipSuccess) return bail(fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e)));
 
-    if (c->k0.on) {                                          /* history before a stream's first sample: x = 0 */
+    if (c->k0.on) A(hipMemsetAsync(c->k0.d_rem, 128, (size_t)2 * c->S * WMBUS_BLOCK_BYTES, c->stream));
+    if (c->k0.resample) {                                    /* history before a stream's first sample: x = 0 */
         A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
-        A(hipMemsetAsync(c->k0.d_rem, 128, (size_t)2 * c->S * WMBUS_BLOCK_BYTES, c->stream));
         A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
         A(hipStreamSynchronize(c->stream));                  /* k0_taps leaves with this function */
     }
@@ -928,12 +951,12 @@ static int launch_k3(wmbus_ctx *c, bool again)
     return 0;
 }
 
-/* cfg.input_rate_hz: the launch arguments of K0 for a push of `raw_bytes`, and the host's copy of the counters moved on.  Returns the
+/* A context with a K0 stage: the launch arguments of K0 for a push of `raw_bytes`, and the host's copy of the counters moved on.  Returns the
  * bytes the pipeline gets from this push: the whole 4096-byte blocks of (remainder + what this push produces); may be 0. */
 static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 {
     auto &k = c->k0;
-    const uint32_t n_in = (uint32_t)(raw_bytes / 2u);
+    const uint32_t n_in = (uint32_t)(raw_bytes / k.bps);
     const uint64_t out_end = ((k.n_in + n_in) * (uint64_t)k.L + k.M - 1u) / k.M;      /* output n exists once input floor(n M / L) is in: n M < pushed L */
     const uint32_t n_out = (uint32_t)(out_end - k.n_out);
     const size_t total = (size_t)k.rem + 2u * (size_t)n_out, whole = total / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES;
@@ -941,11 +964,13 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     ka->raw = k.d_raw + (size_t)c->fill * c->S * k.raw_stride; ka->raw_stride = k.raw_stride;
     ka->out = c->d_in + (size_t)c->fill * c->S * c->in_stride + WM_HIST_BYTES; ka->out_stride = c->in_stride;
     ka->taps = k.d_taps;
-    ka->hist_in = k.d_hist + (size_t)k.cur * c->S * (k.T - 1u); ka->hist_out = k.d_hist + (size_t)(k.cur ^ 1u) * c->S * (k.T - 1u);
+    if (k.resample) { ka->hist_in = k.d_hist + (size_t)k.cur * c->S * (k.T - 1u); ka->hist_out = k.d_hist + (size_t)(k.cur ^ 1u) * c->S * (k.T - 1u); }
     ka->rem_in = k.d_rem + (size_t)k.cur * c->S * WMBUS_BLOCK_BYTES; ka->rem_out = k.d_rem + (size_t)(k.cur ^ 1u) * c->S * WMBUS_BLOCK_BYTES;
     ka->n_first = k.n_out; ka->in_first = k.n_in; ka->n_in = n_in; ka->n_out = n_out;
     ka->rem_prev = k.rem; ka->keep_from = (uint32_t)whole;
     ka->L = k.L; ka->M = k.M; ka->T = k.T; ka->tile = k.tile;
+    ka->gain_q8 = k.gain; ka->clipped = c->d_scalars + SC_CLIP;
+    k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
     k.last_bytes = whole; k.last_win = c->fill;
     return whole;
@@ -953,7 +978,21 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
-    hipLaunchKernelGGL(k0_resample, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS), c->k0.lds, c->stream, ka);
+    const dim3 grid((ka.n_out + ka.tile - 1u) / ka.tile, c->S), block(WM_K0_THREADS);
+    if (c->k0.resample)
+        switch (c->k0.fmt) {
+        case WMBUS_FMT_CU8: hipLaunchKernelGGL(k0_resample, grid, block, c->k0.lds, c->stream, ka); break;
+        case WMBUS_FMT_CS8: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CS8>, grid, block, c->k0.lds, c->stream, ka); break;
+        case WMBUS_FMT_CS16: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CS16>, grid, block, c->k0.lds, c->stream, ka); break;
+        default: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CF32>, grid, block, c->k0.lds, c->stream, ka); break;
+        }
+    else
+        switch (c->k0.fmt) {
+        case WMBUS_FMT_CU8: hipLaunchKernelGGL(k0_convert<WM_K0_CU8>, grid, block, 0, c->stream, ka); break;
+        case WMBUS_FMT_CS8: hipLaunchKernelGGL(k0_convert<WM_K0_CS8>, grid, block, 0, c->stream, ka); break;
+        case WMBUS_FMT_CS16: hipLaunchKernelGGL(k0_convert<WM_K0_CS16>, grid, block, 0, c->stream, ka); break;
+        default: hipLaunchKernelGGL(k0_convert<WM_K0_CF32>, grid, block, 0, c->stream, ka); break;
+        }
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
     return WMBUS_OK;
@@ -996,7 +1035,12 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
     }
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     hipLaunchKernelGGL(k_copy_hist, dim3(c->S), dim3(256), 0, c->stream, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint64_t)0, win, c->in_stride);
-    if (c->k0.on && g.M == 0) { const int rc0 = k0_launch(c, k0a); if (rc0) return rc0; }      /* a push that completes no block: the resampler alone */
+    if (c->k0.on && g.M == 0) {                          /* a push that completes no block: K0 alone, and its clip count */
+        HIPCHK(c, hipMemsetAsync(c->d_scalars + SC_CLIP, 0, sizeof(uint32_t), c->stream));
+        const int rc0 = k0_launch(c, k0a);
+        if (rc0) return rc0;
+        HIPCHK(c, hipMemcpyAsync(c->h_scalars + SC_CLIP, c->d_scalars + SC_CLIP, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
     if (g.M > 0) {
         HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, c->zero_words * sizeof(uint32_t), c->stream));     /* scalars, region flags, spill chains */
         /* K1 */
@@ -1368,6 +1412,7 @@ static int wait_gpu(wmbus_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->in_flight = false;
     c->tim = wmbus_timing{};
+    if (c->k0.on) { c->tim.input_bytes_out = c->k0.last_out; c->tim.input_clipped = c->h_scalars[SC_CLIP]; }
     if (c->last.M > 0) {
         float ms = 0;
         hipEventElapsedTime(&ms, c->ev[3], c->ev[4]); c->tim.demod_ms = ms;
@@ -1595,7 +1640,7 @@ long wmbus_read_tap(wmbus_ctx *c, const char *what, int chain, unsigned stream, 
 long wmbus_read_resampled(wmbus_ctx *c, unsigned stream, uint8_t *out, size_t cap)
 {
     if (!c || !out || stream >= c->S) return WMBUS_EINVAL;
-    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and cfg.input_rate_hz");
+    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples or converts (cfg.input_rate_hz, input_format, input_gain_q8)");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_resampled: collect the push first");
     const size_t n = std::min(cap, c->k0.last_bytes);
     HIPCHK(c, hipSetDevice(c->cfg.device));

@@ -110,7 +110,7 @@ void batch_worker(wmbus_batch *b, unsigned i, const wmbus_batch_io *io, BatchTot
         if (n_cur) {
             rc = wait_gpu(c);
             if (rc) { batch_fail(b, rc, "batch: context %u: %s", i, c->err); break; }
-            tot->samples += (uint64_t)S * (n_cur / 2);
+            tot->samples += (uint64_t)S * (n_cur / k0_bps((int)b->cfg.input_format));
             tot->pushes++;
             have_prev = true;
         } else have_prev = false;

@@ -22,10 +22,21 @@
  * samples (as {I, Q} int16 pairs) and the bytes behind the last whole 4096-byte block (the pipeline takes whole blocks, as the
  * reference's fread does).  The output counter is the same for every capture of a context (they advance in lock step) and
  * travels as a launch argument, like WmPush.n0.
+ *
+ * Sample formats and input gain (cfg.input_format, cfg.input_gain_q8; the contract is in include/wmbus_hip.h): the format is a
+ * template parameter of the block function.  Only the staging loop that fills the LDS span (and the history hand-over) knows the
+ * raw layout -- every format becomes the same {I, Q} int16 pair there -- and only the output stage knows the shift F and the gain:
+ *   cu8  x = 2u - 255   cs8  x = 2s + 1 (one XOR in front of the cu8 rule)   F = 15
+ *   cs16 x = s (the raw dword IS the LDS dword)   cf32 x = clamp(rint(f 32768)), NaN -> 0   F = 22
+ *   byte = clamp((acc g + (128 << (F + 8))) >> (F + 8), 0, 255), the product in int64; g = 256 at F = 15 is the line above.
+ * k0_convert_block is the same stage for an input that is already at decimation x 800 kHz (acc = 16384 x): no taps, no LDS span,
+ * 16 raw bytes per lane and load, the same remainder / keep_from hand-over.  Both count the bytes the clamp changed (K0Args.clipped):
+ * per lane in a register, per block in LDS, one atomic add per block.
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
 
+#include <math.h>
 #include <stdint.h>
 
 #define WM_K0_THREADS   256u
@@ -34,6 +45,11 @@
 #define WM_K0_MAX_M     1024u
 #define WM_K0_MAX_T     512u
 #define WM_K0_OUT_BIAS  (255 * 16384 + 16384)
+#define WM_K0_CU8   0              /* = WMBUS_FMT_* of include/wmbus_hip.h */
+#define WM_K0_CS8   1
+#define WM_K0_CS16  2
+#define WM_K0_CF32  3
+#define WM_K0_CONV_UNROLL 4u       /* k0_convert_block: 16-byte loads a lane has in flight */
 
 struct K0Args {
     const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
@@ -51,7 +67,17 @@ struct K0Args {
     uint32_t rem_prev;           /* bytes in rem_in                                                           */
     uint32_t keep_from;          /* window bytes from here on wait for the next push: they go to rem_out too  */
     uint32_t L, M, T, tile;      /* tile: outputs per block (even)                                            */
+    /* sample formats and gain; all zero: cu8, gain x 1, nothing counted */
+    uint32_t gain_q8;            /* cfg.input_gain_q8 (0: 256)                                                */
+    uint32_t *clipped;           /* += output bytes the clamp changed in this push, all captures (NULL: not counted) */
 };
+
+/* raw bytes per sample; F + 8, the shift behind the gain product */
+__host__ __device__ constexpr uint32_t k0_bps(int fmt) { return fmt == WM_K0_CF32 ? 8u : fmt == WM_K0_CS16 ? 4u : 2u; }
+__host__ __device__ constexpr uint32_t k0_shift(int fmt) { return fmt == WM_K0_CS16 || fmt == WM_K0_CF32 ? 30u : 23u; }
+
+struct alignas(8) K0U2 { uint32_t x, y; };
+struct alignas(16) K0U4 { uint32_t x, y, z, w; };
 
 /* samples of LDS a block needs for its input span: every lane computes WM_K0_OPL outputs, so a partial last group reads
  * (and discards) up to WM_K0_OPL * L outputs past the tile */
@@ -83,6 +109,39 @@ __device__ __forceinline__ uint32_t k0_pack(uint32_t byte_pair)        /* cu8 {I
 {
     const int32_t i = 2 * (int32_t)(byte_pair & 0xFFu) - 255, q = 2 * (int32_t)((byte_pair >> 8) & 0xFFu) - 255;
     return ((uint32_t)i & 0xFFFFu) | ((uint32_t)q << 16);
+}
+
+/* cf32 -> int16: clamp(rint(f * 32768), -32768, 32767), round half even, NaN -> 0 (the product is exact: a power of two) */
+__device__ __forceinline__ int32_t k0_f2x(uint32_t bits)
+{
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    float v = f * 32768.0f;
+    v = v == v ? v : 0.0f;
+    return (int32_t)rintf(fminf(fmaxf(v, -32768.0f), 32767.0f));
+}
+__device__ __forceinline__ uint32_t k0_pair(int32_t i, int32_t q) { return ((uint32_t)i & 0xFFFFu) | ((uint32_t)q << 16); }
+
+/* two consecutive raw samples at p (the first one's index within the push is even: p is aligned to both) -> two LDS dwords */
+template <int FMT> __device__ __forceinline__ void k0_load2(const uint8_t *p, uint32_t &v0, uint32_t &v1)
+{
+    if constexpr (FMT == WM_K0_CS16) {                           /* already the LDS layout */
+        const K0U2 w = *(const K0U2 *)p;
+        v0 = w.x; v1 = w.y;
+    } else if constexpr (FMT == WM_K0_CF32) {
+        const K0U4 w = *(const K0U4 *)p;
+        v0 = k0_pair(k0_f2x(w.x), k0_f2x(w.y)); v1 = k0_pair(k0_f2x(w.z), k0_f2x(w.w));
+    } else {
+        uint32_t w = *(const uint32_t *)p;
+        if constexpr (FMT == WM_K0_CS8) w ^= 0x80808080u;        /* s + 128: the cu8 byte of the same level */
+        v0 = k0_pack(w); v1 = k0_pack(w >> 16);
+    }
+}
+template <int FMT> __device__ __forceinline__ uint32_t k0_load1(const uint8_t *p)
+{
+    if constexpr (FMT == WM_K0_CS16) return *(const uint32_t *)p;
+    else if constexpr (FMT == WM_K0_CF32) { const K0U2 w = *(const K0U2 *)p; return k0_pair(k0_f2x(w.x), k0_f2x(w.y)); }
+    else return k0_pack((uint32_t)*(const uint16_t *)p ^ (FMT == WM_K0_CS8 ? 0x8080u : 0u));
 }
 
 /* a.lo * b.lo + a.hi * b.hi + c on int16 halves, exact in int32 */
@@ -118,11 +177,52 @@ __device__ __forceinline__ uint32_t k0_byte(int32_t acc)
     return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
 
+/* the output stage of every format: g = 256 at F = 15 stays on the 32-bit line above (the branch is uniform); nclip counts the
+ * values the clamp changed */
+template <int FMT> __device__ __forceinline__ uint32_t k0_byte_g(int32_t acc, uint32_t g, uint32_t &nclip)
+{
+    int32_t v;
+    if (k0_shift(FMT) == 23u && g == 256u) v = (acc + WM_K0_OUT_BIAS) >> 15;
+    else v = (int32_t)(((int64_t)acc * (int64_t)g + ((int64_t)128 << k0_shift(FMT))) >> k0_shift(FMT));
+    nclip += (v < 0 || v > 255) ? 1u : 0u;
+    return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+__device__ __forceinline__ void k0_add(uint32_t *p, uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd(p, v);
+#else
+    *p += v;                                                     /* the block emulator runs one lane at a time */
+#endif
+}
+/* a block's clip count -> a.clipped: word is a dword of LDS nobody reads any more; every lane of the block arrives */
+__device__ __forceinline__ void k0_count_clips(const K0Args &a, uint32_t *word, uint32_t nclip)
+{
+    if (!a.clipped) return;
+    if (threadIdx.x == 0) *word = 0u;
+    __syncthreads();
+    if (nclip) k0_add(word, nclip);
+    __syncthreads();
+    if (threadIdx.x == 0 && *word) k0_add(a.clipped, *word);
+}
+/* block 0 of a capture: the bytes earlier pushes left go in front of this push's in the window */
+__device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_t *out)
+{
+    const uint16_t *rin = (const uint16_t *)(a.rem_in + (uint64_t)s * 4096u);
+    uint16_t *rout = (uint16_t *)(a.rem_out + (uint64_t)s * 4096u);
+    for (uint32_t j = threadIdx.x; j < a.rem_prev / 2u; j += blockDim.x) {
+        const uint16_t v = rin[j];
+        *(uint16_t *)(out + 2u * j) = v;
+        if (2u * j >= a.keep_from) rout[(2u * j - a.keep_from) / 2u] = v;
+    }
+}
+
 /* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
-__device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds)
+template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
-    const uint32_t L = a.L, M = a.M, T = a.T;
+    const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
+    constexpr uint32_t BPS = k0_bps(FMT);
     const uint32_t span = k0_span(L, M, T, a.tile);
     uint32_t *xs = lds;                                          /* [span] {I, Q} */
     const uint32_t *tp = lds + span;                             /* [L][k0_row(T)] tap pairs */
@@ -142,13 +242,12 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
     const uint32_t sh = (uint32_t)(rel & 1);
     const int64_t base = rel - (int64_t)sh;
 
-    for (uint32_t j = 2u * tid; j < span; j += 2u * nthr) {      /* two samples per lane and trip: one aligned dword of the push */
+    for (uint32_t j = 2u * tid; j < span; j += 2u * nthr) {      /* two samples per lane and trip: one aligned load of 4, 8 or 16 bytes of the push */
         const int64_t r = base + (int64_t)j;
         uint32_t v0 = 0u, v1 = 0u;
         if (r >= 0) {
             if (r < (int64_t)a.n_in) {                           /* n_in is even: r + 1 lies inside too */
-                const uint32_t w = *(const uint32_t *)(raw + 2u * (uint64_t)r);
-                v0 = k0_pack(w); v1 = k0_pack(w >> 16);
+                k0_load2<FMT>(raw + BPS * (uint64_t)r, v0, v1);
             }
         } else {                                                 /* r <= -2: both samples are history (the oldest slot, index -T, is never read) */
             const int64_t h = r + (int64_t)(T - 1u);
@@ -167,20 +266,14 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
         uint32_t *hist_out = a.hist_out + (uint64_t)s * (T - 1u);
         for (uint32_t j = tid; j < T - 1u; j += nthr) {
             const uint32_t r = a.n_in - (T - 1u) + j;
-            hist_out[j] = k0_pack(*(const uint16_t *)(raw + 2u * (uint64_t)r));
+            hist_out[j] = k0_load1<FMT>(raw + BPS * (uint64_t)r);
         }
-        /* the bytes earlier pushes left: in front of this push's in the window */
-        const uint16_t *rin = (const uint16_t *)(a.rem_in + (uint64_t)s * 4096u);
-        uint16_t *rout = (uint16_t *)(a.rem_out + (uint64_t)s * 4096u);
-        for (uint32_t j = tid; j < a.rem_prev / 2u; j += nthr) {
-            const uint16_t v = rin[j];
-            *(uint16_t *)(out + 2u * j) = v;
-            if (2u * j >= a.keep_from) rout[(2u * j - a.keep_from) / 2u] = v;
-        }
+        k0_carry_rem(a, s, out);
     }
     __syncthreads();
 
     const uint32_t groups = (ntile + WM_K0_OPL * L - 1u) / (WM_K0_OPL * L);
+    uint32_t nclip = 0u;
     for (uint32_t w = tid; w < groups * L; w += nthr) {
         const uint32_t t0 = (w / L) * WM_K0_OPL * L + w % L;     /* this lane's outputs: t0 + i L */
         const uint32_t v = r0 + t0 * M;
@@ -202,7 +295,7 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
 #pragma unroll
         for (uint32_t i = 0; i < WM_K0_OPL; i++) {
             const uint32_t t = t0 + i * L;
-            if (t < ntile) ob[t] = (uint16_t)(k0_byte(ai[i]) | (k0_byte(aq[i]) << 8));
+            if (t < ntile) ob[t] = (uint16_t)(k0_byte_g<FMT>(ai[i], gain, nclip) | (k0_byte_g<FMT>(aq[i], gain, nclip) << 8));
         }
     }
     __syncthreads();
@@ -215,13 +308,91 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
         *(uint16_t *)(out + o) = v;
         if (o >= a.keep_from) rout[(o - a.keep_from) / 2u] = v;
     }
+    k0_count_clips(a, xs, nclip);                                /* the span has been read for the last time before the barrier above */
+}
+__device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds) { k0_resample_block_t<WM_K0_CU8>(a, lds); }
+
+/* Conversion only: the input is at decimation x 800 kHz already, output t is input t and acc = 16384 x.  Block = (a.tile consecutive
+ * samples, capture); a lane takes 16 raw bytes per load -- 8 / 8 / 4 / 2 samples of cu8 / cs8 / cs16 / cf32 -- and has WM_K0_CONV_UNROLL
+ * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
+ * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
+ * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
+template <int FMT> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+{
+    constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
+    const uint8_t *raw = a.raw + (uint64_t)s * a.raw_stride;
+    uint8_t *out = a.out + (uint64_t)s * a.out_stride;
+    uint8_t *rout = a.rem_out + (uint64_t)s * 4096u;
+    const uint32_t t_first = blockIdx.x * a.tile;
+    if (t_first >= a.n_out) return;
+    const uint32_t ntile = a.n_out - t_first < a.tile ? a.n_out - t_first : a.tile;
+    if (blockIdx.x == 0) k0_carry_rem(a, s, out);
+    uint32_t nclip = 0u;
+    for (uint32_t i0 = SPL * tid; i0 < ntile; i0 += WM_K0_CONV_UNROLL * SPL * nthr) {
+        K0U4 w[WM_K0_CONV_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < WM_K0_CONV_UNROLL; u++) {
+            const uint32_t i = i0 + u * SPL * nthr;
+            if (i < ntile) w[u] = *(const K0U4 *)(raw + BPS * (uint64_t)(t_first + i));
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < WM_K0_CONV_UNROLL; u++) {
+            const uint32_t i = i0 + u * SPL * nthr;
+            if (i >= ntile) continue;
+            const uint32_t o = a.rem_prev + 2u * (t_first + i);
+            uint8_t *dst = o >= a.keep_from ? rout + (o - a.keep_from) : nullptr;
+            const uint32_t in[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+            if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) {
+                uint32_t r[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) {
+                    const uint32_t v = FMT == WM_K0_CS8 ? in[k] ^ 0x80808080u : in[k];
+                    r[k] = 0u;
+#pragma unroll
+                    for (uint32_t b = 0; b < 4u; b++)
+                        r[k] |= k0_byte_g<FMT>(16384 * (2 * (int32_t)((v >> (8u * b)) & 0xFFu) - 255), gain, nclip) << (8u * b);
+                }
+                const K0U4 y = {r[0], r[1], r[2], r[3]};
+                *(K0U4 *)(out + o) = y;
+                if (dst) *(K0U4 *)dst = y;
+            } else if constexpr (FMT == WM_K0_CS16) {
+                uint32_t r[2] = {0u, 0u};
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) {
+                    r[k / 2u] |= k0_byte_g<FMT>(16384 * (int32_t)(int16_t)(in[k] & 0xFFFFu), gain, nclip) << (16u * (k & 1u));
+                    r[k / 2u] |= k0_byte_g<FMT>(16384 * (int32_t)(int16_t)(in[k] >> 16), gain, nclip) << (16u * (k & 1u) + 8u);
+                }
+                const K0U2 y = {r[0], r[1]};
+                *(K0U2 *)(out + o) = y;
+                if (dst) *(K0U2 *)dst = y;
+            } else {
+                uint32_t y = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) y |= k0_byte_g<FMT>(16384 * k0_f2x(in[k]), gain, nclip) << (8u * k);
+                *(uint32_t *)(out + o) = y;
+                if (dst) *(uint32_t *)dst = y;
+            }
+        }
+    }
+    k0_count_clips(a, word, nclip);
 }
 
 #if defined(__HIPCC__)
-__global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)
+__global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {
     extern __shared__ uint32_t k0_lds[];
     k0_resample_block(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_fmt(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT>(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT>(a, &word);
 }
 #endif
 

@@ -3,6 +3,9 @@
  *
  *   k0_resample  option (cfg.input_rate_hz): exact integer polyphase resampler, cu8 at any rate -> cu8 at decimation x 800 kHz
  *                in the input window; everything below runs unchanged behind it.    (no counterpart: rtl_wmbus.c:1274-1292)
+ *   k0_resample_fmt<cs8 | cs16 | cf32>  the same for cfg.input_format, with cfg.input_gain_q8 in the output stage;
+ *   k0_convert<fmt>  the format / gain conversion alone for an input that is at decimation x 800 kHz already; both count the
+ *                bytes their clamp changed (wmbus_timing.input_clipped).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.

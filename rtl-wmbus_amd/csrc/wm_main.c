@@ -9,7 +9,7 @@
  * reached through the C ABI in include/wmbus_hip.h.
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
- * -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
+ * -I sample format of the input and -g input gain in dB (converted on the GPU), -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
  * A batch is a wmbus_batch of the library per device: the files are split over several receiver contexts (whole groups
@@ -19,6 +19,7 @@
  * (file-per-GPU, no collective), each file's lines in its own order.  -M prints that map and exits.
  */
 #include <arpa/inet.h>
+#include <math.h>
 #include <netdb.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -54,6 +55,8 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-f exit if flow of incoming data stops\n");
     fprintf(stdout, "\t-R rate of the input in samples/s when it is not -d x 800 kHz (2048000, 2.048M, 2048k): resampled on the GPU to -d x 800 kHz\n");
     fprintf(stdout, "\t   (output rate / input rate = L / M in lowest terms with L <= 32, M <= 1024; at least 800k; with -P only to 1.6 MS/s)\n");
+    fprintf(stdout, "\t-I cu8|cs8|cs16|cf32 sample format of the input (default cu8; cs16 and cf32 little-endian, cf32 full scale +-1.0): converted on the GPU\n");
+    fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -102,6 +105,7 @@ struct batch_job {
     unsigned told;                                       /* warnings already reported for this device */
     int stats, fast_exit;
     wmbus_batch_stats st;
+    unsigned long long bytes_out, clipped;               /* wmbus_timing.input_bytes_out / input_clipped over the run */
 };
 
 static pthread_mutex_t out_lock = PTHREAD_MUTEX_INITIALIZER;      /* one push's lines leave as a unit, whichever device they come from */
@@ -203,7 +207,9 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
     }
     pthread_mutex_unlock(&pool.m);
     for (unsigned k = 0; k < n; k++) if (got[k] > most) most = got[k];
-    for (unsigned k = 0; k < n; k++) if (got[k] < most) memset(slab + (size_t)k * pitch + got[k], 128, most - got[k]);
+    /* no signal: mid-scale for cu8, zero for the signed formats and for cf32 (0.0f) */
+    const int silence = j->cfg.input_format == WMBUS_FMT_CU8 ? 128 : 0;
+    for (unsigned k = 0; k < n; k++) if (got[k] < most) memset(slab + (size_t)k * pitch + got[k], silence, most - got[k]);
     free(got);
     return most;
 }
@@ -214,6 +220,7 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     (void)first; (void)n;
     pthread_mutex_lock(&out_lock);
     report_warnings(t->warnings, &j->told);
+    j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
         fwrite(text + ln[i].text_off, 1, ln[i].text_len, stdout);
@@ -251,6 +258,9 @@ static int run_batch(struct batch_job *j)
         fprintf(stderr, "rtl_wmbus_hip: device %d: %d files, %u contexts, %llu samples, %llu lines, %u pushes in %.3f s = %.1f Msamples/s\n", j->cfg.device, j->n,
                 wmbus_batch_contexts(b), (unsigned long long)j->st.samples, (unsigned long long)j->st.lines, j->st.pushes, j->st.seconds,
                 j->st.seconds > 0 ? (double)j->st.samples / j->st.seconds / 1e6 : 0.0);
+    if (j->stats && j->bytes_out)                            /* a converting path is active: what the gain did */
+        fprintf(stderr, "rtl_wmbus_hip: device %d: input conversion: %llu of %llu bytes clipped (%.4f %%)\n", j->cfg.device, j->clipped, j->bytes_out,
+                100.0 * (double)j->clipped / (double)j->bytes_out);
     rc = EXIT_SUCCESS;
 out:
     if (!j->fast_exit || rc != EXIT_SUCCESS) wmbus_batch_close(b);      /* every exit path closes what it opened, unless the process is about to end anyway */
@@ -336,6 +346,24 @@ static unsigned parse_rate(const char *arg)
     return (double)r - v * mul > 1e-3 || v * mul - (double)r > 1e-3 ? 0 : r;      /* a whole number of Hz */
 }
 
+/* -I: the format's WMBUS_FMT_*, or -1 */
+static int parse_format(const char *arg)
+{
+    static const char *const names[] = {"cu8", "cs8", "cs16", "cf32"};      /* index = WMBUS_FMT_* */
+    for (int k = 0; k < 4; k++) if (!strcmp(arg, names[k])) return k;
+    return -1;
+}
+
+/* -g: decimal dB (may be negative) -> linear gain in Q8, clamp(rint(256 * 10^(dB / 20)), 1, 65535); 0 if it is not a number */
+static unsigned parse_gain_db(const char *arg)
+{
+    char *end;
+    const double db = strtod(arg, &end);
+    if (end == arg || *end || !(db == db) || db > 1000. || db < -1000.) return 0;
+    const double q = rint(256. * pow(10., db / 20.));
+    return q < 1. ? 1u : q > 65535. ? 65535u : (unsigned)q;
+}
+
 /* -G: "3" | "all" | "0,2,5" -> device list; returns the count or -1 */
 static int parse_devices(const char *arg, int *devs, int cap)
 {
@@ -387,7 +415,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -422,6 +450,16 @@ int main(int argc, char **argv)
         case 'R':
             cfg.input_rate_hz = parse_rate(optarg);
             if (!cfg.input_rate_hz) { print_usage(argv[0]); return EXIT_FAILURE; }
+            break;
+        case 'I': {
+            const int f = parse_format(optarg);
+            if (f < 0) { print_usage(argv[0]); return EXIT_FAILURE; }
+            cfg.input_format = (unsigned)f;
+            break;
+        }
+        case 'g':
+            cfg.input_gain_q8 = parse_gain_db(optarg);
+            if (!cfg.input_gain_q8) { print_usage(argv[0]); return EXIT_FAILURE; }
             break;
         default: print_usage(argv[0]); return EXIT_FAILURE;
         }
