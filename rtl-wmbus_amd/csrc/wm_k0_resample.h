@@ -262,7 +262,8 @@ template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0A
         for (uint32_t j = tid; j < L * T / 2u; j += nthr) tl[j / (T / 2u) * k0_row(T) + j % (T / 2u)] = tg[j];
     }
     if (blockIdx.x == 0) {
-        /* the next push's history: the last T - 1 samples of this one (a push is at least 2048 samples) */
+        /* the next push's history: the last T - 1 samples of this one (a push is a multiple of 4096 raw bytes, 512 samples of cf32
+         * at the least: n_in >= 512 > T - 1) */
         uint32_t *hist_out = a.hist_out + (uint64_t)s * (T - 1u);
         for (uint32_t j = tid; j < T - 1u; j += nthr) {
             const uint32_t r = a.n_in - (T - 1u) + j;

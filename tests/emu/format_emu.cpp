@@ -48,6 +48,12 @@ void *wm_emu_fmt_new(uint32_t fmt, uint32_t gain_q8, uint32_t L, uint32_t M, uin
 void wm_emu_fmt_free(void *p) { delete (Emu *)p; }
 unsigned wm_emu_fmt_bps(uint32_t fmt) { return k0_bps((int)fmt); }
 unsigned wm_emu_fmt_pick_tile(uint32_t L, uint32_t M, uint32_t T) { return k0_pick_tile(L, M, T); }
+/* as wm_emu_k0_start_at of resample_emu.cpp: the stream so far is in_first samples of x = 0 (cs16 / cf32: raw zeros) */
+void wm_emu_fmt_start_at(void *p, uint64_t in_first, uint64_t n_first)
+{
+    Emu *e = (Emu *)p;
+    e->n_in = in_first; e->n_out = n_first; e->rem = 0;
+}
 unsigned wm_emu_fmt_convert_tile(uint32_t fmt) { return WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k0_bps((int)fmt)); }
 
 /* One push of raw_bytes (multiple of 4096) of one capture.  window: receives the remainder of earlier pushes followed by this

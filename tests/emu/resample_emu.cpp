@@ -38,6 +38,15 @@ void *wm_emu_k0_new(uint32_t L, uint32_t M, uint32_t T, const int16_t *taps, uin
 void wm_emu_k0_free(void *p) { delete (Emu *)p; }
 unsigned wm_emu_k0_pick_tile(uint32_t L, uint32_t M, uint32_t T) { return k0_pick_tile(L, M, T); }
 unsigned wm_emu_k0_lds_bytes(uint32_t L, uint32_t M, uint32_t T, uint32_t tile) { return k0_lds_bytes(L, M, T, tile); }
+unsigned wm_emu_k0_span(uint32_t L, uint32_t M, uint32_t T, uint32_t tile) { return k0_span(L, M, T, tile); }
+/* A stream that is already in_first input samples and n_first outputs long (all of them x = 0, nothing waiting for a block): the next
+ * push starts at these counters.  The host's k0_plan starts at 0 and has no such entry; only the kernel's 64-bit arguments are
+ * reachable this way. */
+void wm_emu_k0_start_at(void *p, uint64_t in_first, uint64_t n_first)
+{
+    Emu *e = (Emu *)p;
+    e->n_in = in_first; e->n_out = n_first; e->rem = 0;
+}
 
 /* One push of raw_bytes (multiple of 4096) of one capture.  window: room for 4096 + 2 * outputs bytes; receives the remainder of
  * earlier pushes followed by this push's bytes.  Returns the bytes the pipeline would take (whole 4096-byte blocks). */

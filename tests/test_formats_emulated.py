@@ -22,6 +22,7 @@ FORMATS = [FR.CU8, FR.CS8, FR.CS16, FR.CF32]
 FMT_IDS = [FR.NAMES[f] for f in FORMATS]
 RATES = [0, 2048000, 2500000, 10000000]                # 0: already at 1.6 MS/s, the conversion kernel; else the resampler to 1.6 MS/s
 GAINS = [256, 1, 4096, 65535]
+WIDE = [FR.CS8, FR.CS16, FR.CF32]
 
 
 def test_the_abi_has_the_format_fields(wm):
@@ -54,6 +55,7 @@ def emu():
     L.wm_emu_fmt_bps.argtypes = [ctypes.c_uint]
     L.wm_emu_fmt_pick_tile.restype = ctypes.c_uint
     L.wm_emu_fmt_pick_tile.argtypes = [ctypes.c_uint] * 3
+    L.wm_emu_fmt_start_at.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     L.wm_emu_fmt_convert_tile.restype = ctypes.c_uint
     L.wm_emu_fmt_convert_tile.argtypes = [ctypes.c_uint]
     return L
@@ -67,11 +69,14 @@ def design(wm, rate):
     return L, M, taps
 
 
-def run_emulated(emu, raw, fmt, gain, L, M, taps, cuts, tile):
-    """(the bytes the pipeline takes, push by push, concatenated; the clip counts of the pushes summed)."""
+def run_emulated(emu, raw, fmt, gain, L, M, taps, cuts, tile, start_at=None):
+    """(the bytes the pipeline takes, push by push, concatenated; the clip counts of the pushes summed).  start_at: (input samples,
+    outputs) the stream already has behind it, all of them x = 0."""
     T = taps.shape[1] if taps is not None else 1
     tp = np.ascontiguousarray(taps, np.int16) if taps is not None else None
     h = emu.wm_emu_fmt_new(fmt, gain, L, M, T, tp.ctypes.data if tp is not None else None, tile)
+    if start_at is not None:
+        emu.wm_emu_fmt_start_at(h, start_at[0], start_at[1])
     got, off, clipped = [], 0, 0
     try:
         for n in cuts:
@@ -158,6 +163,112 @@ def test_result_does_not_depend_on_the_tile(emu, wm, fmt, rate):
         for tile in ((8, 72, 1000) if rate == 0 else (64, 190)):
             got, got_clips = run_emulated(emu, raw, fmt, g, L, M, taps, CUTS["uneven"], tile)
             assert np.array_equal(got, want) and got_clips == clips, (g, tile)
+
+
+SMALL_TILE = 190                                    # not a multiple of any 4 L: every block ends in a partial group
+CLIP_GAIN = 4096                                    # x 16: random full-range input clips
+
+
+def design_inputs(fmt, n_bytes, T):
+    """random, all-minimum, all-maximum of inputs() and the full-scale square wave of 3 T samples per half period, in the format."""
+    named = inputs(fmt, n_bytes)
+    lo, hi = {FR.CU8: (0, 255), FR.CS8: (-128, 127), FR.CS16: (-32768, 32767), FR.CF32: (-1.0, 1.0)}[fmt]
+    n = n_bytes // FR.BPS[fmt]
+    sq = np.repeat(np.where((np.arange(n) // (3 * T)) % 2 == 0, lo, hi), 2)
+    return {"random": named["random"], "min": named["min"], "max": named["max"], "square": FR.raw_bytes(sq, fmt)}
+
+
+FULL = os.environ.get("WMBUS_RESAMPLE_FULL") == "1"
+
+
+def check_design_on_the_emulator(emu, wm, fin, d, fmt, full=True):
+    """One design and format, bytes and clip counts.  Inputs random, all-minimum, all-maximum and the square wave at gain x 1, the
+    random one at x 16 as well; each under one push, the uneven cut and 4096-byte pushes with the library's tile; the random one
+    also with the small odd tile under the uneven cut.  full=False (the drawn designs, unless WMBUS_RESAMPLE_FULL=1): random and
+    square only, 4096-byte pushes with the library's tile and the uneven cut with the small one.  The input is sized so that the
+    pipeline gets at least three whole blocks.  A 4096-byte cf32 push is 512 samples: at T = 512 one more than the history the next
+    push needs."""
+    L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+    assert (L, M, T) == RR.geometry(fin, d)
+    tile = emu.wm_emu_fmt_pick_tile(L, M, T)
+    assert tile > 0
+    n_bytes = RR.blocks_input(L, M, FR.BPS[fmt])
+    cuts = RR.cuts_for(n_bytes)
+    assert min(cuts["each-4096"]) // FR.BPS[fmt] > T - 1
+    clip_seen = 0
+    for name, raw in design_inputs(fmt, n_bytes, T).items():
+        if not full and name not in ("random", "square"):
+            continue
+        for g in (256, CLIP_GAIN) if name == "random" else (256,):
+            want, clips = FR.convert(raw, fmt, g, L, M, taps)
+            want = want[:want.size // BLK * BLK]
+            assert want.size // BLK >= 3
+            runs = [("one", tile), ("uneven", tile), ("each-4096", tile)] if full else [("each-4096", tile)]
+            for cut, tl in runs + ([("uneven", SMALL_TILE)] if name == "random" or not full else []):
+                got, got_clips = run_emulated(emu, raw, fmt, g, L, M, taps, cuts[cut], tl)
+                assert got.size == want.size, (name, g, cut, tl)
+                assert np.array_equal(got, want), (name, g, cut, tl, int(np.argmax(got != want)))
+                assert got_clips == clips, (name, g, cut, tl)
+            clip_seen += clips
+    assert clip_seen > 0
+
+
+@pytest.mark.parametrize("fin,d", RR.CORNERS, ids=RR.CORNER_IDS)
+@pytest.mark.parametrize("fmt", FORMATS, ids=FMT_IDS)
+def test_corners_on_host_match_the_restatement(emu, wm, fmt, fin, d):
+    check_design_on_the_emulator(emu, wm, fin, d, fmt)
+
+
+def test_sampled_designs_on_host_match_the_restatement(emu, wm):
+    """tests/resample_ref.py::sample_designs, one drawn format each (cu8 at gain x 1 goes through the kernel's cu8 entry point in
+    test_resample_emulated.py); with WMBUS_RESAMPLE_FULL=1 cu8 as well, and the corners' whole matrix."""
+    rng = np.random.default_rng(0x5A)
+    for fin, d in RR.sample_designs():
+        for fmt in ((FR.CU8,) if FULL else ()) + (WIDE[int(rng.integers(3))],):
+            check_design_on_the_emulator(emu, wm, fin, d, fmt, full=FULL)
+
+
+# (in_hz, decimation): T = 512 with the smallest tile, upsampling, the flagship ratio 25 / 32, integer decimation
+LONG_STREAMS = [(25575000, 1), (1000000, 2), (2048000, 2), (3200000, 2), (2400000, 3)]
+
+
+@pytest.mark.parametrize("fin,d", LONG_STREAMS, ids=[f"{f}-d{d}" for f, d in LONG_STREAMS])
+def test_counters_beyond_32_bits(emu, wm, fin, d):
+    """K0Args.n_first / in_first are 64-bit and nm = (n_first + t_first) M: a cs16 stream whose first 2^32 - (a push and a half) input
+    samples were silence (x = 0: the carried history is zero, as in a fresh handle) is continued by 4096-byte pushes across 2^32
+    input samples (at L > M the output counter is beyond 2^32 from the start).  in_first is a multiple of M, so n_first = in_first L / M
+    is whole and no output is waiting for a block.  The restatement is evaluated at those output indices in Python integers.  At
+    2.4 MS/s a live stream is there after half an hour; the HOST's counters (k0_plan in wm_api.hip) start at 0 and cannot be set
+    through the ABI, so this reaches the kernel's arithmetic only."""
+    L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+    tile = emu.wm_emu_fmt_pick_tile(L, M, T)
+    per_push = BLK // FR.BPS[FR.CS16]
+    n_bytes = RR.blocks_input(L, M, FR.BPS[FR.CS16])
+    n_push = n_bytes // BLK
+    in_first = (2 ** 32 - per_push * (n_push // 2) - per_push // 2) // M * M
+    n_first = in_first * L // M
+    assert in_first < 2 ** 32 < in_first + n_bytes // 4 and in_first % M == 0 and n_first * M == in_first * L
+    x = np.random.default_rng(fin).integers(-32768, 32768, (n_bytes // 4, 2))
+    raw = FR.raw_bytes(x.reshape(-1), FR.CS16)
+    n_end = ((in_first + x.shape[0]) * L + M - 1) // M
+    idx = [((n * M) % L, (n * M) // L - in_first) for n in range(n_first, n_end)]      # phase, newest input within x: Python integers
+    assert all(0 <= b < x.shape[0] for _, b in idx)
+    p, b = np.array([i[0] for i in idx]), np.array([i[1] for i in idx]) + (T - 1)
+    xx = np.concatenate([np.zeros((T - 1, 2), np.int64), x.astype(np.int64)])
+    acc = np.zeros((len(idx), 2), np.int64)
+    for k in range(T):
+        acc += taps.astype(np.int64)[p, k][:, None] * xx[b - k]
+    v = (acc * 256 + (128 << 30)) >> 30
+    want = np.clip(v, 0, 255).astype(np.uint8).reshape(-1)
+    want = want[:want.size // BLK * BLK]
+    assert want.size // BLK >= 3
+    for tl in (tile, SMALL_TILE):
+        got, clips = run_emulated(emu, raw, FR.CS16, 256, L, M, taps, [BLK] * n_push, tl, start_at=(in_first, n_first))
+        assert np.array_equal(got, want), (tl, int(np.argmax(got != want)) if got.size == want.size else (got.size, want.size))
+        assert clips == int(np.count_nonzero((v < 0) | (v > 255)))
+    # in_first L = n_first M: the phases repeat, so the very same samples at the start of a stream give the same bytes -- a check of
+    # the Python-integer restatement above against format_ref.py, not of the kernel
+    assert np.array_equal(want, FR.pipeline_bytes(raw, FR.CS16, 256, L, M, taps))
 
 
 def test_gain_zero_is_unity_and_the_cu8_rule_is_unchanged(emu, wm):

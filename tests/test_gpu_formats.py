@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import format_ref as FR
-from test_formats_emulated import FMT_IDS, FORMATS, inputs
+from test_formats_emulated import FMT_IDS, FORMATS, design_inputs, inputs
+import resample_ref as RR
 from test_resample_emulated import BLK, CUTS, N_BLOCKS
 
 pytestmark = pytest.mark.gpu
@@ -69,6 +70,53 @@ def test_converted_bytes_and_clip_count_equal_the_restatement(wm, fmt, rate, n_s
             want_clips += clips
         assert clipped == want_clips, g
         assert bytes_out == n_streams * FR.convert(caps[0], fmt, g, L, M, taps)[0].size, g
+
+
+def corner_cases():
+    """cu8 and cf32 at every corner; all four formats at the T = 512 corners and at 16 / 1."""
+    out = []
+    for fin, d in RR.CORNERS:
+        L, M, T = RR.geometry(fin, d)
+        for fmt in (FORMATS if T == 512 or (L, M) == (16, 1) else [FR.CU8, FR.CF32]):
+            out.append(pytest.param(fin, d, fmt, id=f"{fin}-d{d}-{FR.NAMES[fmt]}"))
+    return out
+
+
+@pytest.mark.parametrize("fin,d,fmt", corner_cases())
+def test_corners_bytes_and_clip_count_equal_the_restatement(wm, fin, d, fmt):
+    """The compiled kernels at the corners of the design space (tests/resample_ref.py::CORNERS): 1 stream at gain x 1 and 8 streams
+    (random, minimum, maximum, square wave, random bit patterns) at x 16, one and two input windows, one push and 4096-byte pushes
+    (cf32 at T = 512: 512 samples against a history of 511).  max_push_bytes is the length of the one push, so at 16 / 1 and
+    decimation 16 the pipeline behind the resampler is sized by what a full raw push resamples to (push_cap in wmbus_open), 16 times
+    the raw push."""
+    L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+    n_bytes = RR.blocks_input(L, M, FR.BPS[fmt])
+    cuts = RR.cuts_for(n_bytes)
+    named = design_inputs(fmt, n_bytes, T)
+    rng = np.random.default_rng(fin + fmt)
+    for n_streams, g in ((1, 256), (8, 4096)):
+        caps = [named[k] for k in list(named)[:n_streams]] + [rng.integers(0, 256, n_bytes, dtype=np.uint8) for _ in range(n_streams - 4)]
+        want = [FR.convert(c, fmt, g, L, M, taps) for c in caps]
+        assert all(w[0].size // BLK >= 3 for w in want)
+        for windows in (1, 2):
+            for cut in ("one", "each-4096"):
+                with wm.Receiver(n_streams=n_streams, max_push_bytes=n_bytes, decimation=d, input_rate_hz=fin, input_format=fmt, input_gain_q8=g,
+                                 input_windows=windows) as rx:
+                    got, off, clipped, bytes_out = [[] for _ in caps], 0, 0, 0
+                    for n in cuts[cut]:
+                        rx.push([a[off:off + n] for a in caps]); off += n
+                        for s in range(n_streams):
+                            got[s].append(rx.read_resampled(s, cap=BLK + 2 * FR.n_outputs(n // FR.BPS[fmt], L, M)))
+                        tm = rx.timing()
+                        clipped += tm["input_clipped"]; bytes_out += tm["input_bytes_out"]
+                    assert rx.resampler_launches() == len(cuts[cut])
+                for s in range(n_streams):
+                    y = want[s][0]
+                    have = np.concatenate(got[s])
+                    assert have.size == y.size // BLK * BLK, (n_streams, windows, cut, s)
+                    assert np.array_equal(have, y[:have.size]), (n_streams, windows, cut, s, int(np.argmax(have != y[:have.size])))
+                assert clipped == sum(w[1] for w in want), (n_streams, windows, cut)
+                assert bytes_out == sum(w[0].size for w in want), (n_streams, windows, cut)
 
 
 @pytest.mark.parametrize("sample,key,kw,cli", GOLDENS, ids=GOLDEN_IDS)

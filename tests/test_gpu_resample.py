@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import resample_ref as RR
-from test_resample_emulated import BLK, CUTS, IDS, N_BLOCKS, N_YIELD, RATES, crc_clean, received, yield_captures
+from test_resample_emulated import BLK, CUTS, IDS, N_BLOCKS, N_YIELD, RATES, WORST, WORST_IDS, crc_clean, received, worst_yield_captures, yield_captures
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +124,54 @@ def test_text_equals_the_oracle_on_the_restated_bytes(wm, oracle, fs_khz, d):
         st = b.run_from(fill, on_push)
         assert st["samples"] == 3 * caps[0].size // 2         # raw samples consumed
     assert text == want
+
+
+# (generator fs_khz, decimation, samples): upsampling 8 / 5 (T = 16) and 1 / 32 (T = 512)
+CORNER_TEXT_RATES = [(1000, 2, 1 << 20), (25600, 1, 1 << 24)]
+
+
+@pytest.mark.parametrize("fs_khz,d,n_samples", CORNER_TEXT_RATES, ids=[str(r[0]) for r in CORNER_TEXT_RATES])
+def test_text_at_two_corner_rates_equals_the_oracle_on_the_restated_bytes(wm, oracle, fs_khz, d, n_samples):
+    L, M, T, taps = wm.resampler_design(fs_khz * 1000, 800000 * d)
+    assert L > M or T >= 256
+    caps = [synth_at(wm, fs_khz, 7300 + fs_khz + s, n_samples=n_samples)[0] for s in range(3)]
+    opts = oracle.make_opts(decimation=d)
+    want = []
+    for c in caps:
+        y = RR.resample_long(c, L, M, taps)
+        want.append(oracle.run(y[:y.size // BLK * BLK], opts)["text"])
+    assert all(len(w.splitlines()) >= 10 for w in want)
+    push = 1 << 21
+    with wm.Receiver(n_streams=3, max_push_bytes=push, decimation=d, input_rate_hz=fs_khz * 1000, input_windows=2, keep_taps=False) as rx:
+        assert rx.run(caps, push_bytes=BLK * 97) == want
+    text = [""] * 3
+    with wm.Batch(n_streams=3, max_push_bytes=push, decimation=d, input_rate_hz=fs_khz * 1000, input_windows=2) as b:
+        pos = {}
+
+        def fill(first, n, slab):
+            off = pos.get(first, 0)
+            k = min(push, caps[0].size - off)
+            for s in range(n):
+                slab[s, :k] = caps[first + s][off:off + k]
+            pos[first] = off + k
+            return k
+
+        def on_push(first, n, lines, tm):
+            for ln in lines:
+                text[ln["stream"]] += ln["text"]
+        st = b.run_from(fill, on_push)
+        assert st["samples"] == 3 * caps[0].size // 2
+    assert text == want
+
+
+@pytest.mark.parametrize("fin,d", WORST, ids=WORST_IDS)
+def test_capture_at_the_worst_ratios_is_received_like_a_native_one_on_the_gpu(wm, oracle, fin, d):
+    raw, fr_raw, nat, fr_nat = worst_yield_captures(wm, fin, d)
+    with wm.Receiver(n_streams=1, max_push_bytes=4 << 20, decimation=d, input_rate_hz=fin) as rx:
+        got = received(fr_raw, rx.run(raw)[0])
+    ref = received(fr_nat, oracle.run(nat, oracle.make_opts(decimation=d))["text"])
+    print(f"{fin} -> {800000 * d}: of the first {N_YIELD} frames placed: received resampled (GPU) {got}, native (oracle) {ref}")
+    assert got >= ref - 0.02 * N_YIELD
 
 
 def test_simultaneous_reception_behind_the_resampler(wm, oracle):

@@ -39,6 +39,9 @@ def emu():
     L.wm_emu_k0_pick_tile.argtypes = [ctypes.c_uint] * 3
     L.wm_emu_k0_lds_bytes.restype = ctypes.c_uint
     L.wm_emu_k0_lds_bytes.argtypes = [ctypes.c_uint] * 4
+    L.wm_emu_k0_span.restype = ctypes.c_uint
+    L.wm_emu_k0_span.argtypes = [ctypes.c_uint] * 4
+    L.wm_emu_k0_start_at.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     return L
 
 
@@ -104,6 +107,64 @@ def test_result_does_not_depend_on_the_tile(emu, wm, fin, d):
         assert np.array_equal(run_emulated(emu, cu8, L, M, taps, CUTS["uneven"], tile), want), tile
 
 
+SMALL_TILE = 190                                    # not a multiple of any 4 L: every block ends in a partial group
+
+
+def design_inputs(n_bytes, T):
+    named = inputs(n_bytes, T)
+    return {"random": named["random"], "min": named["zeros"], "max": named["ones"], "square": named["square"]}
+
+
+FULL = os.environ.get("WMBUS_RESAMPLE_FULL") == "1"
+
+
+def check_design_on_the_emulator(emu, wm, fin, d, full=True):
+    """One design, cu8 at gain x 1 through the kernel's cu8 entry point: the library's tile under all three cuts, the small odd tile
+    under the uneven one, four inputs, the input sized so that the pipeline gets at least three whole blocks.  full=False (the drawn
+    designs, unless WMBUS_RESAMPLE_FULL=1): random and square only, 4096-byte pushes with the library's tile, the uneven cut with
+    the small one."""
+    L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+    assert (L, M, T) == RR.geometry(fin, d)
+    tile = library_tile(emu, L, M, T)
+    n_bytes = RR.blocks_input(L, M, 2)
+    cuts = RR.cuts_for(n_bytes)
+    for name, cu8 in design_inputs(n_bytes, T).items():
+        if not full and name not in ("random", "square"):
+            continue
+        want = RR.pipeline_bytes(cu8, L, M, taps)
+        assert want.size // BLK >= 3
+        for cut, tl in ([("one", tile), ("uneven", tile)] if full else []) + [("each-4096", tile), ("uneven", SMALL_TILE)]:
+            got = run_emulated(emu, cu8, L, M, taps, cuts[cut], tl)
+            assert got.size == want.size, (name, cut, tl)
+            assert np.array_equal(got, want), (name, cut, tl, int(np.argmax(got != want)))
+        if name == "square":
+            assert want.min() == 0 and want.max() == 255      # the clamp is reached
+        if name == "min":
+            assert np.all(want[2 * T * max(1, L // M + 1):] == 0)
+        if name == "max":
+            assert np.all(want[2 * T * max(1, L // M + 1):] == 255)
+
+
+@pytest.mark.parametrize("fin,d", RR.CORNERS, ids=RR.CORNER_IDS)
+def test_corners_on_host_match_the_restatement(emu, wm, fin, d):
+    check_design_on_the_emulator(emu, wm, fin, d)
+
+
+def test_sampled_designs_on_host_match_the_restatement(emu, wm):
+    """The seeded draw of tests/resample_ref.py::sample_designs (WMBUS_RESAMPLE_N, WMBUS_RESAMPLE_SEED): with the corners, every value
+    of T and every value of L that the library accepts."""
+    for fin, d in RR.sample_designs():
+        check_design_on_the_emulator(emu, wm, fin, d, full=FULL)
+
+
+def test_long_restatement_equals_the_plain_one(wm):
+    rng = np.random.default_rng(3)
+    for fin, d in [(25600000, 1), (3200000, 2), (1000000, 2), (2048000, 2), (25575000, 1)]:
+        L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+        cu8 = rng.integers(0, 256, 2 * (3000 * M // L + 777), dtype=np.uint8)
+        assert np.array_equal(RR.resample_long(cu8, L, M, taps, chunk=1000), RR.resample(cu8, L, M, taps)), (fin, d)
+
+
 def crc_clean(text):
     return {l.split(";")[-1][2:] for l in text.splitlines() if l.split(";")[2] == "1"}
 
@@ -137,6 +198,38 @@ def test_resampled_capture_is_received_like_a_native_one(wm, oracle):
     got = received(fr_raw, oracle.run(RR.pipeline_bytes(raw, L, M, taps), opts)["text"])
     ref = received(fr_nat, oracle.run(nat, opts)["text"])
     print(f"of the first {N_YIELD} frames placed: received resampled {got}, native {ref}")
+    assert got >= ref - 0.02 * N_YIELD
+
+
+# The designs the response test ranks worst (tests/test_resampler_design.py::test_response_against_the_float_design): the integer
+# ratio 1 / 2 (float design already at -57.9 dB: no slack in T) and the T = 512 ratio 1 / 32 (Q14 rounding floor): (in_hz, decimation)
+WORST = [(3200000, 2), (25600000, 1)]
+WORST_IDS = [f"{f}-d{d}" for f, d in WORST]
+
+
+def worst_yield_captures(wm, fin, d):
+    """yield_captures() at another rate: same seed, same traffic, 6.5 s, the native twin at decimation x 800 kHz.  The generator
+    places about 55 frames a second with these settings, so N_YIELD frames need nearly the whole 6.5 s at any rate: nothing is
+    shortened."""
+    assert fin % 1000 == 0
+    seed, seconds, kinds = 0xA11CE, 6.5, wm.T1 | wm.C1A | wm.C1B | wm.S1
+    raw, fr_raw = wm.synth_capture(seed=seed, n_samples=int(fin * seconds) // 2048 * 2048, fs_khz=fin // 1000, kinds=kinds, frames_per_s=160.0)
+    nat, fr_nat = wm.synth_capture(seed=seed, n_samples=int(800000 * d * seconds) // 2048 * 2048, fs_khz=800 * d, kinds=kinds, frames_per_s=160.0)
+    assert len(fr_raw) >= N_YIELD and len(fr_nat) >= N_YIELD
+    return raw, fr_raw[:N_YIELD], nat, fr_nat[:N_YIELD]
+
+
+@pytest.mark.parametrize("fin,d", WORST, ids=WORST_IDS)
+def test_capture_at_the_worst_ratios_is_received_like_a_native_one(wm, oracle, fin, d):
+    """test_resampled_capture_is_received_like_a_native_one at the ratios with the poorest stop band: the same reference (the oracle
+    on the native twin) and the same margin."""
+    raw, fr_raw, nat, fr_nat = worst_yield_captures(wm, fin, d)
+    L, M, T, taps = wm.resampler_design(fin, 800000 * d)
+    opts = oracle.make_opts(decimation=d)
+    y = RR.resample_long(raw, L, M, taps)
+    got = received(fr_raw, oracle.run(y[:y.size // BLK * BLK], opts)["text"])
+    ref = received(fr_nat, oracle.run(nat, opts)["text"])
+    print(f"{fin} -> {800000 * d}: of the first {N_YIELD} frames placed: received resampled {got}, native {ref}")
     assert got >= ref - 0.02 * N_YIELD
 
 
