@@ -34,81 +34,45 @@
 
 namespace {
 
-/* one formatted line of a push: where its text lies in its part's buffer (round 6: a std::string per line was a heap allocation per
- * line -- with eight ranks' contexts decoding at once on one host, 64 x 4 threads in malloc, the decode of a context-push took
- * 18 ms instead of 2.8: tools/host_replay.py) */
-struct LineRec {
-    uint64_t sample; uint32_t stream; uint8_t chain, algo, crc_ok; uint32_t seq; uint32_t part, off, len;
-};
-struct LinePart { std::vector<LineRec> recs; std::string text; };
-
-/* Persistent host worker pool of a context (packet decoders): run(n, f) executes f(0..n-1) on the
- * workers and the caller; threads are created once, not per push. */
-class WorkerPool {
-public:
-    explicit WorkerPool(unsigned n_workers)
-    {
-        for (unsigned i = 0; i < n_workers; i++) th_.emplace_back([this] { loop(); });
-    }
-    ~WorkerPool()
-    {
-        { std::lock_guard<std::mutex> lk(m_); stop_ = true; }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    unsigned size() const { return (unsigned)th_.size(); }
-    template <typename F> void run(unsigned n, F &&f)
-    {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            job_ = f; next_ = 0; total_ = n; done_ = 0; gen_++;      /* the job lives in the pool, not on this stack frame */
-        }
-        cv_.notify_all();
-        work();                                              /* the caller helps */
-        std::unique_lock<std::mutex> lk(m_);
-        /* every item done AND every worker that picked this generation up has left work(): nothing of
-         * this run can still be executing when the caller's captures go out of scope */
-        cv_done_.wait(lk, [&] { return done_ == total_ && active_ == 0; });
-        job_ = nullptr;
-    }
-private:
-    void work()
-    {
-        for (;;) {
-            unsigned i;
-            { std::lock_guard<std::mutex> lk(m_); if (next_ >= total_) return; i = next_++; }
-            job_(i);                                         /* job_ only changes while no item is outstanding */
-            { std::lock_guard<std::mutex> lk(m_); if (++done_ == total_) cv_done_.notify_all(); }
-        }
-    }
-    void loop()
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&] { return stop_ || (gen_ != seen && job_ != nullptr); });
-                if (stop_) return;
-                seen = gen_; active_++;
-            }
-            work();
-            { std::lock_guard<std::mutex> lk(m_); if (--active_ == 0) cv_done_.notify_all(); }
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, cv_done_;
-    std::function<void(unsigned)> job_;
-    unsigned next_ = 0, total_ = 0, done_ = 0, active_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
+class WorkerPool;              /* wm_host_decode.h */
 
 struct HostDecoder {           /* persistent across pushes */
     wm_decoder dec;
     uint32_t owed;             /* chips to request at the start of the next push */
     uint64_t fed;              /* push in which the decoder last took chips (see the dropped-burst clean-up in wmbus_collect) */
 };
+
+/* Every device and page-locked allocation of a context is made here and recorded; wmbus_close -- and with it every refused open --
+ * frees what was recorded, so no buffer can be allocated and not freed.  (Sub-allocations such as Framer::d_sync_seen are views.) */
+struct Owned {
+    std::vector<void *> dev, pinned;
+    hipError_t dbytes(void **p, size_t n) { const hipError_t e = hipMalloc(p, n); if (e == hipSuccess) dev.push_back(*p); return e; }
+    template <typename T> hipError_t dalloc(T **p, size_t n) { return dbytes((void **)p, n * sizeof(T)); }
+    template <typename T> hipError_t halloc(T **p, size_t n) { const hipError_t e = hipHostMalloc((void **)p, n * sizeof(T)); if (e == hipSuccess) pinned.push_back(*p); return e; }
+    void release() { for (void *p : dev) hipFree(p); for (void *p : pinned) hipHostFree(p); dev.clear(); pinned.clear(); }
+};
+
+/* One framer's share of a context, indexed by WMBUS_ALGO_*: [0] the run-length framer, [1] clock recovery + time2. */
+struct Framer {
+    uint32_t C = 0, cap = 0, nseg_cap = 0;             /* segment length (decimated samples), chips a segment's region holds, segments per row at most */
+    uint32_t state_bytes = 0;                          /* sizeof(WmRlaState) / sizeof(WmClkState) */
+    uint32_t *d_chips = nullptr, *d_counts = nullptr;
+    void *d_st_start = nullptr, *d_st_final = nullptr, *d_st_carry = nullptr;   /* carry: [2][rows], see wmbus_ctx.carry_in */
+    uint32_t *d_sync_seen = nullptr;                   /* [2][S][nseg_cap] access-code chip seen in region (a view into d_scalars) */
+    uint32_t *d_list = nullptr;                        /* re-run list; every verifier has its own: collect's slow path starts from what the LAST verify of each kind left */
+    uint32_t *d_bad = nullptr;                         /* [2][nseg_cap][S] the verifier's verdict per segment (K2Args.bad) */
+    uint32_t sc = 0;                                   /* SC_* index of its round counters: list round r counts in sc + r, the last verification in sc + rounds */
+    unsigned round0 = 0, rounds = 0;                   /* list rounds round0 .. rounds - 1 are enqueued unattended, see WM_MAX_ROUNDS (the run-length framer's start at 1) */
+    K2Args k2{};                                       /* this push's launch arguments (collect's slow path re-uses them) */
+};
+
+/* The demodulation kernels a context can launch, resolved once in wmbus_open (k1_resolve). */
+enum K1Role { K1_FIRST /* first pass without the RSSI */, K1_RSSI /* RSSI of the listed tiles */, K1_FULL /* everything, every tile */,
+              K1_REPAIR /* the general kernel: re-run lists, option paths */, K1_ROLES };
+struct K1Entry { void (*kernel)(K1Args) = nullptr; uint32_t threads = 0, lds = 0, lds_most = 0; };      /* lds_most: the most any context launches it with (the attribute) */
+
+/* events of a push, on the context's stream (wait_gpu turns pairs of them into wmbus_timing) */
+enum { EV_PUSH, EV_K1, EV_K1_END, EV_CLK, EV_RLA, EV_FR_END, EV_K3, EV_K3_END, EV_D2H_END, EV_RS, EV_RS_END /* the RSSI launch over the listed tiles */, EV_COUNT };
 
 }  // namespace
 
@@ -117,15 +81,15 @@ struct wmbus_ctx {
     char err[256] = {0};
     hipStream_t stream = nullptr;                      /* every kernel of the context */
     hipStream_t copy_stream = nullptr;                 /* wmbus_stage's H2D copies (north_star: "pinned hipMemcpyAsync on a side stream") */
-    hipEvent_t ev[11] = {};                            /* [9], [10]: the RSSI launch over the listed tiles (timing) */
+    hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_staged = nullptr;                    /* recorded on copy_stream at process(): the push's input is in HBM */
     hipEvent_t ev_turn = nullptr;                       /* behind the main part of this context's K1: the next context's K1 waits for it */
     uint32_t n_win = 1, fill = 0;                      /* input windows (cfg.input_windows) and the one wmbus_stage fills now */
     /* geometry */
-    uint32_t d = 2, S = 1, C[2] = {8192, 32768}, Mcap = 0, nseg_cap[2] = {0, 0}, ntiles_cap = 0, T = WM_K1_TILE2;
-    uint32_t cap[2] = {0, 0}, flags = 0;
+    uint32_t d = 2, S = 1, Mcap = 0, ntiles_cap = 0, T = WM_K1_TILE2, flags = 0;
+    Framer fr[2];
+    Owned mem;
     uint64_t in_stride = 0, n0 = 0;
-    size_t staged = 0;
     size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
     /* cfg.input_rate_hz / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) -- the resampler
      * (`resample`), which also reads every format and applies the gain, or for an input at the native rate the conversion kernel
@@ -136,7 +100,7 @@ struct wmbus_ctx {
         bool on = false, resample = false;
         uint32_t fmt = WMBUS_FMT_CU8, bps = 2, gain = 0;   /* cfg.input_format, its raw bytes per sample, cfg.input_gain_q8 */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
-        size_t raw_cap = 0; uint64_t raw_stride = 0;
+        uint64_t raw_stride = 0;
         uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
         int16_t *d_taps = nullptr;                     /* [L][T] */
         uint32_t *d_hist = nullptr;                    /* [2][S][T - 1] {I, Q} int16 */
@@ -157,20 +121,12 @@ struct wmbus_ctx {
      * certified; if wmbus_collect has to finish rounds, the re-runs of first tiles / segments still find the state
      * they must start from, and the commit is simply made again. */
     uint32_t carry_in = 0; bool committed = false;
-    uint32_t *d_chips[2] = {}, *d_counts[2] = {};
-    void *d_st_start[2] = {}, *d_st_final[2] = {}, *d_st_carry[2] = {};
-    uint32_t *d_list2 = nullptr;                        /* run-length re-run list */
-    uint32_t *d_list_ema = nullptr;                     /* RSSI repair list (one entry per row at most); every verifier has its own list:
-                                                           collect's slow path starts from what the LAST verify of each kind left */
-    uint32_t *d_list = nullptr;
+    uint32_t *d_list_ema = nullptr;                     /* RSSI repair list (one entry per row at most) */
     uint32_t *d_scalars = nullptr;                      /* head of ONE allocation zeroed once per push: scalars | sync_seen[0] | sync_seen[1] |
                                                            nchain + bump counter (separate fills cost a context's chain of launches 40 us each) */
     size_t zero_words = 0;
-    uint32_t *d_sync_seen[2] = {};                      /* per framer: [2][S][nseg_cap] access-code chip seen in region */
     uint32_t *d_spill = nullptr, *d_chain = nullptr, *d_nchain = nullptr; uint32_t spill_words = 0;   /* WmSpill (wm_dev.h) */
-    unsigned ema_rounds = 1, fr_rounds = 2, rla_rounds = 3;   /* hand-off rounds enqueued unattended, see WM_MAX_ROUNDS; the run-length framer's
-                                                          counters start at index 1 (its list rounds: 1 .. rla_rounds - 1) */
-    unsigned rla_fin = 3;                               /* this push: index of the run-length framer's last (unattended) verification */
+    unsigned ema_rounds = 1;                            /* RSSI hand-off rounds enqueued unattended, see WM_MAX_ROUNDS (the framers': Framer::rounds) */
     bool opt_rounds = true;                             /* hand-off rounds are enqueued unattended (cfg.rounds_on_host = 0) */
     bool poisoned = false, gpu_decode = true;                              /* an internal error left the carried state undefined */
     uint32_t *d_first_bad = nullptr;                    /* [2][S] first uncertified EMA tile of a row, or ~0 */
@@ -187,9 +143,6 @@ struct wmbus_ctx {
     uint32_t *d_rs_flags = nullptr, *d_rs_list = nullptr;   /* [ntiles_cap][S] chains read per (tile, capture); the tiles listed */
     WmItemRec *d_plans = nullptr;                          /* [4 S + hits_cap] what k3_spans leaves k3_bursts about every item */
     uint32_t *d_ckpt = nullptr; uint32_t nck = 0;       /* clock kernel checkpoints [2][S][nseg_cap][nck][16] */
-    uint32_t *d_bad = nullptr;                          /* [2][nseg_cap[0]][S] the run-length verifier's verdict per segment (K2Args.bad) */
-    uint32_t *d_bad_clk = nullptr;                      /* [2][nseg_cap[1]][S] the clock verifier's */
-    bool rla_chains = true;                             /* the run-length re-run lanes walk chains from their second list round on (K2Args.bad) */
     uint2 *d_hits = nullptr; uint32_t hits_cap = 0;
     uint32_t *d_pending = nullptr;
     uint32_t hdr_cap = 0, words_cap = 0, pkts_cap = 0, bytes_cap = 0;
@@ -200,7 +153,8 @@ struct wmbus_ctx {
     WmPkt *h_pkts = nullptr; uint8_t *h_bytes = nullptr;
     void *dv_hdr = nullptr, *dv_words = nullptr, *dv_pkts = nullptr, *dv_bytes = nullptr;    /* their device views */
     uint32_t n_hdr = 0, n_words = 0, n_pkts = 0;
-    K1Args k1a{}; K2Args k2clk{}, k2rla{}; uint32_t ntiles = 0;    /* this push's launch arguments (collect's slow path re-uses them) */
+    K1Entry k1[K1_ROLES];                               /* the demodulation kernels of this context */
+    K1Args k1a{}; uint32_t ntiles = 0;                  /* this push's launch arguments (collect's slow path re-uses them) */
     std::vector<HostDecoder> decs;                      /* [stream][chain][algo] */
     std::vector<wm_twin> twins;                         /* [stream][chain][2]: the last lines printed (cfg.dedup_twins) */
     std::unique_ptr<WorkerPool> pool;                   /* packet-decoder workers, created on first use */
@@ -232,18 +186,16 @@ int fail(wmbus_ctx *c, int code, const char *fmt, ...)
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
     return fail((c), WMBUS_EDEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
-template <typename T> hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
-
 /* Hand-off verification runs a few rounds WITHOUT asking the host: verify -> re-run list on the device -> list launch
  * with a fixed grid -> verify ..., each round with its own counter; the host only looks at the last counters when it
  * collects the push and finishes the (rare) leftovers round by round. */
 enum { WM_MAX_DEVICES = 64 };                    /* per-device tables (K1 order, kernel attributes); wmbus_open refuses ordinals beyond */
-/* How many: wmbus_ctx.ema_rounds / fr_rounds.  A batch of whole waves enqueues one RSSI round and two framer rounds (bench
+/* How many: wmbus_ctx.ema_rounds / Framer::rounds.  A batch of whole waves enqueues one RSSI round and two framer rounds (bench
  * workload: clock re-runs 1400, then < 10, then 0; run-length 2300, then 0; a third costs every push 0.2 ms of empty launches).
  * A small batch is bound by its chain of dependent launches and by every host round trip in it, and its short segments
  * (wmbus_open) cascade further: it enqueues more rounds, so that the host-driven path (0.5 ms per round) stays the exception. */
 enum { WM_MAX_ROUNDS = 6 };                      /* counters per kind of round: rounds + 1 <= 8 slots of the SC_* layout below (the run-length framer's
-                                                    index runs to rla_rounds <= WM_MAX_ROUNDS + 1) */
+                                                    index runs to its rounds <= WM_MAX_ROUNDS + 1) */
 /* bounded grids of the burst kernels and of the RSSI launch over the listed tiles (launch_k3) */
 #ifndef WM_K3_BLOCKS
 #define WM_K3_BLOCKS 64           /* build-time A/B (tools/build_variant.sh): r02 256 -> 64 blocks + 6 %, 16 blocks - 9 % */
@@ -253,7 +205,7 @@ enum { WM_K1_TPB_DEFAULT = 2 };                /* tiles per block of the demodul
 enum { SC_ERR = 0, SC_NHITS = 1, SC_NHDR = 2, SC_NWORDS = 3, SC_NPKTS = 4, SC_NBYTES = 5, SC_SLOW = 6, SC_CHIPS = 8 /* [algo][chain] */,
        SC_RS_N = 12 /* tiles listed for the RSSI-on-demand launch */, SC_RS_FAIL = 13 /* a lane that is read could not prove its value */,
        SC_CLIP = 14 /* K0: output bytes the clamp changed (wmbus_timing.input_clipped) */,
-       SC_EMA = 16 /* [ema_rounds + 1] */, SC_CLK = 24 /* [fr_rounds + 1] */, SC_RLA = 32 /* [rla_rounds + 1] */, SC_COUNT = 40 };
+       SC_EMA = 16 /* [ema_rounds + 1] */, SC_CLK = 24 /* [fr[1].rounds + 1] */, SC_RLA = 32 /* [fr[0].rounds + 1] */, SC_COUNT = 40 };
 static_assert(WM_MAX_ROUNDS + 2 <= 8 && SC_RLA + WM_MAX_ROUNDS + 2 <= SC_COUNT, "every kind of round keeps its counters inside its eight SC_* slots");
 
 /* 4096 bytes per capture from src + row * sstride + soff to dst + row * dstride (256 threads x 16 bytes).  The input
@@ -302,43 +254,53 @@ __global__ __launch_bounds__(256) void k_sum_counts(WmPush g, const uint32_t *co
     }
 }
 
-template <int D, bool SHIFT, bool GEN, bool FAST = false, int RS = 0, int NT = 256> int launch_k1v3(wmbus_ctx *c, const K1Args &a, dim3 grid, hipStream_t st)
+/* the reference's default switches: what the demodulation kernel without the option paths (k1_demod2<.., GEN = false>) and RSSI on demand are built for */
+bool default_switches(uint32_t flags)
 {
-    const size_t sm = K1GeoT<NT>::smem(D ? D : (int)c->d, SHIFT);
-    static std::atomic<size_t> set_for[WM_MAX_DEVICES];     /* per device: the attribute call is not free, a push makes several launches */
-    if (set_for[c->cfg.device] < sm) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k1_demod2<D, SHIFT, GEN, FAST, RS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-        set_for[c->cfg.device] = sm;
+    return (flags & (WM_F_ACCURATE | WM_F_T1C1 | WM_F_S1 | WM_F_APPROX1 | WM_F_APPROX2)) == (WM_F_ACCURATE | WM_F_T1C1 | WM_F_S1);
+}
+
+template <int D, bool SHIFT, bool GEN, bool FAST = false, int RS = 0, int NT = 256> K1Entry k1_entry(const wmbus_ctx *c)
+{
+    return K1Entry{k1_demod2<D, SHIFT, GEN, FAST, RS, NT>, (uint32_t)NT, (uint32_t)K1GeoT<NT>::smem(D ? D : (int)c->d, SHIFT), (uint32_t)K1GeoT<NT>::smem(D ? D : (int)WM_MAX_DECIM, SHIFT)};
+}
+
+/* The kernel of every role for decimation D (0: any rate without a kernel of its own) with or without -s.  Tolerance mode is an option
+ * of the default switches' kernels only (everything else stays exact; the listed tiles' RSSI is the same in tolerance mode). */
+template <int D, bool SHIFT> void k1_resolve_for(wmbus_ctx *c)
+{
+    const bool tol = c->cfg.tolerance_mode;
+    c->k1[K1_REPAIR] = k1_entry<D, SHIFT, true>(c);
+    c->k1[K1_FULL] = D == 0 || !default_switches(c->flags) ? c->k1[K1_REPAIR] : tol ? k1_entry<D, SHIFT, false, true>(c) : k1_entry<D, SHIFT, false>(c);
+    if (!c->rs_od) return;                       /* RSSI on demand (open_geometry has checked the switches): the first pass without it ... */
+    c->k1[K1_FIRST] = tol ? k1_entry<D, SHIFT, false, true, 1>(c) : k1_entry<D, SHIFT, false, false, 1>(c);
+    if (c->k1_big)                               /* ... on the 2000-sample tile of 512 threads (the launch's grid counts THOSE tiles; wmbus_ctx.k1_big) */
+        c->k1[K1_FIRST] = tol ? k1_entry<2, false, false, true, 1, 512>(c) : k1_entry<2, false, false, false, 1, 512>(c);
+    c->k1[K1_RSSI] = k1_entry<D, SHIFT, false, false, 2>(c);
+}
+
+/* wmbus_open: one entry per role this context can launch, each kernel's dynamic LDS allowed for */
+int k1_resolve(wmbus_ctx *c)
+{
+    const bool sh = c->flags & WM_F_SHIFT;
+    if (c->cfg.prefilter == WMBUS_PREFILTER_POLYPHASE)
+        for (auto &e : c->k1) e = K1Entry{k1_demod_ppf, 256u, (uint32_t)K1PpfGeo::smem(), (uint32_t)K1PpfGeo::smem()};
+    else switch (c->d) {
+    case 2: sh ? k1_resolve_for<2, true>(c) : k1_resolve_for<2, false>(c); break;
+    case 3: sh ? k1_resolve_for<3, true>(c) : k1_resolve_for<3, false>(c); break;
+    case 4: sh ? k1_resolve_for<4, true>(c) : k1_resolve_for<4, false>(c); break;
+    case 5: sh ? k1_resolve_for<5, true>(c) : k1_resolve_for<5, false>(c); break;
+    default: sh ? k1_resolve_for<0, true>(c) : k1_resolve_for<0, false>(c); break;      /* any other rate */
     }
-    hipLaunchKernelGGL((k1_demod2<D, SHIFT, GEN, FAST, RS, NT>), grid, dim3(NT), sm, st, a);
-    HIPCHK(c, hipGetLastError());
+    for (const auto &e : c->k1)
+        if (e.kernel) HIPCHK(c, hipFuncSetAttribute((const void *)e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds_most));
     return 0;
 }
 
-/* the default switches' first pass runs the kernel without the option paths (k1_demod2<.., GEN = false>) */
-template <int D, bool SHIFT> int launch_k1v2(wmbus_ctx *c, const K1Args &a, dim3 grid, hipStream_t st, int rs, bool big)
+int launch_k1(wmbus_ctx *c, K1Role role, const K1Args &a, dim3 grid)
 {
-    const uint32_t need = WM_F_ACCURATE | WM_F_T1C1 | WM_F_S1, never = WM_F_APPROX1 | WM_F_APPROX2;
-    if (D == 2 && !SHIFT && rs == 1 && big)      /* ... on the 2000-sample tile of 512 threads (the caller's grid counts THOSE tiles; wmbus_ctx.k1_big) */
-        return c->cfg.tolerance_mode ? launch_k1v3<2, false, false, true, 1, 512>(c, a, grid, st) : launch_k1v3<2, false, false, false, 1, 512>(c, a, grid, st);
-    if (D != 0 && rs == 1)                       /* RSSI on demand (wmbus_open has checked the switches): the first pass without it */
-        return c->cfg.tolerance_mode ? launch_k1v3<D, SHIFT, false, true, 1>(c, a, grid, st) : launch_k1v3<D, SHIFT, false, false, 1>(c, a, grid, st);
-    if (D != 0 && rs == 2) return launch_k1v3<D, SHIFT, false, false, 2>(c, a, grid, st);     /* ... and the listed tiles' RSSI (the same in tolerance mode) */
-    if (D != 0 && a.relist == nullptr && (c->flags & need) == need && !(c->flags & never))
-        /* tolerance mode (an option of the default switches' kernel only; everything else stays exact) */
-        return c->cfg.tolerance_mode ? launch_k1v3<D, SHIFT, false, true>(c, a, grid, st) : launch_k1v3<D, SHIFT, false>(c, a, grid, st);
-    return launch_k1v3<D, SHIFT, true>(c, a, grid, st);
-}
-
-int launch_k1_ppf(wmbus_ctx *c, const K1Args &a, dim3 grid, hipStream_t st)
-{
-    const size_t sm = K1PpfGeo::smem();
-    static std::atomic<size_t> set_for[WM_MAX_DEVICES];
-    if (set_for[c->cfg.device] < sm) {
-        HIPCHK(c, hipFuncSetAttribute((const void *)k1_demod_ppf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-        set_for[c->cfg.device] = sm;
-    }
-    hipLaunchKernelGGL(k1_demod_ppf, grid, dim3(256), sm, st, a);
+    const K1Entry &e = c->k1[role];
+    hipLaunchKernelGGL(e.kernel, grid, dim3(e.threads), e.lds, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -395,6 +357,8 @@ double now_ms()
 
 }  // namespace
 
+#include "wm_host_decode.h"
+
 extern "C" {
 
 void wmbus_runtime_init(void)
@@ -439,13 +403,7 @@ void wmbus_close(wmbus_ctx *c)
         std::lock_guard<std::mutex> lk(kc.m);
         if (kc.owner == c) { kc.last = nullptr; kc.owner = nullptr; }      /* nobody may wait on an event that is about to go */
     }
-    void *dev[] = {c->k0.d_raw, c->k0.d_taps, c->k0.d_hist, c->k0.d_rem, c->d_plans, c->d_rs_flags, c->d_rs_list, c->d_bad, c->d_bad_clk, c->d_hist, c->d_list_ema, c->d_spill, c->d_chain, c->d_list2, c->d_first_bad, c->d_ckpt, c->d_in, c->d_dphi, c->d_rssi, c->d_bits, c->d_lut, c->d_ema_head, c->d_ema_tail, c->d_ema_carry,
-                   c->d_chips[0], c->d_chips[1], c->d_counts[0], c->d_counts[1], c->d_st_start[0], c->d_st_start[1],
-                   c->d_st_final[0], c->d_st_final[1], c->d_st_carry[0], c->d_st_carry[1], c->d_list, c->d_scalars,
-                   c->d_hits, c->d_pending};
-    for (void *p : dev) if (p) hipFree(p);
-    void *host[] = {c->h_scalars, c->h_hdr, c->h_words, c->h_pending, c->h_pkts, c->h_bytes};
-    for (void *p : host) if (p) hipHostFree(p);
+    c->mem.release();
     for (auto &e : c->ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : {c->ev_staged, c->ev_turn}) if (e) hipEventDestroy(e);
     if (c->copy_stream && c->copy_stream != c->stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
@@ -453,97 +411,96 @@ void wmbus_close(wmbus_ctx *c)
     delete c;
 }
 
-int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
+/* wmbus_open, step 1: is the configuration one the library takes, and is its device there?  Designs the resampler on the way (a rate
+ * without a design is a refusal); `k0_taps` keeps its taps for open_init. */
+static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
 {
-    if (!cfg || !out) return WMBUS_EINVAL;
-    *out = nullptr;
-    wmbus_ctx *c = new wmbus_ctx();
-    c->cfg = *cfg;
-    auto bail = [&](int code) { *out = c; return code; };   /* caller reads the message, then closes */
-
-    if (cfg->decimation < 1 || cfg->decimation > WM_MAX_DECIM) return bail(fail(c, WMBUS_EINVAL, "decimation must be 1..%u", WM_MAX_DECIM));
-    if (cfg->n_streams < 1) return bail(fail(c, WMBUS_EINVAL, "n_streams must be >= 1"));
+    const wmbus_cfg *cfg = &c->cfg;
+    if (cfg->decimation < 1 || cfg->decimation > WM_MAX_DECIM) return fail(c, WMBUS_EINVAL, "decimation must be 1..%u", WM_MAX_DECIM);
+    if (cfg->n_streams < 1) return fail(c, WMBUS_EINVAL, "n_streams must be >= 1");
     if (cfg->max_push_bytes < WMBUS_BLOCK_BYTES || cfg->max_push_bytes % WMBUS_BLOCK_BYTES)
-        return bail(fail(c, WMBUS_EINVAL, "max_push_bytes must be a positive multiple of 4096"));
+        return fail(c, WMBUS_EINVAL, "max_push_bytes must be a positive multiple of 4096");
     if (cfg->prefilter != WMBUS_PREFILTER_BOXCAR && cfg->prefilter != WMBUS_PREFILTER_POLYPHASE)
-        return bail(fail(c, WMBUS_EINVAL, "prefilter must be WMBUS_PREFILTER_BOXCAR or WMBUS_PREFILTER_POLYPHASE"));
+        return fail(c, WMBUS_EINVAL, "prefilter must be WMBUS_PREFILTER_BOXCAR or WMBUS_PREFILTER_POLYPHASE");
     if (cfg->atan_mode < WMBUS_ATAN_LIBM || cfg->atan_mode > WMBUS_ATAN_APPROX2)
-        return bail(fail(c, WMBUS_EINVAL, "atan_mode must be WMBUS_ATAN_LIBM, WMBUS_ATAN_APPROX1 or WMBUS_ATAN_APPROX2"));
+        return fail(c, WMBUS_EINVAL, "atan_mode must be WMBUS_ATAN_LIBM, WMBUS_ATAN_APPROX1 or WMBUS_ATAN_APPROX2");
     if (cfg->prefilter == WMBUS_PREFILTER_POLYPHASE && (cfg->decimation != 2 || cfg->simultaneous))
-        return bail(fail(c, WMBUS_EINVAL, "the polyphase pre-filter is the 1.6 MS/s design of rtl_wmbus.c:258-294: decimation 2, no -s"));
-    if (cfg->input_format > WMBUS_FMT_CF32) return bail(fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format));
-    if (cfg->input_gain_q8 > 65535u) return bail(fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8));
-    c->push_cap = cfg->max_push_bytes;
-    c->k0.fmt = cfg->input_format; c->k0.bps = k0_bps((int)cfg->input_format); c->k0.gain = cfg->input_gain_q8;
-    const bool converts = cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u);
-    std::vector<int16_t> k0_taps;
+        return fail(c, WMBUS_EINVAL, "the polyphase pre-filter is the 1.6 MS/s design of rtl_wmbus.c:258-294: decimation 2, no -s");
+    if (cfg->input_format > WMBUS_FMT_CF32) return fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format);
+    if (cfg->input_gain_q8 > 65535u) return fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8);
+    auto &k = c->k0;
+    k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
     if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
         unsigned L = 0, M = 0, T = 0;
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
         const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
-        if (why) return bail(fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u));
-        if (c->k0.fmt == WMBUS_FMT_CS16 || c->k0.fmt == WMBUS_FMT_CF32)
+        if (why) return fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u);
+        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32)
             for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples: |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
                 int64_t abs_total = 0;
-                for (unsigned k = 0; k < T; k++) abs_total += std::abs((int)k0_taps[(size_t)p * T + k]);
-                if (32768ll * abs_total >= (1ll << 31)) return bail(fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's accumulator bound for 16-bit input is exceeded (phase %u)", p));
+                for (unsigned t = 0; t < T; t++) abs_total += std::abs((int)k0_taps[(size_t)p * T + t]);
+                if (32768ll * abs_total >= (1ll << 31)) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's accumulator bound for 16-bit input is exceeded (phase %u)", p);
             }
-        c->k0.on = true; c->k0.resample = true; c->k0.L = L; c->k0.M = M; c->k0.T = T;
-        c->k0.raw_cap = cfg->max_push_bytes;
-        c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
-        /* the pipeline behind K0 is sized for what a full raw push resamples to, plus the remainder in front of it */
-        const uint64_t most = ((uint64_t)(cfg->max_push_bytes / c->k0.bps) * L + M - 1u) / M * 2u;
-        c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
-        const uint32_t tile = k0_pick_tile(L, M, T);
-        if (!tile) return bail(fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T));
-        c->k0.tile = tile; c->k0.lds = k0_lds_bytes(L, M, T, tile);
-    } else if (converts) {                                   /* the native rate in another format or with a gain: the conversion kernel alone */
-        c->k0.on = true; c->k0.L = c->k0.M = c->k0.T = 1u;
-        c->k0.raw_cap = cfg->max_push_bytes;
-        c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
-        c->push_cap = (size_t)((cfg->max_push_bytes / c->k0.bps * 2u + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
-        c->k0.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / c->k0.bps); c->k0.lds = 0u;
+        k.on = true; k.resample = true; k.L = L; k.M = M; k.T = T;
+        k.tile = k0_pick_tile(L, M, T);
+        if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
+        k.lds = k0_lds_bytes(L, M, T, k.tile);
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u)) {
+        /* the native rate in another format or with a gain: the conversion kernel alone */
+        k.on = true; k.L = k.M = k.T = 1u;
+        k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
-    if (cfg->device < 0 || cfg->device >= WM_MAX_DEVICES) return bail(fail(c, WMBUS_EINVAL, "device must be 0..%d", WM_MAX_DEVICES - 1));
-    if (wmbus_device_count() <= cfg->device) return bail(fail(c, WMBUS_ENODEVICE, "no HIP device %d (this library has no CPU fallback)", cfg->device));
-    if (hipSetDevice(cfg->device) != hipSuccess) return bail(fail(c, WMBUS_EDEVICE, "hipSetDevice(%d) failed", cfg->device));
+    if (cfg->device < 0 || cfg->device >= WM_MAX_DEVICES) return fail(c, WMBUS_EINVAL, "device must be 0..%d", WM_MAX_DEVICES - 1);
+    if (wmbus_device_count() <= cfg->device) return fail(c, WMBUS_ENODEVICE, "no HIP device %d (this library has no CPU fallback)", cfg->device);
+    if (hipSetDevice(cfg->device) != hipSuccess) return fail(c, WMBUS_EDEVICE, "hipSetDevice(%d) failed", cfg->device);
+    return WMBUS_OK;
+}
 
+/* step 2: every size, count and switch of the context from its configuration -- arithmetic only, no HIP call */
+static int open_geometry(wmbus_ctx *c)
+{
+    const wmbus_cfg *cfg = &c->cfg;
+    Framer &rla = c->fr[WMBUS_ALGO_RLA], &clk = c->fr[WMBUS_ALGO_T2A];
     c->d = cfg->decimation; c->S = cfg->n_streams;
+    c->n_win = cfg->input_windows == 2 ? 2u : 1u;
+    /* the pipeline behind K0 is sized for what a full raw push resamples (converts) to, plus the remainder in front of it */
+    c->push_cap = cfg->max_push_bytes;
+    if (c->k0.on) {
+        const uint64_t most = ((uint64_t)(cfg->max_push_bytes / c->k0.bps) * c->k0.L + c->k0.M - 1u) / c->k0.M * 2u;
+        c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
+        c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
+    }
     /* Time segments: 32768 / 8192 decimated samples for batches of whole waves (r02 / r03 A/Bs: clock 65536 -8 %, 16384 -25 %;
      * run-length 16384 -9 %, 4096 -20 %).  A batch with fewer captures than a wave has lanes is bound by how long ONE lane
      * walks (5 us per 32 samples whatever runs beside it), not by the work: its segments shrink with the capture count, down
      * to 8192 / 2048 for a single capture (one 2^22-sample push of one capture: 29 -> 9 ms; the result does not depend on the
      * segmentation, test_result_independent_of_segmentation). */
-    {
-        uint32_t k = 1;
-        while (k < 8u && c->S * k < 64u) k *= 2u;          /* 1 for >= 64 captures ... 8 for fewer than 16 */
-        c->clk_form = cfg->clock_waves == 1u ? 1u : 4u;
-        if (c->clk_form != 4u)
-            c->C[1] = 32768u / std::min(k, 4u);            /* one capture, r04: 9.3 / 8.8 / 7.7 ms per configs[1] push with 4096 / 8192 / 16384, 9.5 / 9.0 / 10.5 for configs[2]: 8192 */
-        else
-            /* the systolic form walks a segment in 0.4 of the time (round 6, one capture of configs[1]: 5.6 / 4.9 / 4.25 / 5.8 ms per push with
-             * 8192 / 16384 / 32768 / 65536, against 7.6 with the one-wave form's 8192): 32768 whatever the batch size -- and 65536 where the
-             * demodulation kernel is the heavier side (exact arithmetic, 1.6 MS/s, no -s: the warm-ups of 12288 / 24576 samples are a quarter
-             * less work per sample; bench workload 181-187 against 174-181 Gsamples/s, tolerance mode 199 against 202, configs[2] 161 against 171) */
-            c->C[1] = c->S >= 64u && !cfg->tolerance_mode && cfg->decimation == 2u && !cfg->simultaneous ? 65536u : 32768u;
-        /* a live stream's pushes are short (the CLI's 1 MiB = 2^18 decimated samples at 1.6 MS/s): a push of two to eight 32768-sample
-         * segments is as long as its one lane with a full warm-up, 57 344 samples; with 16384 that lane is 40 960 (one capture, ms per push of
-         * 2^17 / 2^18 / 2^19 input samples: 5.1 / 4.6 / 3.9 -> 2.8 / 3.4 / 3.4; 2^22: 4.3 against 4.8, so long pushes keep 32768) */
-        {
-            const uint64_t mp = c->push_cap / 2u / std::max(1u, cfg->decimation);      /* a push's decimated samples at most */
-            if (c->clk_form == 4u && c->S < 64u && mp > 32768u && mp <= (1u << 19)) c->C[1] = 16384u;      /* <= 32768: one segment from its exact start */
-        }
-        if (cfg->seg_len) c->C[1] = cfg->seg_len;
-        /* run-length segments: 4096 (r04 A/B on the bench workload: 151.0 / 151.1 against 148.9 / 150.6 with round 3's 8192 and
-         * 136.3 / 134.1 with 2048); 2048 with -s, where S1 telegrams -- 30-100 ms, several segments long -- are expected in both
-         * chains and every segment inside one is re-run in a chain walk whose length is the telegram's whatever the segment
-         * length, while first pass and first list round scale with it (configs[2] batch: 92.8 / 110.3 / 133.3 Gsamples/s with
-         * 8192 / 4096 / 2048, 124.9 with 1024) */
-        c->C[0] = cfg->rla_seg_len ? cfg->rla_seg_len : std::max(2048u, (cfg->simultaneous ? 2048u : 4096u) / k);
-    }
-    for (int a = 0; a < 2; a++)
-        if (c->C[a] < 1024u || c->C[a] > (1u << 20) || (c->C[a] & (c->C[a] - 1)))
-            return bail(fail(c, WMBUS_EINVAL, "seg_len / rla_seg_len must be powers of two in [1024, 1048576]"));
+    uint32_t k = 1;
+    while (k < 8u && c->S * k < 64u) k *= 2u;              /* 1 for >= 64 captures ... 8 for fewer than 16 */
+    c->clk_form = cfg->clock_waves == 1u ? 1u : 4u;
+    if (c->clk_form != 4u)
+        clk.C = 32768u / std::min(k, 4u);              /* one capture, r04: 9.3 / 8.8 / 7.7 ms per configs[1] push with 4096 / 8192 / 16384, 9.5 / 9.0 / 10.5 for configs[2]: 8192 */
+    else
+        /* the systolic form walks a segment in 0.4 of the time (round 6, one capture of configs[1]: 5.6 / 4.9 / 4.25 / 5.8 ms per push with
+         * 8192 / 16384 / 32768 / 65536, against 7.6 with the one-wave form's 8192): 32768 whatever the batch size -- and 65536 where the
+         * demodulation kernel is the heavier side (exact arithmetic, 1.6 MS/s, no -s: the warm-ups of 12288 / 24576 samples are a quarter
+         * less work per sample; bench workload 181-187 against 174-181 Gsamples/s, tolerance mode 199 against 202, configs[2] 161 against 171) */
+        clk.C = c->S >= 64u && !cfg->tolerance_mode && cfg->decimation == 2u && !cfg->simultaneous ? 65536u : 32768u;
+    /* a live stream's pushes are short (the CLI's 1 MiB = 2^18 decimated samples at 1.6 MS/s): a push of two to eight 32768-sample
+     * segments is as long as its one lane with a full warm-up, 57 344 samples; with 16384 that lane is 40 960 (one capture, ms per push of
+     * 2^17 / 2^18 / 2^19 input samples: 5.1 / 4.6 / 3.9 -> 2.8 / 3.4 / 3.4; 2^22: 4.3 against 4.8, so long pushes keep 32768) */
+    const uint64_t mp = c->push_cap / 2u / std::max(1u, cfg->decimation);      /* a push's decimated samples at most */
+    if (c->clk_form == 4u && c->S < 64u && mp > 32768u && mp <= (1u << 19)) clk.C = 16384u;      /* <= 32768: one segment from its exact start */
+    if (cfg->seg_len) clk.C = cfg->seg_len;
+    /* run-length segments: 4096 (r04 A/B on the bench workload: 151.0 / 151.1 against 148.9 / 150.6 with round 3's 8192 and
+     * 136.3 / 134.1 with 2048); 2048 with -s, where S1 telegrams -- 30-100 ms, several segments long -- are expected in both
+     * chains and every segment inside one is re-run in a chain walk whose length is the telegram's whatever the segment
+     * length, while first pass and first list round scale with it (configs[2] batch: 92.8 / 110.3 / 133.3 Gsamples/s with
+     * 8192 / 4096 / 2048, 124.9 with 1024) */
+    rla.C = cfg->rla_seg_len ? cfg->rla_seg_len : std::max(2048u, (cfg->simultaneous ? 2048u : 4096u) / k);
+    for (const Framer &f : c->fr)
+        if (f.C < 1024u || f.C > (1u << 20) || (f.C & (f.C - 1)))
+            return fail(c, WMBUS_EINVAL, "seg_len / rla_seg_len must be powers of two in [1024, 1048576]");
     c->cfg.warmup_t1c1 = cfg->warmup_t1c1 ? (cfg->warmup_t1c1 + 31u) & ~31u : 12288u;   /* whole 32-sample blocks */
     c->cfg.warmup_s1 = cfg->warmup_s1 ? (cfg->warmup_s1 + 31u) & ~31u : 24576u;
     c->cfg.rla_lookback = cfg->rla_lookback ? (cfg->rla_lookback + 31u) & ~31u : 1024u;
@@ -551,102 +508,41 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
                (cfg->simultaneous ? WM_F_SHIFT : 0) | (cfg->accurate_atan ? WM_F_ACCURATE : 0) | (cfg->remove_dc ? WM_F_DC : 0) |
                (cfg->t1c1_enabled ? WM_F_T1C1 : 0) | (cfg->s1_enabled ? WM_F_S1 : 0) | (cfg->rla_enabled ? WM_F_RLA : 0) |
                (cfg->time2_enabled ? WM_F_T2A : 0);
-    if (c->S < 64u) { c->ema_rounds = 2; c->fr_rounds = 5; }
+    c->ema_rounds = c->S < 64u ? 2 : 1;
+    clk.sc = SC_CLK; clk.round0 = 0; clk.rounds = c->S < 64u ? 5 : 2;
     c->opt_rounds = !cfg->rounds_on_host;
     /* the run-length framer gets as many list rounds as the clock kernel (round 3: one fewer -- enough for 1.6 MS/s captures,
      * "2300 re-runs, then 0", but configs[2] (-d 5 -s) leaves 750 lanes after the first round and fell to the host-driven
-     * path on EVERY push: 64 ms per step instead of 25) */
-    c->rla_rounds = std::min<unsigned>(c->fr_rounds + 1u, WM_MAX_ROUNDS + 1u);
+     * path on EVERY push: 64 ms per step instead of 25); its counters start at index 1 (its list rounds: 1 .. rounds - 1) */
+    rla.sc = SC_RLA; rla.round0 = 1; rla.rounds = std::min<unsigned>(clk.rounds + 1u, WM_MAX_ROUNDS + 1u);
     /* ... and one more with -s: S1 telegrams (30-100 ms) lie in BOTH chains' bands there, a telegram is a chain of twenty to forty
      * run-length segments that only a walk from its first one settles, and two list rounds left a remainder in every tenth push of
      * configs[2] (round 5: rla_round = 10 994, 5 088, then the host-driven path; an empty round costs 0.2 ms) */
-    if (cfg->simultaneous) c->rla_rounds = std::min<unsigned>(c->rla_rounds + 1u, WM_MAX_ROUNDS + 1u);
+    if (cfg->simultaneous) rla.rounds = std::min<unsigned>(rla.rounds + 1u, WM_MAX_ROUNDS + 1u);
     c->T = (uint32_t)WM_K1_TILE2;
-    const uint32_t T = c->T;
-    const uint64_t max_samples = c->push_cap / 2;
-    c->ntiles_cap = (uint32_t)((max_samples / c->d + 1 + 8 + T - 1) / T);
-    c->Mcap = (c->ntiles_cap * T + 255) / 256 * 256;     /* whole tiles (partial tiles still store full runs); slicer-word rows 32-byte aligned */
-    for (int a = 0; a < 2; a++) c->nseg_cap[a] = (c->Mcap + c->C[a] - 1) / c->C[a];
-    c->cap[1] = c->C[1] / 4 + 8;   /* time2: the lock logic needs >= 4 samples per chip */
+    c->ntiles_cap = (uint32_t)((c->push_cap / 2 / c->d + 1 + 8 + c->T - 1) / c->T);
+    c->Mcap = (c->ntiles_cap * c->T + 255) / 256 * 256;     /* whole tiles (partial tiles still store full runs); slicer-word rows 32-byte aligned */
+    for (Framer &f : c->fr) f.nseg_cap = (c->Mcap + f.C - 1) / f.C;
+    rla.state_bytes = sizeof(WmRlaState); clk.state_bytes = sizeof(WmClkState);
+    clk.cap = clk.C / 4 + 8;       /* time2: the lock logic needs >= 4 samples per chip */
     /* run-length: a primary region of half a chip per sample (four times the nominal eight samples per chip); the
      * reference's bit-length tracker has no floor -- switch combinations (-d 3 -s -o -a on a capture with both modes)
      * and interferers drag it to a third of a sample per chip for a while (3.1 chips per sample seen, found by the host
      * emulation campaigns), and exact silence ends in one long run -- such segments continue in the spill arena
      * (WmSpill, wm_dev.h); a push never fails for want of chip storage */
-    c->cap[0] = (c->C[0] / 2 + 8 + 7) / 8 * 8;
+    rla.cap = (rla.C / 2 + 8 + 7) / 8 * 8;
     /* K1 stages whole tiles: the partial last tile of a push reads up to (tile + halo) x d input samples past the
      * staged bytes (never used: they only feed outputs beyond M) -- the row must hold them */
     c->in_stride = (WM_HIST_BYTES + c->push_cap + 2ull * (WM_K1_TILE2 + WM_K1_HALO + 16) * WM_MAX_DECIM + WM_IN_SLACK + 255) / 256 * 256;
-
-    const uint64_t rows = 2ull * c->S;
-    hipError_t e = hipSuccess;
-    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    A(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    c->n_win = cfg->input_windows == 2 ? 2u : 1u;
-    /* the side stream for wmbus_stage's copies exists where it can overlap something: with two input windows.  (Every
-     * stream takes a hardware queue -- ROCm maps streams onto GPU_MAX_HW_QUEUES of them round robin -- and two contexts'
-     * compute streams that end up on one queue serialise: an idle copy stream per context halved the 8-context rate.) */
-    if (c->n_win == 2) A(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); else c->copy_stream = c->stream;
-    for (auto &ev : c->ev) A(hipEventCreate(&ev));
-    A(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&c->ev_turn, hipEventDisableTiming));
-    A(dalloc(&c->d_in, (size_t)c->in_stride * c->S * c->n_win));
-    A(dalloc(&c->d_hist, (size_t)WM_HIST_BYTES * c->S));
-    if (c->k0.on) {
-        A(dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->S * c->n_win));
-        if (c->k0.resample) {
-            A(dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
-            A(dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
-        }
-        A(dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
-    }
-    A(dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
-    A(dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
-    A(dalloc(&c->d_bits, (size_t)rows * (c->Mcap / 32)));
-    A(dalloc(&c->d_lut, (size_t)2 * 32 * WM_MAX_DECIM));
-    A(dalloc(&c->d_ema_head, (size_t)rows * c->ntiles_cap));
-    A(dalloc(&c->d_ema_tail, (size_t)rows * c->ntiles_cap));
-    A(dalloc(&c->d_ema_carry, (size_t)2 * rows));
-    A(dalloc(&c->d_first_bad, (size_t)rows));
-    {
-        const uint32_t need = WM_F_ACCURATE | WM_F_T1C1 | WM_F_S1, never = WM_F_APPROX1 | WM_F_APPROX2;
-        c->rs_od = !cfg->rssi_full && !cfg->keep_taps && cfg->prefilter != WMBUS_PREFILTER_POLYPHASE && c->d >= 2 && c->d <= 5 &&
-                   (c->flags & need) == need && !(c->flags & never);
-        /* the larger tile of the first pass: decimation 2 without -s (the LDS of a 512-thread block at d >= 3 or with the -s staging
-         * would cost more occupancy than the halo saves) */
-        c->k1_big = c->rs_od && c->d == 2 && !(c->flags & WM_F_SHIFT) && !cfg->k1_small_tile;
-        c->k1_tail_pm = cfg->tolerance_mode ? 0u : 60u;
-        c->k1_tpb = cfg->k1_tiles_per_block ? std::min(cfg->k1_tiles_per_block, 64u) : WM_K1_TPB_DEFAULT;
-        c->clk_form = cfg->clock_waves == 1u ? 1u : 4u;
-        if (c->rs_od) { A(dalloc(&c->d_rs_flags, (size_t)c->ntiles_cap * c->S)); A(dalloc(&c->d_rs_list, (size_t)c->ntiles_cap * c->S)); }
-    }
-    const size_t stw[2] = {sizeof(WmRlaState), sizeof(WmClkState)};
-    for (int a = 0; a < 2; a++) {
-        A(dalloc(&c->d_chips[a], (size_t)rows * c->nseg_cap[a] * c->cap[a]));
-        A(dalloc(&c->d_counts[a], (size_t)rows * c->nseg_cap[a]));
-        A(hipMalloc(&c->d_st_start[a], (size_t)rows * c->nseg_cap[a] * stw[a]));
-        A(hipMalloc(&c->d_st_final[a], (size_t)rows * c->nseg_cap[a] * stw[a]));
-        A(hipMalloc(&c->d_st_carry[a], (size_t)2 * rows * stw[a]));
-    }
-    {
-        const uint64_t dec_total_ = (uint64_t)c->S * c->Mcap;
-        const uint64_t want = cfg->spill_words ? cfg->spill_words : std::max<uint64_t>(1u << 20, dec_total_ / 16);
-        c->spill_words = (uint32_t)std::min<uint64_t>((want + WM_SPILL_CHUNK - 1) / WM_SPILL_CHUNK * WM_SPILL_CHUNK, 0xFFFF0000u);
-        A(dalloc(&c->d_spill, (size_t)c->spill_words));
-        A(dalloc(&c->d_chain, (size_t)rows * c->nseg_cap[0] * WM_SPILL_LEVELS));
-    }
-    A(dalloc(&c->d_list, (size_t)rows * std::max(c->nseg_cap[0], c->nseg_cap[1])));
-    A(dalloc(&c->d_list2, (size_t)rows * c->nseg_cap[0]));
-    A(dalloc(&c->d_list_ema, (size_t)rows));
-    c->nck = c->C[1] / WM_CK_SAMPLES ? c->C[1] / WM_CK_SAMPLES - 1 : 0;
-    A(dalloc(&c->d_ckpt, std::max<size_t>(16, (size_t)rows * c->nseg_cap[1] * c->nck * 16)));
-    {
-        const size_t n_seen0 = (size_t)rows * c->nseg_cap[0], n_seen1 = (size_t)rows * c->nseg_cap[1], n_chain = (size_t)rows * c->nseg_cap[0] + 1;
-        c->zero_words = SC_COUNT + n_seen0 + n_seen1 + n_chain;
-        A(dalloc(&c->d_scalars, c->zero_words));
-        c->d_sync_seen[0] = c->d_scalars + SC_COUNT; c->d_sync_seen[1] = c->d_sync_seen[0] + n_seen0; c->d_nchain = c->d_sync_seen[1] + n_seen1;
-    }
-    const uint64_t dec_total = (uint64_t)c->S * c->Mcap;
+    c->rs_od = !cfg->rssi_full && !cfg->keep_taps && cfg->prefilter != WMBUS_PREFILTER_POLYPHASE && c->d >= 2 && c->d <= 5 && default_switches(c->flags);
+    /* the larger tile of the first pass: decimation 2 without -s (the LDS of a 512-thread block at d >= 3 or with the -s staging
+     * would cost more occupancy than the halo saves) */
+    c->k1_big = c->rs_od && c->d == 2 && !(c->flags & WM_F_SHIFT) && !cfg->k1_small_tile;
+    c->k1_tail_pm = cfg->tolerance_mode ? 0u : 60u;
+    c->k1_tpb = cfg->k1_tiles_per_block ? std::min(cfg->k1_tiles_per_block, 64u) : WM_K1_TPB_DEFAULT;
+    const uint64_t dec_total = (uint64_t)c->S * c->Mcap, want = cfg->spill_words ? cfg->spill_words : std::max<uint64_t>(1u << 20, dec_total / 16);
+    c->spill_words = (uint32_t)std::min<uint64_t>((want + WM_SPILL_CHUNK - 1) / WM_SPILL_CHUNK * WM_SPILL_CHUNK, 0xFFFF0000u);
+    c->nck = clk.C / WM_CK_SAMPLES ? clk.C / WM_CK_SAMPLES - 1 : 0;
     c->hdr_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(65536, dec_total / 1024), 1u << 24);
     c->hits_cap = c->hdr_cap;
     /* bursts that still travel as chips are the ones whose plan reaches past the end of the push (every such hit is
@@ -661,76 +557,142 @@ int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
     if (cfg->burst_caps[1]) c->words_cap = cfg->burst_caps[1];
     if (cfg->burst_caps[2]) c->pkts_cap = cfg->burst_caps[2];
     if (cfg->burst_caps[3]) c->bytes_cap = cfg->burst_caps[3];
-    A(dalloc(&c->d_hits, (size_t)c->hits_cap));
-    if (c->rs_od) A(dalloc(&c->d_plans, (size_t)4 * c->S + c->hits_cap));
-    A(dalloc(&c->d_pending, (size_t)4 * c->S));
+    return WMBUS_OK;
+}
+
+/* step 3: streams, events, the demodulation kernels and every buffer (recorded in c->mem: wmbus_close frees them) */
+static int open_allocate(wmbus_ctx *c)
+{
+    Owned &m = c->mem;
+    const uint64_t rows = 2ull * c->S;
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    A(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    /* the side stream for wmbus_stage's copies exists where it can overlap something: with two input windows.  (Every
+     * stream takes a hardware queue -- ROCm maps streams onto GPU_MAX_HW_QUEUES of them round robin -- and two contexts'
+     * compute streams that end up on one queue serialise: an idle copy stream per context halved the 8-context rate.) */
+    if (c->n_win == 2) A(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); else c->copy_stream = c->stream;
+    for (auto &ev : c->ev) A(hipEventCreate(&ev));
+    A(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
+    A(hipEventCreateWithFlags(&c->ev_turn, hipEventDisableTiming));
+    A(m.dalloc(&c->d_in, (size_t)c->in_stride * c->S * c->n_win));
+    A(m.dalloc(&c->d_hist, (size_t)WM_HIST_BYTES * c->S));
+    if (c->k0.on) {
+        A(m.dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->S * c->n_win));
+        if (c->k0.resample) {
+            A(m.dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
+            A(m.dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
+        }
+        A(m.dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
+    }
+    A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
+    A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
+    A(m.dalloc(&c->d_bits, (size_t)rows * (c->Mcap / 32)));
+    A(m.dalloc(&c->d_lut, (size_t)2 * 32 * WM_MAX_DECIM));
+    A(m.dalloc(&c->d_ema_head, (size_t)rows * c->ntiles_cap));
+    A(m.dalloc(&c->d_ema_tail, (size_t)rows * c->ntiles_cap));
+    A(m.dalloc(&c->d_ema_carry, (size_t)2 * rows));
+    A(m.dalloc(&c->d_first_bad, (size_t)rows));
+    A(m.dalloc(&c->d_list_ema, (size_t)rows));
+    if (c->rs_od) {
+        A(m.dalloc(&c->d_rs_flags, (size_t)c->ntiles_cap * c->S));
+        A(m.dalloc(&c->d_rs_list, (size_t)c->ntiles_cap * c->S));
+        A(m.dalloc(&c->d_plans, (size_t)4 * c->S + c->hits_cap));
+    }
+    size_t n_seen = 0;
+    for (Framer &f : c->fr) {
+        const size_t segs = (size_t)rows * f.nseg_cap;
+        A(m.dalloc(&f.d_chips, segs * f.cap));
+        A(m.dalloc(&f.d_counts, segs));
+        A(m.dbytes(&f.d_st_start, segs * f.state_bytes));
+        A(m.dbytes(&f.d_st_final, segs * f.state_bytes));
+        A(m.dbytes(&f.d_st_carry, (size_t)2 * rows * f.state_bytes));
+        A(m.dalloc(&f.d_list, (size_t)rows * (&f == &c->fr[WMBUS_ALGO_T2A] ? std::max(c->fr[0].nseg_cap, c->fr[1].nseg_cap) : f.nseg_cap)));
+        A(m.dalloc(&f.d_bad, segs));
+        n_seen += segs;
+    }
+    A(m.dalloc(&c->d_spill, (size_t)c->spill_words));
+    A(m.dalloc(&c->d_chain, (size_t)rows * c->fr[0].nseg_cap * WM_SPILL_LEVELS));
+    A(m.dalloc(&c->d_ckpt, std::max<size_t>(16, (size_t)rows * c->fr[1].nseg_cap * c->nck * 16)));
+    c->zero_words = SC_COUNT + n_seen + (size_t)rows * c->fr[0].nseg_cap + 1;      /* scalars | sync_seen[0] | sync_seen[1] | nchain + bump counter */
+    A(m.dalloc(&c->d_scalars, c->zero_words));
+    c->fr[0].d_sync_seen = c->d_scalars + SC_COUNT;
+    c->fr[1].d_sync_seen = c->fr[0].d_sync_seen + (size_t)rows * c->fr[0].nseg_cap;
+    c->d_nchain = c->fr[1].d_sync_seen + (size_t)rows * c->fr[1].nseg_cap;
+    A(m.dalloc(&c->d_hits, (size_t)c->hits_cap));
+    A(m.dalloc(&c->d_pending, (size_t)4 * c->S));
+    A(m.halloc(&c->h_scalars, SC_COUNT));
+    A(m.halloc(&c->h_hdr, (size_t)c->hdr_cap));
+    A(m.halloc(&c->h_words, (size_t)c->words_cap));
+    A(m.halloc(&c->h_pkts, (size_t)c->pkts_cap));
+    A(m.halloc(&c->h_bytes, (size_t)c->bytes_cap));
+    A(m.halloc(&c->h_pending, (size_t)4 * c->S));
+    if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_hdr, c->h_hdr, 0)); A(hipHostGetDevicePointer(&c->dv_words, c->h_words, 0)); }
+    if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_pkts, c->h_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_bytes, c->h_bytes, 0)); }
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e));
+    return k1_resolve(c);
+}
+
+/* step 4: the state a fresh context carries into its first push = the reference's zero-initialised statics */
+static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
+{
+    const uint64_t rows = 2ull * c->S;
+    hipError_t e = hipSuccess;
+    auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     /* the verifiers' verdict per segment, for the chain walk of the re-run lanes (K2Args.bad).  Zeroed on the context's own stream: a
      * synchronous hipMemset runs on the NULL stream, whose hardware queue then takes part in the round-robin of streams onto
      * queues -- eight contexts lost 5 % to that in round 4's A/Bs. */
-    A(dalloc(&c->d_bad, (size_t)rows * c->nseg_cap[0]));
-    if (e == hipSuccess) A(hipMemsetAsync(c->d_bad, 0, (size_t)rows * c->nseg_cap[0] * sizeof(uint32_t), c->stream));
-    A(dalloc(&c->d_bad_clk, (size_t)rows * c->nseg_cap[1]));
-    if (e == hipSuccess) A(hipMemsetAsync(c->d_bad_clk, 0, (size_t)rows * c->nseg_cap[1] * sizeof(uint32_t), c->stream));
-    A(hipHostMalloc((void **)&c->h_scalars, SC_COUNT * sizeof(uint32_t)));
-    A(hipHostMalloc((void **)&c->h_hdr, (size_t)c->hdr_cap * sizeof(WmBurstHdr)));
-    A(hipHostMalloc((void **)&c->h_words, (size_t)c->words_cap * sizeof(uint32_t)));
-    A(hipHostMalloc((void **)&c->h_pkts, (size_t)c->pkts_cap * sizeof(WmPkt)));
-    A(hipHostMalloc((void **)&c->h_bytes, (size_t)c->bytes_cap));
-    A(hipHostMalloc((void **)&c->h_pending, (size_t)4 * c->S * sizeof(uint32_t)));
-    if (e == hipSuccess) {
-        A(hipHostGetDevicePointer(&c->dv_hdr, c->h_hdr, 0)); A(hipHostGetDevicePointer(&c->dv_words, c->h_words, 0));
-        A(hipHostGetDevicePointer(&c->dv_pkts, c->h_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_bytes, c->h_bytes, 0));
-    }
-    if (e != hipSuccess) return bail(fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e)));
-
+    for (Framer &f : c->fr) A(hipMemsetAsync(f.d_bad, 0, (size_t)rows * f.nseg_cap * sizeof(uint32_t), c->stream));
     if (c->k0.on) A(hipMemsetAsync(c->k0.d_rem, 128, (size_t)2 * c->S * WMBUS_BLOCK_BYTES, c->stream));
     if (c->k0.resample) {                                    /* history before a stream's first sample: x = 0 */
         A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
         A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-        A(hipStreamSynchronize(c->stream));                  /* k0_taps leaves with this function */
     }
-    /* initial state = the reference's zero-initialised statics */
     A(hipMemsetAsync(c->d_ema_carry, 0, 2 * rows * sizeof(float), c->stream));
     /* a disabled chain (-p T / -p S) never writes its hand-off records: they must compare equal, not hold what an
      * earlier context left in the recycled allocation */
     A(hipMemsetAsync(c->d_ema_head, 0, (size_t)rows * c->ntiles_cap * sizeof(float), c->stream));
     A(hipMemsetAsync(c->d_ema_tail, 0, (size_t)rows * c->ntiles_cap * sizeof(float), c->stream));
     A(hipMemsetAsync(c->d_first_bad, 0xFF, rows * sizeof(uint32_t), c->stream));
-    A(hipMemsetAsync(c->d_st_carry[1], 0, 2 * rows * sizeof(WmClkState), c->stream));
-    {
-        std::vector<WmRlaState> init(2 * rows, WmRlaState{0, 8 * 256, 0, 0u, 0u, 0u, 24, 24});   /* rtl_wmbus.c:628-637,717-726 */
-        A(hipMemcpyAsync(c->d_st_carry[0], init.data(), 2 * rows * sizeof(WmRlaState), hipMemcpyHostToDevice, c->stream));
-        A(hipStreamSynchronize(c->stream));
-    }
+    A(hipMemsetAsync(c->fr[WMBUS_ALGO_T2A].d_st_carry, 0, 2 * rows * sizeof(WmClkState), c->stream));
+    const std::vector<WmRlaState> init(2 * rows, WmRlaState{0, 8 * 256, 0, 0u, 0u, 0u, 24, 24});   /* rtl_wmbus.c:628-637,717-726 */
+    A(hipMemcpyAsync(c->fr[WMBUS_ALGO_RLA].d_st_carry, init.data(), 2 * rows * sizeof(WmRlaState), hipMemcpyHostToDevice, c->stream));
     A(hipMemsetAsync(c->d_scalars, 0, c->zero_words * sizeof(uint32_t), c->stream));
     A(hipMemsetAsync(c->d_pending, 0, 4 * c->S * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_fill, dim3(c->S * c->n_win), dim3(256), 0, c->stream, c->d_in, c->in_stride, (uint32_t)c->in_stride, (uint8_t)128);
     hipLaunchKernelGGL(k_fill, dim3(c->S), dim3(256), 0, c->stream, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint32_t)WM_HIST_BYTES, (uint8_t)128);
     /* frequency-translation LUT, built with the host libm exactly like rtl_wmbus.c:974-993 */
-    {
-        const int fs_khz = (int)c->d * 800;
-        const size_t n_max = (size_t)(fs_khz / 25);
-        std::vector<float> lut(2 * 32 * WM_MAX_DECIM, 0.f);
-        for (size_t n = 0; n < n_max; n++) {
-            const double phi = (2. * M_PI * (25 * (double)n)) / fs_khz;
-            lut[n] = cosf(phi);
-            lut[32 * WM_MAX_DECIM + n] = -sinf(phi);
-        }
-        A(hipMemcpyAsync(c->d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        A(hipStreamSynchronize(c->stream));
+    const int fs_khz = (int)c->d * 800;
+    std::vector<float> lut(2 * 32 * WM_MAX_DECIM, 0.f);
+    for (size_t n = 0; n < (size_t)(fs_khz / 25); n++) {
+        const double phi = (2. * M_PI * (25 * (double)n)) / fs_khz;
+        lut[n] = cosf(phi);
+        lut[32 * WM_MAX_DECIM + n] = -sinf(phi);
     }
-    if (e != hipSuccess) return bail(fail(c, WMBUS_EDEVICE, "initialisation failed: %s", hipGetErrorString(e)));
+    A(hipMemcpyAsync(c->d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    A(hipStreamSynchronize(c->stream));                      /* k0_taps, init and lut leave with this function */
+    if (e != hipSuccess) return fail(c, WMBUS_EDEVICE, "initialisation failed: %s", hipGetErrorString(e));
 
-    c->decs.resize((size_t)c->S * 4);
-    for (uint32_t s = 0; s < c->S; s++)
-        for (int ch = 0; ch < 2; ch++)
-            for (int al = 0; al < 2; al++) {
-                HostDecoder &hd = c->decs[((size_t)s * 2 + ch) * 2 + al];
-                wm_decoder_init(&hd.dec, ch ? WM_MODE_S1 : WM_MODE_T1C1);
-                hd.owed = 0; hd.fed = 0;
-            }
-    *out = c;
+    c->decs.resize((size_t)c->S * 4);                        /* [stream][chain][algo] */
+    for (size_t i = 0; i < c->decs.size(); i++) {
+        wm_decoder_init(&c->decs[i].dec, (i >> 1) & 1u ? WM_MODE_S1 : WM_MODE_T1C1);
+        c->decs[i].owed = 0; c->decs[i].fed = 0;
+    }
     return WMBUS_OK;
+}
+
+int wmbus_open(const wmbus_cfg *cfg, wmbus_ctx **out)
+{
+    if (!cfg || !out) return WMBUS_EINVAL;
+    wmbus_ctx *c = new wmbus_ctx();
+    c->cfg = *cfg;
+    *out = c;                                                /* after a refusal the caller reads the message, then closes */
+    std::vector<int16_t> k0_taps;
+    int rc = open_validate(c, k0_taps);
+    if (!rc) rc = open_geometry(c);
+    if (!rc) rc = open_allocate(c);
+    if (!rc) rc = open_init(c, k0_taps);
+    return rc;
 }
 
 void *wmbus_alloc_pinned(size_t nbytes)
@@ -741,15 +703,24 @@ void *wmbus_alloc_pinned(size_t nbytes)
 
 void wmbus_free_pinned(void *p) { if (p) hipHostFree(p); }
 
+/* what wmbus_stage and wm_stage_all ask of a copy of `nbytes` per stream, of which the caller holds `room` */
+static int stage_check(wmbus_ctx *c, size_t nbytes, size_t room)
+{
+    if (nbytes > c->cfg.max_push_bytes || nbytes % WMBUS_BLOCK_BYTES || room < nbytes) return fail(c, WMBUS_EINVAL, "stage: nbytes must be a multiple of 4096 and <= max_push_bytes");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    /* with one input window the kernels of a push in flight still read it; with two (cfg.input_windows = 2) the next
+     * push is staged into the other one while they run */
+    if (c->in_flight && c->n_win == 1) return fail(c, WMBUS_EINVAL, "stage: a push is in flight and the context has one input window (cfg.input_windows = 2 overlaps them)");
+    return WMBUS_OK;
+}
+
 /* Every stream's bytes of the next push in ONE copy (the batch's host-sourced path: a context's streams lie `pitch` apart in
  * its page-locked slab and in_stride apart in HBM -- a pitched copy; 128 copies of 1-2 MiB per context-push were 1024
  * copy commands per step of the batch CLI).  Same rules as wmbus_stage. */
 static int wm_stage_all(wmbus_ctx *c, const uint8_t *slab, size_t pitch, size_t nbytes)
 {
     if (!c || !slab) return WMBUS_EINVAL;
-    if (nbytes > c->cfg.max_push_bytes || nbytes % WMBUS_BLOCK_BYTES || pitch < nbytes) return fail(c, WMBUS_EINVAL, "stage: nbytes must be a multiple of 4096 and <= max_push_bytes");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->in_flight && c->n_win == 1) return fail(c, WMBUS_EINVAL, "stage: a push is in flight and the context has one input window (cfg.input_windows = 2 overlaps them)");
+    if (const int rc = stage_check(c, nbytes, pitch)) return rc;
     HIPCHK(c, hipMemcpy2DAsync(wmbus_device_input(c, 0), c->k0.on ? c->k0.raw_stride : c->in_stride, slab, pitch, nbytes, c->S, hipMemcpyHostToDevice, c->copy_stream));
     return WMBUS_OK;
 }
@@ -764,11 +735,7 @@ void *wmbus_device_input(wmbus_ctx *c, unsigned stream)
 int wmbus_stage(wmbus_ctx *c, unsigned stream, const uint8_t *cu8, size_t nbytes)
 {
     if (!c || stream >= c->S || !cu8) return WMBUS_EINVAL;
-    if (nbytes > c->cfg.max_push_bytes || nbytes % WMBUS_BLOCK_BYTES) return fail(c, WMBUS_EINVAL, "stage: nbytes must be a multiple of 4096 and <= max_push_bytes");
-    /* with one input window the kernels of a push in flight still read it; with two (cfg.input_windows = 2) the next
-     * push is staged into the other one while they run */
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (c->in_flight && c->n_win == 1) return fail(c, WMBUS_EINVAL, "stage: a push is in flight and the context has one input window (cfg.input_windows = 2 overlaps them)");
+    if (const int rc = stage_check(c, nbytes, nbytes)) return rc;
     HIPCHK(c, hipMemcpyAsync(wmbus_device_input(c, stream), cu8, nbytes, hipMemcpyHostToDevice, c->copy_stream));
     return WMBUS_OK;
 }
@@ -777,20 +744,8 @@ int wmbus_stage(wmbus_ctx *c, unsigned stream, const uint8_t *cu8, size_t nbytes
 static float *ema_carry(wmbus_ctx *c, bool out) { return c->d_ema_carry + (size_t)(c->carry_in ^ (out ? 1u : 0u)) * 2 * c->S; }
 static void *st_carry(wmbus_ctx *c, int algo, bool out)
 {
-    const size_t w = algo == WMBUS_ALGO_RLA ? sizeof(WmRlaState) : sizeof(WmClkState);
-    return (char *)c->d_st_carry[algo] + (size_t)(c->carry_in ^ (out ? 1u : 0u)) * 2 * c->S * w;
-}
-
-static int launch_k1_any(wmbus_ctx *c, const K1Args &k1, dim3 grid, hipStream_t st = nullptr, int rs = 0, bool big = false)    /* rs: 0 everything, 1 no RSSI, 2 RSSI of the listed tiles; big: grid.x counts 2000-sample tiles (rs = 1 only) */
-{
-    const bool sh = c->flags & WM_F_SHIFT;
-    if (!st) st = c->stream;
-    if (c->cfg.prefilter == WMBUS_PREFILTER_POLYPHASE) return launch_k1_ppf(c, k1, grid, st);
-    if (c->d == 2) return sh ? launch_k1v2<2, true>(c, k1, grid, st, rs, false) : launch_k1v2<2, false>(c, k1, grid, st, rs, big);
-    if (c->d == 3) return sh ? launch_k1v2<3, true>(c, k1, grid, st, rs, false) : launch_k1v2<3, false>(c, k1, grid, st, rs, false);
-    if (c->d == 4) return sh ? launch_k1v2<4, true>(c, k1, grid, st, rs, false) : launch_k1v2<4, false>(c, k1, grid, st, rs, false);
-    if (c->d == 5) return sh ? launch_k1v2<5, true>(c, k1, grid, st, rs, false) : launch_k1v2<5, false>(c, k1, grid, st, rs, false);
-    return sh ? launch_k1v2<0, true>(c, k1, grid, st, rs, false) : launch_k1v2<0, false>(c, k1, grid, st, rs, false);      /* any other rate */
+    const Framer &f = c->fr[algo];
+    return (char *)f.d_st_carry + (size_t)(c->carry_in ^ (out ? 1u : 0u)) * 2 * c->S * f.state_bytes;
 }
 
 /* EMA hand-offs between tiles (k1_verify), the first uncertified tile of every row into the repair list (k1_collect),
@@ -807,7 +762,7 @@ static int ema_repair(wmbus_ctx *c, uint32_t cnt)          /* list launch: a fix
 {
     K1Args k1 = c->k1a;
     k1.relist = c->d_list_ema; k1.n_relist = c->d_scalars + cnt;
-    return launch_k1_any(c, k1, dim3(16, 1));
+    return launch_k1(c, K1_REPAIR, k1, dim3(16, 1));
 }
 
 static void ema_commit(wmbus_ctx *c)
@@ -819,28 +774,26 @@ static void ema_commit(wmbus_ctx *c)
  * The framers' FIRST list round is the parallel one -- except the run-length framer's with -s (fr_launch has the measurements). */
 static bool list_walks_chains(const wmbus_ctx *c, int algo, uint32_t cnt)
 {
-    if (algo == WMBUS_ALGO_RLA) return c->rla_chains && (c->cfg.simultaneous || cnt != SC_RLA + 1u);
-    return cnt != (uint32_t)SC_CLK;
+    return cnt != c->fr[algo].sc + c->fr[algo].round0 || (algo == WMBUS_ALGO_RLA && c->cfg.simultaneous);
 }
 
-static void fr_verify(wmbus_ctx *c, int algo, uint32_t cnt, hipStream_t st = nullptr)
+static void fr_verify(wmbus_ctx *c, int algo, uint32_t cnt)
 {
-    if (!st) st = c->stream;
-    const K2Args &a = algo == WMBUS_ALGO_RLA ? c->k2rla : c->k2clk;
-    const uint32_t lanes = 2u * a.g.nseg[algo] * a.g.S, words = (algo == WMBUS_ALGO_RLA ? sizeof(WmRlaState) : sizeof(WmClkState)) / 4;
-    hipLaunchKernelGGL(k2_verify, dim3((lanes + 255) / 256), dim3(256), 0, st, a.g, (uint32_t)algo, (const uint32_t *)a.st_start,
-                       (const uint32_t *)a.st_final, words, algo == WMBUS_ALGO_RLA ? c->d_list2 : c->d_list, c->d_scalars + cnt,
-                       algo == WMBUS_ALGO_RLA ? (c->rla_chains ? c->d_bad : (uint32_t *)nullptr) : c->d_bad_clk, list_walks_chains(c, algo, cnt) ? 1u : 0u);
+    const Framer &f = c->fr[algo];
+    const K2Args &a = f.k2;
+    const uint32_t lanes = 2u * a.g.nseg[algo] * a.g.S;
+    hipLaunchKernelGGL(k2_verify, dim3((lanes + 255) / 256), dim3(256), 0, c->stream, a.g, (uint32_t)algo, (const uint32_t *)a.st_start,
+                       (const uint32_t *)a.st_final, f.state_bytes / 4u, f.d_list, c->d_scalars + cnt, f.d_bad, list_walks_chains(c, algo, cnt) ? 1u : 0u);
 }
 
 /* one framer's kernel alone: every lane (cnt == ~0) or the re-run list whose length is scalar `cnt` */
-static void fr_launch(wmbus_ctx *c, int algo, uint32_t cnt, hipStream_t st = nullptr)
+static void fr_launch(wmbus_ctx *c, int algo, uint32_t cnt)
 {
-    if (!st) st = c->stream;
-    K2Args a = algo == WMBUS_ALGO_RLA ? c->k2rla : c->k2clk;
+    const hipStream_t st = c->stream;
+    K2Args a = c->fr[algo].k2;
     const uint32_t lanes = 2u * a.g.nseg[algo] * a.g.S;
     const bool all = cnt == 0xFFFFFFFFu;
-    a.list = all ? nullptr : (algo == WMBUS_ALGO_RLA ? c->d_list2 : c->d_list);
+    a.list = all ? nullptr : c->fr[algo].d_list;
     a.n_lanes = lanes; a.n_ptr = all ? nullptr : c->d_scalars + cnt;
     /* The run-length framer's FIRST list round re-runs every listed segment on its own, in parallel, from its predecessor's
      * end state as recorded: a neighbour that is listed too usually comes out of its re-run with the end state it had (the
@@ -862,42 +815,30 @@ static void fr_launch(wmbus_ctx *c, int algo, uint32_t cnt, hipStream_t st = nul
 #ifdef WM_DBG_SKIP_RLA
     if (algo == WMBUS_ALGO_RLA && c->push_seq > 3) return;
 #endif
-    if (algo == WMBUS_ALGO_T2A && c->clk_form == 4u) {
-        /* the systolic form: a block of four waves per 64 lanes (wm_k2_clock_sys.h); list launches as below: blocks for 3/16 of the lanes */
-        const uint32_t grid = all ? (lanes + 63u) / 64u : std::max(64u, (lanes / 64u) * 3u / 16u);
-        if (all) {
-            const bool dc = c->flags & WM_F_DC, coop = a.g.S % 64u == 0u;        /* whole waves of captures load cooperatively */
-            if (dc && coop) hipLaunchKernelGGL((k2_clock_sys<true, true>), dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-            else if (dc) hipLaunchKernelGGL((k2_clock_sys<true, false>), dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-            else if (coop) hipLaunchKernelGGL((k2_clock_sys<false, true>), dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-            else hipLaunchKernelGGL((k2_clock_sys<false, false>), dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-        } else if (c->flags & WM_F_DC) hipLaunchKernelGGL(k2_clock_sys_list<true>, dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-        else hipLaunchKernelGGL(k2_clock_sys_list<false>, dim3(grid), dim3(256), sizeof(ClkSysLds), st, a);
-        return;
-    }
-    const uint32_t B = 64 * (algo == WMBUS_ALGO_RLA ? WM_RLA_WPB : WM_CLK_WPB), grid = all ? (lanes + B - 1) / B : std::max(16u, (lanes / B) * 3u / 16u);
-    if (algo == WMBUS_ALGO_RLA) {
-        if (all) hipLaunchKernelGGL(k2_rla, dim3(grid), dim3(B), 0, st, a);
-        else hipLaunchKernelGGL(k2_rla_list, dim3(grid), dim3(B), 0, st, a);
-    }
-    else if (all) {
-        if (c->flags & WM_F_DC) hipLaunchKernelGGL(k2_clock<true>, dim3(grid), dim3(B), 0, st, a);
-        else hipLaunchKernelGGL(k2_clock<false>, dim3(grid), dim3(B), 0, st, a);
-    } else if (c->flags & WM_F_DC) hipLaunchKernelGGL(k2_clock_list<true>, dim3(grid), dim3(B), 0, st, a);
-    else hipLaunchKernelGGL(k2_clock_list<false>, dim3(grid), dim3(B), 0, st, a);
+    /* the systolic form of the clock kernel: a block of four waves per 64 lanes (wm_k2_clock_sys.h); the others: a lane per thread */
+    const bool sys = algo == WMBUS_ALGO_T2A && c->clk_form == 4u, dc = c->flags & WM_F_DC, coop = a.g.S % 64u == 0u;      /* coop: whole waves of captures load cooperatively */
+    void (*k)(K2Args);
+    if (algo == WMBUS_ALGO_RLA) k = all ? k2_rla : k2_rla_list;
+    else if (!sys) k = all ? (dc ? k2_clock<true> : k2_clock<false>) : (dc ? k2_clock_list<true> : k2_clock_list<false>);
+    else if (!all) k = dc ? k2_clock_sys_list<true> : k2_clock_sys_list<false>;
+    else k = dc ? (coop ? k2_clock_sys<true, true> : k2_clock_sys<true, false>) : (coop ? k2_clock_sys<false, true> : k2_clock_sys<false, false>);
+    const uint32_t B = sys ? 256u : 64u * (algo == WMBUS_ALGO_RLA ? WM_RLA_WPB : WM_CLK_WPB), per = sys ? 64u : B;      /* threads, lanes per block */
+    const uint32_t grid = all ? (lanes + per - 1u) / per : std::max(sys ? 64u : 16u, (lanes / per) * 3u / 16u);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(B), sys ? sizeof(ClkSysLds) : 0, st, a);
 }
 
 static void fr_carry(wmbus_ctx *c)
 {
     const uint32_t rows = 2u * c->S;
-    const WmPush &g = c->k2clk.g;
-    hipLaunchKernelGGL(k_carry, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)c->k2clk.st_final,
-                       (uint32_t *)st_carry(c, 1, true), (uint32_t)(sizeof(WmClkState) / 4), rows, g.nseg_cap[1], g.nseg[1]);
-    if (c->flags & WM_F_RLA)
-        hipLaunchKernelGGL(k_carry, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)c->k2rla.st_final,
-                           (uint32_t *)st_carry(c, 0, true), (uint32_t)(sizeof(WmRlaState) / 4), rows, g.nseg_cap[0], g.nseg[0]);
-    else   /* a disabled run-length framer keeps its state */
-        hipMemcpyAsync(st_carry(c, 0, true), st_carry(c, 0, false), (size_t)rows * sizeof(WmRlaState), hipMemcpyDeviceToDevice, c->stream);
+    for (int al = 1; al >= 0; al--) {
+        const Framer &f = c->fr[al];
+        const WmPush &g = f.k2.g;
+        if (al == WMBUS_ALGO_T2A || (c->flags & WM_F_RLA))
+            hipLaunchKernelGGL(k_carry, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)f.k2.st_final,
+                               (uint32_t *)st_carry(c, al, true), f.state_bytes / 4u, rows, g.nseg_cap[al], g.nseg[al]);
+        else   /* a disabled run-length framer keeps its state */
+            hipMemcpyAsync(st_carry(c, al, true), st_carry(c, al, false), (size_t)rows * f.state_bytes, hipMemcpyDeviceToDevice, c->stream);
+    }
 }
 
 /* K3 on the settled chip streams: chips-per-framer sums, access-code hits, bursts (decoded on the GPU where they are
@@ -911,16 +852,16 @@ static int launch_k3(wmbus_ctx *c, bool again)
         /* ... and so does its burst-storage warning (chips dropped by the framers stay dropped: that bit is kept) */
         hipLaunchKernelGGL(k_and_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_ERR, ~(uint32_t)WM_ERR_BURST_OVERFLOW);
     }
-    hipLaunchKernelGGL(k_sum_counts, dim3(std::min(64u, (2u * (c->nseg_cap[0] + c->nseg_cap[1]) * c->S + 255u) / 256u)), dim3(256), 0, c->stream, g,
-                       c->d_counts[0], c->d_counts[1], c->d_scalars + SC_CHIPS);
+    hipLaunchKernelGGL(k_sum_counts, dim3(std::min(64u, (2u * (c->fr[0].nseg_cap + c->fr[1].nseg_cap) * c->S + 255u) / 256u)), dim3(256), 0, c->stream, g,
+                       c->fr[0].d_counts, c->fr[1].d_counts, c->d_scalars + SC_CHIPS);
     /* grid.y: the parts a region is scanned in -- the run-length framer's regions can be longer than their capacity (spill chunks) */
     const uint32_t scan_parts = (std::max(g.cap[0] + WM_SPILL_LEVELS * WM_SPILL_CHUNK, g.cap[1]) + WM_K3_SCAN_PART - 1u) / WM_K3_SCAN_PART;
-    hipLaunchKernelGGL(k3_scan, dim3((2u * (g.nseg[0] + g.nseg[1]) * g.S + 255u) / 256u, scan_parts), dim3(256), 0, c->stream, g, c->d_chips[0], c->d_chips[1],
-                       c->d_counts[0], c->d_counts[1], c->d_sync_seen[0], c->d_sync_seen[1], c->d_hits, c->d_scalars + SC_NHITS,
+    hipLaunchKernelGGL(k3_scan, dim3((2u * (g.nseg[0] + g.nseg[1]) * g.S + 255u) / 256u, scan_parts), dim3(256), 0, c->stream, g, c->fr[0].d_chips, c->fr[1].d_chips,
+                       c->fr[0].d_counts, c->fr[1].d_counts, c->fr[0].d_sync_seen, c->fr[1].d_sync_seen, c->d_hits, c->d_scalars + SC_NHITS,
                        c->hits_cap, c->d_scalars + SC_ERR);
     K3Args k3{};
     k3.g = g; k3.rssi = c->d_rssi;
-    k3.chips[0] = c->d_chips[0]; k3.chips[1] = c->d_chips[1]; k3.counts[0] = c->d_counts[0]; k3.counts[1] = c->d_counts[1];
+    for (int al = 0; al < 2; al++) { k3.chips[al] = c->fr[al].d_chips; k3.counts[al] = c->fr[al].d_counts; }
     k3.hits = c->d_hits; k3.n_hits = c->d_scalars + SC_NHITS; k3.hits_cap = c->hits_cap; k3.pending = c->d_pending;
     k3.hdr = (WmBurstHdr *)c->dv_hdr; k3.hdr_cap = c->hdr_cap; k3.words = (uint32_t *)c->dv_words; k3.words_cap = c->words_cap;
     k3.n_hdr = c->d_scalars + SC_NHDR; k3.n_words = c->d_scalars + SC_NWORDS; k3.err = c->d_scalars + SC_ERR;
@@ -928,7 +869,6 @@ static int launch_k3(wmbus_ctx *c, bool again)
         k3.pkts = (WmPkt *)c->dv_pkts; k3.pkts_cap = c->pkts_cap; k3.bytes = (uint8_t *)c->dv_bytes; k3.bytes_cap = c->bytes_cap;
         k3.n_pkts = c->d_scalars + SC_NPKTS; k3.n_bytes = c->d_scalars + SC_NBYTES;
     }
-    k3.plans = nullptr;
     if (c->rs_this && !c->rs_full_now) {
         k3.plans = c->d_plans;
         /* RSSI on demand: which tiles do the bursts touch (k3_spans), then their RSSI (an RS = 2 launch of the demodulation
@@ -938,10 +878,10 @@ static int launch_k3(wmbus_ctx *c, bool again)
                            c->d_rs_flags, c->d_rs_list, c->d_scalars + SC_RS_N);
         K1Args k1 = c->k1a;
         k1.relist = c->d_rs_list; k1.n_relist = c->d_scalars + SC_RS_N;
-        HIPCHK(c, hipEventRecord(c->ev[9], c->stream));
-        const int rc = launch_k1_any(c, k1, dim3(std::max(1u, std::min((uint32_t)WM_RS_BLOCKS, c->ntiles * c->S)), 1), nullptr, 2);    /* r04 A/B: 512 / 1024 / 2048 / 4096 blocks: no difference */
+        HIPCHK(c, hipEventRecord(c->ev[EV_RS], c->stream));
+        const int rc = launch_k1(c, K1_RSSI, k1, dim3(std::max(1u, std::min((uint32_t)WM_RS_BLOCKS, c->ntiles * c->S)), 1));    /* r04 A/B: 512 / 1024 / 2048 / 4096 blocks: no difference */
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev[10], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev[EV_RS_END], c->stream));
     }
     /* Few blocks: a latency-bound wave parked on a SIMD costs the demodulation kernel one of its eight wave slots there
      * for as long as it lives; 256 blocks put one on every SIMD of the chip (r02 sweep: 256 -> 64 blocks + 6 %, 16 blocks - 9 %: then the kernel itself becomes the longest link of the chain) */
@@ -978,21 +918,10 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
-    const dim3 grid((ka.n_out + ka.tile - 1u) / ka.tile, c->S), block(WM_K0_THREADS);
-    if (c->k0.resample)
-        switch (c->k0.fmt) {
-        case WMBUS_FMT_CU8: hipLaunchKernelGGL(k0_resample, grid, block, c->k0.lds, c->stream, ka); break;
-        case WMBUS_FMT_CS8: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CS8>, grid, block, c->k0.lds, c->stream, ka); break;
-        case WMBUS_FMT_CS16: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CS16>, grid, block, c->k0.lds, c->stream, ka); break;
-        default: hipLaunchKernelGGL(k0_resample_fmt<WM_K0_CF32>, grid, block, c->k0.lds, c->stream, ka); break;
-        }
-    else
-        switch (c->k0.fmt) {
-        case WMBUS_FMT_CU8: hipLaunchKernelGGL(k0_convert<WM_K0_CU8>, grid, block, 0, c->stream, ka); break;
-        case WMBUS_FMT_CS8: hipLaunchKernelGGL(k0_convert<WM_K0_CS8>, grid, block, 0, c->stream, ka); break;
-        case WMBUS_FMT_CS16: hipLaunchKernelGGL(k0_convert<WM_K0_CS16>, grid, block, 0, c->stream, ka); break;
-        default: hipLaunchKernelGGL(k0_convert<WM_K0_CF32>, grid, block, 0, c->stream, ka); break;
-        }
+    void (*const resample[4])(K0Args) = {k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>};
+    void (*const convert[4])(K0Args) = {k0_convert<WM_K0_CU8>, k0_convert<WM_K0_CS8>, k0_convert<WM_K0_CS16>, k0_convert<WM_K0_CF32>};      /* [WMBUS_FMT_*] */
+    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
+                       c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
     return WMBUS_OK;
@@ -1018,12 +947,13 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
     g.lut_phase0 = (uint32_t)((13ull * (c->n0 % g.lut_n)) % g.lut_n);
     g.flags = c->flags;
     for (int al = 0; al < 2; al++) {
-        g.seg_len[al] = c->C[al]; g.nseg[al] = (g.M + c->C[al] - 1) / c->C[al]; g.nseg_cap[al] = c->nseg_cap[al]; g.cap[al] = c->cap[al];
+        const Framer &f = c->fr[al];
+        g.seg_len[al] = f.C; g.nseg[al] = (g.M + f.C - 1) / f.C; g.nseg_cap[al] = f.nseg_cap; g.cap[al] = f.cap;
     }
     g.warm[0] = c->cfg.warmup_t1c1; g.warm[1] = c->cfg.warmup_s1; g.lookback = c->cfg.rla_lookback;
     g.s1_span = 1u;                                     /* (2: S1 clock lanes over two segments -- built and measured in rounds 2-4, -2 %: the kernels keep the form) */
     g.sp.arena = c->d_spill; g.sp.arena_words = c->spill_words; g.sp.chain = c->d_chain; g.sp.nchain = c->d_nchain;
-    g.sp.used = c->d_nchain + (size_t)2 * c->S * c->nseg_cap[0];
+    g.sp.used = c->d_nchain + (size_t)2 * c->S * c->fr[0].nseg_cap;
     c->last = g; c->have_last = true;
     c->n_hdr = c->n_words = c->n_pkts = 0;
     c->enqueued = true;                                 /* from here on a failure leaves half a push on the stream: the context is poisoned */
@@ -1033,7 +963,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
         HIPCHK(c, hipEventRecord(c->ev_staged, c->copy_stream));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
     }
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[EV_PUSH], c->stream));
     hipLaunchKernelGGL(k_copy_hist, dim3(c->S), dim3(256), 0, c->stream, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint64_t)0, win, c->in_stride);
     if (c->k0.on && g.M == 0) {                          /* a push that completes no block: K0 alone, and its clip count */
         HIPCHK(c, hipMemsetAsync(c->d_scalars + SC_CLIP, 0, sizeof(uint32_t), c->stream));
@@ -1060,7 +990,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             K1Chain &kc = k1_chain[c->cfg.device];
             std::lock_guard<std::mutex> lk(kc.m);
             if (kc.last && kc.owner != c) HIPCHK(c, hipStreamWaitEvent(c->stream, kc.last, 0));
-            HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+            HIPCHK(c, hipEventRecord(c->ev[EV_K1], c->stream));
             if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
             /* The hand-over of the turn costs 0.15-0.2 ms (the next context's stream sits in an event wait on another
              * hardware queue; r03 trace: median 128 us between one K1 and the next, eight times per step = 5 % of it).
@@ -1073,7 +1003,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             const uint32_t T1 = big ? (uint32_t)WM_K1_TILE_BIG : T, nt1 = (g.M + T1 - 1) / T1;
             const uint32_t n_tail = std::min(nt1 - 1u, (uint32_t)((uint64_t)nt1 * c->k1_tail_pm / 1000u));
             K1Args k1 = c->k1a;
-            const int rs = c->rs_this ? 1 : 0;
+            const K1Role role = c->rs_this ? K1_FIRST : K1_FULL;
             /* the first pass without the RSSI takes several consecutive tiles per block: the input of a block's next tile is on
              * its way while the current one is computed (wm_k1_demod.h, K1Args.tpb) */
             const uint32_t tpb = c->rs_this && c->d >= 2 && c->d <= 5 ? c->k1_tpb : 1u;
@@ -1085,16 +1015,16 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
 #else
             const bool dbg_skip = false;
 #endif
-            rc = dbg_skip ? 0 : launch_k1_any(c, k1, dim3((nt1 - n_tail + tpb - 1u) / tpb, c->S), nullptr, rs, big);
+            rc = dbg_skip ? 0 : launch_k1(c, role, k1, dim3((nt1 - n_tail + tpb - 1u) / tpb, c->S));
             if (rc) return rc;
             if (n_tail && !dbg_skip) {
                 HIPCHK(c, hipEventRecord(c->ev_turn, c->stream));
                 k1.tile0 = nt1 - n_tail; k1.tile_end = nt1;
-                rc = launch_k1_any(c, k1, dim3((n_tail + tpb - 1u) / tpb, c->S), nullptr, rs, big);
+                rc = launch_k1(c, role, k1, dim3((n_tail + tpb - 1u) / tpb, c->S));
                 if (rc) return rc;
             }
-            HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-            kc.last = n_tail ? c->ev_turn : c->ev[4]; kc.owner = c;
+            HIPCHK(c, hipEventRecord(c->ev[EV_K1_END], c->stream));
+            kc.last = n_tail ? c->ev_turn : c->ev[EV_K1_END]; kc.owner = c;
         }
         /* Everything behind K1 is enqueued while it runs -- no step of a push waits for the host any more:
          * hand-off verification makes its first rounds on the device (counters per round), K3 reads its item
@@ -1111,18 +1041,17 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
         }
 
         /* K2: clock recovery + time2 framer (also produces the slicer bits the RLA needs) */
-        K2Args k2{};
+        K2Args k2{};                                        /* what both framers share; the rest is Framer's */
         k2.g = g; k2.dphi = c->d_dphi; k2.rssi = c->d_rssi; k2.bits = c->d_bits;
         k2.err = c->d_scalars + SC_ERR;
         k2.ckpt = c->d_ckpt; k2.nck = c->nck;
-        c->k2clk = k2; c->k2rla = k2;
-        K2Args &ka = c->k2clk, &kr = c->k2rla;
-        ka.algo = WMBUS_ALGO_T2A; ka.bad = c->d_bad_clk;
-        ka.chips = c->d_chips[1]; ka.counts = c->d_counts[1]; ka.sync_seen = c->d_sync_seen[1];
-        ka.st_start = c->d_st_start[1]; ka.st_final = c->d_st_final[1]; ka.st_carry = st_carry(c, 1, false);
-        kr.algo = WMBUS_ALGO_RLA; kr.bad = c->rla_chains ? c->d_bad : nullptr;
-        kr.chips = c->d_chips[0]; kr.counts = c->d_counts[0]; kr.sync_seen = c->d_sync_seen[0];
-        kr.st_start = c->d_st_start[0]; kr.st_final = c->d_st_final[0]; kr.st_carry = st_carry(c, 0, false);
+        for (int al = 0; al < 2; al++) {
+            Framer &f = c->fr[al];
+            f.k2 = k2;
+            f.k2.algo = (uint32_t)al; f.k2.bad = f.d_bad;
+            f.k2.chips = f.d_chips; f.k2.counts = f.d_counts; f.k2.sync_seen = f.d_sync_seen;
+            f.k2.st_start = f.d_st_start; f.k2.st_final = f.d_st_final; f.k2.st_carry = st_carry(c, al, false);
+        }
         /* One stream, one launch after the other: clock first pass, its unattended re-run rounds, then the run-length framer and its
          * rounds.  (Rounds 2-4 built and measured the alternatives -- the clock re-run lanes and the run-length framer fused into one
          * launch; the run-length framer on a side stream beside the clock rounds -- both shorten a context's chain of launches by
@@ -1130,35 +1059,33 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
          * get in its way; DESIGN_HISTORY.md.  Round 5 brought the fused launch back once more, with the demodulation kernel 13 % shorter and
          * a context's chain the bound: 155-161 against 172 Gsamples/s, the demodulation kernel in region 3.8-4.0 instead of 3.3 ms.) */
         const bool rla = c->flags & WM_F_RLA;
-        HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-        fr_launch(c, WMBUS_ALGO_T2A, 0xFFFFFFFFu);                 /* the clock kernel's first pass */
-        /* (a push of one segment per row has no hand-off inside it: its only lane starts from the carried state -- no rounds to enqueue;
-         * a live stream's 2^16-sample pushes are such) */
-        for (unsigned r = 0; r < c->fr_rounds && c->opt_rounds && g.nseg[1] > 1u; r++) { fr_verify(c, WMBUS_ALGO_T2A, SC_CLK + r); fr_launch(c, WMBUS_ALGO_T2A, SC_CLK + r); }
-        HIPCHK(c, hipEventRecord(c->ev[8], c->stream));
-        if (rla) {
-            fr_launch(c, WMBUS_ALGO_RLA, 0xFFFFFFFFu);
-            for (unsigned r = 1; r < c->rla_rounds && c->opt_rounds && g.nseg[0] > 1u; r++) { fr_verify(c, WMBUS_ALGO_RLA, SC_RLA + r); fr_launch(c, WMBUS_ALGO_RLA, SC_RLA + r); }
-        } else HIPCHK(c, hipMemsetAsync(c->d_counts[0], 0, (size_t)2 * c->S * c->nseg_cap[0] * sizeof(uint32_t), c->stream));
-        c->rla_fin = c->rla_rounds;
+        for (int al = 1; al >= (rla ? 0 : 1); al--) {
+            const Framer &f = c->fr[al];
+            HIPCHK(c, hipEventRecord(c->ev[al ? EV_CLK : EV_RLA], c->stream));
+            fr_launch(c, al, 0xFFFFFFFFu);                           /* the first pass */
+            /* (a push of one segment per row has no hand-off inside it: its only lane starts from the carried state -- no rounds to enqueue;
+             * a live stream's 2^16-sample pushes are such) */
+            for (unsigned r = f.round0; r < f.rounds && c->opt_rounds && g.nseg[al] > 1u; r++) { fr_verify(c, al, f.sc + r); fr_launch(c, al, f.sc + r); }
+        }
         if (rla) {
             /* the last verification of either framer and both carries in one launch (k2_finish) */
-            K2Finish f{};
-            const K2Args *ka2[2] = {&c->k2rla, &c->k2clk};
+            K2Finish fin{};
             for (int al = 0; al < 2; al++) {
-                f.st_start[al] = (const uint32_t *)ka2[al]->st_start; f.st_final[al] = (const uint32_t *)ka2[al]->st_final;
-                f.words[al] = (uint32_t)((al ? sizeof(WmClkState) : sizeof(WmRlaState)) / 4);
-                f.carry[al] = (uint32_t *)st_carry(c, al, true); f.verify[al] = 1u; f.do_carry[al] = 1u;
+                const Framer &f = c->fr[al];
+                fin.st_start[al] = (const uint32_t *)f.k2.st_start; fin.st_final[al] = (const uint32_t *)f.k2.st_final;
+                fin.words[al] = f.state_bytes / 4u;
+                fin.carry[al] = (uint32_t *)st_carry(c, al, true); fin.verify[al] = 1u; fin.do_carry[al] = 1u;
+                fin.list[al] = f.d_list; fin.n_list[al] = c->d_scalars + f.sc + f.rounds; fin.bad[al] = f.d_bad;
+                fin.heads[al] = list_walks_chains(c, al, f.sc + f.rounds);
             }
-            f.list[0] = c->d_list2; f.list[1] = c->d_list; f.n_list[0] = c->d_scalars + SC_RLA + c->rla_fin; f.n_list[1] = c->d_scalars + SC_CLK + c->fr_rounds;
-            f.bad[0] = c->rla_chains ? c->d_bad : nullptr; f.bad[1] = c->d_bad_clk;
-            f.heads[0] = list_walks_chains(c, WMBUS_ALGO_RLA, SC_RLA + c->rla_fin); f.heads[1] = list_walks_chains(c, WMBUS_ALGO_T2A, SC_CLK + c->fr_rounds);
             const uint32_t most = std::max(2u * g.S, 2u * std::max(g.nseg[0], g.nseg[1]) * g.S);
-            hipLaunchKernelGGL(k2_finish, dim3((most + 255u) / 256u), dim3(256), 0, c->stream, g, f);
-            HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+            hipLaunchKernelGGL(k2_finish, dim3((most + 255u) / 256u), dim3(256), 0, c->stream, g, fin);
+            HIPCHK(c, hipEventRecord(c->ev[EV_FR_END], c->stream));
         } else {
-            fr_verify(c, WMBUS_ALGO_T2A, SC_CLK + c->fr_rounds);
-            HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+            HIPCHK(c, hipEventRecord(c->ev[EV_RLA], c->stream));
+            HIPCHK(c, hipMemsetAsync(c->fr[0].d_counts, 0, (size_t)2 * c->S * c->fr[0].nseg_cap * sizeof(uint32_t), c->stream));
+            fr_verify(c, WMBUS_ALGO_T2A, c->fr[1].sc + c->fr[1].rounds);
+            HIPCHK(c, hipEventRecord(c->ev[EV_FR_END], c->stream));
             fr_carry(c);
         }
         c->committed = true;
@@ -1186,12 +1113,12 @@ static int enqueue_back_impl(wmbus_ctx *c)
                 for (int al = 0; al < 2; al++)
                     c->h_pending[(al * 2 + ch) * c->S + s] = c->decs[((size_t)s * 2 + ch) * 2 + al].owed;
         HIPCHK(c, hipMemcpyAsync(c->d_pending, c->h_pending, 4 * c->S * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev[EV_K3], c->stream));
         const int rc = launch_k3(c, false);
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev[EV_K3_END], c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev[EV_D2H_END], c->stream));
     }
     return WMBUS_OK;
 }
@@ -1220,185 +1147,67 @@ int wmbus_process(wmbus_ctx *c, size_t nbytes)
 
 /* The optimistic rounds of wmbus_process left work: finish it round by round with the host in the loop (rare: a
  * cascade of hand-off failures longer than the rounds enqueued), then redo what depended on it. */
-static int finish_slowly(wmbus_ctx *c, bool ema_left, bool clk_left, bool rla_left, bool rs_left = false)
+static int finish_slowly(wmbus_ctx *c, bool ema_left, bool left[2], bool rs_left = false)      /* left: [WMBUS_ALGO_*] */
 {
-    auto leftovers = [&](uint32_t *n) -> int {
+    auto read_scalars = [&]() -> int {
         HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        *n = c->h_scalars[SC_SLOW];
         return 0;
     };
+    /* verify once more, counting in SC_SLOW (cleared behind whatever launch has just read it); algo < 0: the RSSI filter's hand-offs */
+    auto recheck = [&](int algo, uint32_t *n) -> int {
+        hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_SLOW, 0u);
+        if (algo < 0) ema_verify(c, SC_SLOW); else fr_verify(c, algo, SC_SLOW);
+        const int rc = read_scalars();
+        *n = c->h_scalars[SC_SLOW];
+        return rc;
+    };
     const uint32_t max_rounds = std::max({c->ntiles, c->last.nseg[0], c->last.nseg[1]}) + 4;
+    /* re-run the list whose length is scalar `cnt` (the list of the last verify of its kind is still there), verify, and again until nothing is listed */
+    auto settle = [&](int algo, uint32_t cnt, unsigned *tally, const char *what) -> int {
+        for (uint32_t round = 0, n = 0;; round++, cnt = SC_SLOW) {
+            *tally += c->h_scalars[cnt];
+            int rc = 0;
+            if (algo < 0) rc = ema_repair(c, cnt); else fr_launch(c, algo, cnt);
+            if (rc || (rc = recheck(algo, &n))) return rc;
+            if (n == 0) return 0;
+            if (round > max_rounds) return fail(c, WMBUS_EDEVICE, "%s did not converge", what);
+        }
+    };
+    int rc;
     if (rs_left) {
         /* RSSI on demand, and a lane whose value is read could not prove it (wm_k1_demod.h: constant input can keep the bracket
          * open): this push's RSSI the long way -- the full kernel over every tile, its hand-offs verified against the carried
          * state and repaired like any other context's */
         uint32_t n = 0;
-        int rc = launch_k1_any(c, c->k1a, dim3(c->ntiles, c->S));
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_SLOW, 0u);
-        ema_verify(c, SC_SLOW);
-        if ((rc = leftovers(&n))) return rc;
+        if ((rc = launch_k1(c, K1_FULL, c->k1a, dim3(c->ntiles, c->S))) || (rc = recheck(-1, &n))) return rc;
         ema_left = n != 0;
         if (!ema_left) ema_commit(c);
         c->rs_full_now = true;
     }
     if (ema_left) {
-        uint32_t cnt = rs_left ? (uint32_t)SC_SLOW : SC_EMA + c->ema_rounds, n = 0;          /* the list of the last verify is still in d_list_ema */
-        for (uint32_t round = 0;; round++) {
-            c->tim.ema_retries += c->h_scalars[cnt];
-            int rc = ema_repair(c, cnt);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_SLOW, 0u);    /* after the repair has read it */
-            ema_verify(c, SC_SLOW);
-            if ((rc = leftovers(&n))) return rc;
-            if (n == 0) break;
-            if (round > max_rounds) return fail(c, WMBUS_EDEVICE, "RSSI filter hand-off repair did not converge");
-            cnt = SC_SLOW;
-        }
+        if ((rc = settle(-1, rs_left ? (uint32_t)SC_SLOW : SC_EMA + c->ema_rounds, &c->tim.ema_retries, "RSSI filter hand-off repair"))) return rc;
         ema_commit(c);
     }
     for (int algo = 1; algo >= 0; algo--) {                    /* clock first: with -o the slicer words depend on it */
-        if (!(algo ? clk_left : rla_left)) continue;
-        uint32_t cnt = algo ? SC_CLK + c->fr_rounds : SC_RLA + c->rla_fin, n = 0;
-        for (uint32_t round = 0;; round++) {
-            (algo ? c->tim.clock_reruns : c->tim.rla_reruns) += c->h_scalars[cnt];
-            fr_launch(c, algo, cnt);
-            hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_SLOW, 0u);
-            fr_verify(c, algo, SC_SLOW);
-            int rc = leftovers(&n);
-            if (rc) return rc;
-            if (n == 0) break;
-            if (round > max_rounds) return fail(c, WMBUS_EDEVICE, "segment verification did not converge");
-            cnt = SC_SLOW;
-        }
-        if (algo == 1 && (c->flags & WM_F_DC) && (c->flags & WM_F_RLA)) {
+        const Framer &f = c->fr[algo];
+        if (left[algo] && (rc = settle(algo, f.sc + f.rounds, algo ? &c->tim.clock_reruns : &c->tim.rla_reruns, "segment verification"))) return rc;
+        if (left[algo] && algo == WMBUS_ALGO_T2A && (c->flags & WM_F_DC) && (c->flags & WM_F_RLA)) {
             /* the run-length framer ran on slicer words that the clock re-runs have just replaced: all of it again */
+            const uint32_t last = c->fr[0].sc + c->fr[0].rounds;
             fr_launch(c, WMBUS_ALGO_RLA, 0xFFFFFFFFu);
-            hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_RLA + c->rla_fin, 0u);
-            fr_verify(c, WMBUS_ALGO_RLA, SC_RLA + c->rla_fin);
-            HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            rla_left = c->h_scalars[SC_RLA + c->rla_fin] != 0;
+            hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + last, 0u);
+            fr_verify(c, WMBUS_ALGO_RLA, last);
+            if ((rc = read_scalars())) return rc;
+            left[0] = c->h_scalars[last] != 0;
         }
     }
     fr_carry(c);
-    int rc = launch_k3(c, true);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = launch_k3(c, true)) || (rc = read_scalars())) return rc;
     /* the chips have changed, so have the bursts and the tiles they touch: one of those may be unprovable in turn */
-    if (c->rs_this && !c->rs_full_now && c->h_scalars[SC_RS_FAIL]) return finish_slowly(c, false, false, false, true);
+    bool none[2] = {false, false};
+    if (c->rs_this && !c->rs_full_now && c->h_scalars[SC_RS_FAIL]) return finish_slowly(c, false, none, true);
     return 0;
-}
-
-namespace {
-struct Entry { uint32_t idx; uint8_t raw; };          /* one candidate telegram of a push: a WmPkt (decoded on the GPU) or a WmBurstHdr (chips) */
-struct EntryKey { uint32_t stream, chip0; uint8_t chain, algo, cont; };
-}
-
-static EntryKey entry_key(const wmbus_ctx *c, const Entry &e)
-{
-    if (e.raw) { const WmBurstHdr &h = c->h_hdr[e.idx]; return EntryKey{h.stream, h.chip0, h.chain, h.algo, (uint8_t)(h.flags & 1u)}; }
-    const WmPkt &p = c->h_pkts[e.idx];
-    return EntryKey{p.stream, p.chip0, p.chain, p.algo, 0};
-}
-
-/* Candidate telegrams of the (stream, chain, framer) groups in order[lo, hi), each group in chip order: what the
- * reference's decoder would do with them -- an access code that passes while the decoder is busy is ignored
- * (t1_c1_packet_decoder.h:272-278), a telegram the GPU has assembled is stripped and formatted, a burst cut by the end
- * of the push goes chip by chip through the persistent host decoder. */
-/* TIMESTAMP field of a line.  The reference stamps a telegram when its last chip is processed (t1_c1_packet_decoder.h:
- * 390,458, s1_packet_decoder.h:229), which behind a live SDR is the moment that sample arrived.  A push is handed over
- * when its LAST sample has arrived, so a telegram completed by decimated sample m of the push was on the air
- * (m_end - 1 - m) / 800 kHz earlier (the decimated rate is 800 kS/s whatever -d is, rtl_wmbus.c:1296). */
-static void line_timestamp(const wmbus_ctx *c, uint64_t sample, const char *ts_fixed, char *ts, size_t cap)
-{
-    if (ts_fixed) { snprintf(ts, cap, "%s", ts_fixed); return; }
-    const uint64_t back = c->done.m_end > sample ? c->done.m_end - 1u - sample : 0u;
-    const int64_t us = (int64_t)c->done.arrival.tv_sec * 1000000 + c->done.arrival.tv_usec - (int64_t)(back * 5u / 4u);   /* 1.25 us per decimated sample */
-    wm_timestamp_at(ts, cap, (long)(us / 1000000), (long)(us % 1000000));
-}
-
-static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, size_t lo, size_t hi,
-                                LinePart &part, uint32_t part_no, const char *ts_fixed)
-{
-    std::vector<LineRec> &out = part.recs;
-    auto keep = [&](LineRec &r, const char *line, size_t n) {
-        r.part = part_no; r.off = (uint32_t)part.text.size(); r.len = (uint32_t)n;
-        part.text.append(line, n);
-        out.push_back(r);
-    };
-    char line[1024], ts[64];
-    uint8_t pkt[WM_PKT_MAXBYTES + 4];
-    uint32_t seq = 0;
-    size_t i = lo;
-    while (i < hi) {
-        const EntryKey k0 = entry_key(c, order[i]);
-        HostDecoder &hd = c->decs[((size_t)k0.stream * 2 + k0.chain) * 2 + k0.algo];
-        const char *tag = c->cfg.show_algorithm ? (k0.algo == WMBUS_ALGO_RLA ? "rla;" : "t2a;") : "";
-        uint64_t next_free = 0;                         /* first chip the decoder has not consumed */
-        size_t j = i;
-        for (; j < hi; j++) {
-            const EntryKey kj = entry_key(c, order[j]);
-            if (kj.stream != k0.stream || kj.chain != k0.chain || kj.algo != k0.algo) break;
-            if (!order[j].raw) {
-                /* ---- the whole burst was inside the push: the GPU has run the decoder over it ---- */
-                const WmPkt &p = c->h_pkts[order[j].idx];
-                if (hd.owed != 0 || p.chip0 < next_free) continue;     /* the access code passed while the decoder was busy */
-                next_free = (uint64_t)p.chip0 + p.consumed;
-                if (p.status != WM_PKT_DONE) continue;
-                const unsigned nb = std::min<unsigned>(std::max<unsigned>(p.L, 2u), WM_PKT_MAXBYTES);
-                /* the reference's decoder is memset on reset (t1_c1_packet_decoder.h:268,276): bytes a short telegram never
-                 * stored read as zero in the ident field of its line (get_serial looks at bytes 4..7 whatever L is) */
-                memset(pkt, 0, sizeof pkt);
-                memcpy(pkt, c->h_bytes + p.off, nb);
-                line_timestamp(c, p.sample, ts_fixed, ts, sizeof ts);
-                const int ok = (p.flags & WM_PKTF_CRC_OK) != 0;
-                const size_t n = wm_packet_format(p.chain ? WM_MODE_S1 : WM_MODE_T1C1, (p.flags & WM_PKTF_C1) != 0, (p.flags & WM_PKTF_FRAME_B) != 0,
-                                                  (p.flags & WM_PKTF_ERR3OF6) != 0, ok, p.L, pkt, p.pkt_rssi, p.rssi_now, tag, ts, line, sizeof line);
-                LineRec r; r.sample = p.sample; r.stream = p.stream; r.chain = p.chain; r.algo = p.algo;
-                r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                keep(r, line, n);
-                continue;
-            }
-            const WmBurstHdr &h = c->h_hdr[order[j].idx];
-            const bool cont = h.flags & 1u;
-            if (cont ? hd.owed == 0 : (hd.owed != 0 || h.chip0 < next_free)) continue;   /* the access code passed while the decoder was busy */
-            const uint32_t *w = c->h_words + h.word_off;
-            int st = cont ? WM_DEC_RECEIVING : WM_DEC_IDLE;
-            uint32_t k = 0;
-            for (; k < h.n_chips; k++) {
-                const uint32_t word = w[k];
-                const unsigned val = word & 7u, rssi = (word >> 3) & 0xFFu;
-                if ((val & 4u) && st == WM_DEC_RECEIVING) {   /* the run-length framer reset itself: telegram lost */
-                    wm_decoder_abort(&hd.dec);
-                    st = WM_DEC_IDLE;
-                    break;                                     /* this chip may start a burst of its own */
-                }
-                st = wm_decoder_chip(&hd.dec, val & 3u, rssi);
-                if (st == WM_DEC_DONE) {
-                    int ok = 0;
-                    line_timestamp(c, h.pos0 + (word >> 11), ts_fixed, ts, sizeof ts);
-                    const size_t n = wm_decoder_format(&hd.dec, tag, ts, rssi, line, sizeof line, &ok);
-                    LineRec r; r.sample = h.pos0 + (word >> 11); r.stream = h.stream; r.chain = h.chain; r.algo = h.algo;
-                    r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                    keep(r, line, n);
-                    st = WM_DEC_IDLE;
-                }
-                if (st == WM_DEC_IDLE) { k++; break; }
-            }
-            next_free = (uint64_t)h.chip0 + k;
-            const bool cut = st == WM_DEC_RECEIVING;
-            if (cut && h.n_chips != h.avail) {                 /* device under-estimated the burst: a bug */
-                uint32_t none = 0;
-                c->short_burst.compare_exchange_strong(none, 1u + order[j].idx);
-            }
-            hd.owed = cut ? std::max(1u, wm_decoder_chips_owed(&hd.dec)) : 0u;
-            hd.fed = c->done.seq;
-        }
-        i = j;
-    }
 }
 
 /* First half of wmbus_collect: wait for the push, finish leftover hand-off rounds, read the counters.  Afterwards the
@@ -1414,15 +1223,15 @@ static int wait_gpu(wmbus_ctx *c)
     c->tim = wmbus_timing{};
     if (c->k0.on) { c->tim.input_bytes_out = c->k0.last_out; c->tim.input_clipped = c->h_scalars[SC_CLIP]; }
     if (c->last.M > 0) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, c->ev[3], c->ev[4]); c->tim.demod_ms = ms;
-        hipEventElapsedTime(&ms, c->ev[2], c->ev[3]); c->tim.turn_wait_ms = ms;  /* on the GPU: behind the other contexts' demodulation kernels */
-        hipEventElapsedTime(&ms, c->ev[0], c->ev[8]); c->tim.clock_ms = ms;      /* the clock kernel's launches */
-        hipEventElapsedTime(&ms, c->ev[8], c->ev[1]); c->tim.rla_ms = ms;        /* the run-length framer's */
-        if (c->rs_this) { hipEventElapsedTime(&ms, c->ev[9], c->ev[10]); c->tim.rssi_ms = ms; }
-        hipEventElapsedTime(&ms, c->ev[5], c->ev[6]); c->tim.gather_ms = ms;
-        hipEventElapsedTime(&ms, c->ev[6], c->ev[7]); c->tim.d2h_ms = ms;
-        hipEventElapsedTime(&ms, c->ev[2], c->ev[7]); c->tim.gpu_total_ms = ms;
+        auto span = [&](int from, int to) { float ms = 0; hipEventElapsedTime(&ms, c->ev[from], c->ev[to]); return ms; };
+        c->tim.demod_ms = span(EV_K1, EV_K1_END);
+        c->tim.turn_wait_ms = span(EV_PUSH, EV_K1);          /* on the GPU: behind the other contexts' demodulation kernels */
+        c->tim.clock_ms = span(EV_CLK, EV_RLA);              /* the clock kernel's launches */
+        c->tim.rla_ms = span(EV_RLA, EV_FR_END);             /* the run-length framer's */
+        if (c->rs_this) c->tim.rssi_ms = span(EV_RS, EV_RS_END);
+        c->tim.gather_ms = span(EV_K3, EV_K3_END);
+        c->tim.d2h_ms = span(EV_K3_END, EV_D2H_END);
+        c->tim.gpu_total_ms = span(EV_PUSH, EV_D2H_END);
         const uint32_t *hs = c->h_scalars;
 #ifdef WM_DBG_WALK_STATS
         if (c->push_seq == 4) {
@@ -1436,22 +1245,24 @@ static int wait_gpu(wmbus_ctx *c)
         }
 #endif
         for (unsigned r = 0; r < c->ema_rounds; r++) c->tim.ema_retries += hs[SC_EMA + r];
-        for (unsigned r = 0; r < c->fr_rounds; r++) c->tim.clock_reruns += hs[SC_CLK + r];
-        for (unsigned r = 0; r < c->rla_fin; r++) c->tim.rla_reruns += hs[SC_RLA + r];
-        const bool ema_left = hs[SC_EMA + c->ema_rounds], clk_left = hs[SC_CLK + c->fr_rounds], rla_left = hs[SC_RLA + c->rla_fin];
-        const bool rs_left = c->rs_this && hs[SC_RS_FAIL] != 0;
-        for (unsigned r = 0; r < 4; r++) {
-            c->tim.clock_round[r] = r < c->fr_rounds ? hs[SC_CLK + r] : 0u;
-            c->tim.rla_round[r] = r + 1u < c->rla_fin ? hs[SC_RLA + 1u + r] : 0u;     /* the run-length framer's counters start at index 1 */
+        unsigned *const reruns[2] = {&c->tim.rla_reruns, &c->tim.clock_reruns}, *const per_round[2] = {c->tim.rla_round, c->tim.clock_round};
+        bool left[2];
+        for (int al = 0; al < 2; al++) {
+            const Framer &f = c->fr[al];
+            for (unsigned r = f.round0; r < f.rounds; r++) *reruns[al] += hs[f.sc + r];
+            for (unsigned r = 0; r < 4; r++) per_round[al][r] = f.round0 + r < f.rounds ? hs[f.sc + f.round0 + r] : 0u;
+            left[al] = hs[f.sc + f.rounds] != 0;
         }
+        const bool ema_left = hs[SC_EMA + c->ema_rounds];
+        const bool rs_left = c->rs_this && hs[SC_RS_FAIL] != 0;
         c->tim.rssi_mode = c->rs_this ? WMBUS_RSSI_ON_DEMAND : c->rs_od ? WMBUS_RSSI_PAUSED : WMBUS_RSSI_EVERY_SAMPLE;
         if (c->rs_this) {
             c->tim.rssi_tiles = hs[SC_RS_N];
             const uint32_t dense_pm = c->cfg.rssi_dense_pm ? c->cfg.rssi_dense_pm : 200u;
             if ((uint64_t)hs[SC_RS_N] * 1000u > (uint64_t)dense_pm * c->ntiles * c->S) c->rs_pause = 16;
         }
-        if (ema_left || clk_left || rla_left || rs_left) {
-            const int rc = finish_slowly(c, ema_left, clk_left, rla_left, rs_left);
+        if (ema_left || left[0] || left[1] || rs_left) {
+            const int rc = finish_slowly(c, ema_left, left, rs_left);
             if (rc) { c->poisoned = true; return rc; }
             c->tim.slow_path = 1;
             if (c->rs_full_now) c->tim.rssi_mode = WMBUS_RSSI_FELL_BACK;
@@ -1470,101 +1281,6 @@ static int wait_gpu(wmbus_ctx *c)
     c->tim.bursts = c->n_hdr + c->n_pkts;
     c->done.n_hdr = c->n_hdr; c->done.n_pkts = c->n_pkts; c->done.m_end = c->last.m0 + c->last.M; c->done.arrival = c->arrival; c->done.seq = c->push_seq;
     c->done.valid = true;
-    return WMBUS_OK;
-}
-
-/* Second half: candidate telegrams -> lines (host packet decoders, strip, format, merge).  Touches pinned host memory
- * and the decoders only, so the NEXT push's front may already be on the GPU. */
-static int decode_host(wmbus_ctx *c)
-{
-    c->lines.clear(); c->text.clear();
-    c->short_burst.store(0);
-    if (!c->done.valid) return WMBUS_OK;
-    c->done.valid = false;
-    const double t0 = now_ms();
-    const uint32_t n_hdr = c->done.n_hdr, n_pkts = c->done.n_pkts;
-
-    /* candidates in the order the decoders take them: (capture, chain, framer), a continuation first, then by chip.  The key is made
-     * ONCE per candidate (the comparator used to look every candidate's record up in the page-locked result area at every comparison) */
-    std::vector<Entry> order(n_hdr + n_pkts);
-    {
-        struct Keyed { uint64_t hi; uint32_t lo; Entry e; };
-        std::vector<Keyed> ks(n_hdr + n_pkts);
-        for (uint32_t i = 0; i < n_hdr + n_pkts; i++) {
-            const Entry e = i < n_hdr ? Entry{i, 1} : Entry{i - n_hdr, 0};
-            const EntryKey k = entry_key(c, e);
-            ks[i] = Keyed{((uint64_t)k.stream << 8) | ((uint64_t)k.chain << 4) | ((uint64_t)k.algo << 1) | (k.cont ? 0u : 1u), k.chip0, e};
-        }
-        std::stable_sort(ks.begin(), ks.end(), [](const Keyed &x, const Keyed &y) { return x.hi != y.hi ? x.hi < y.hi : x.lo < y.lo; });
-        for (size_t i = 0; i < ks.size(); i++) order[i] = ks[i].e;
-    }
-    unsigned nt = c->cfg.host_threads ? c->cfg.host_threads : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (order.size() < 4096) nt = 1;
-    const char *tsf = c->cfg.fixed_timestamp ? "TS" : nullptr;
-    /* more pieces than threads (cut at stream boundaries): the decoders' cost per stream is uneven */
-    const unsigned np = nt == 1 ? 1 : 4 * nt;
-    std::vector<LinePart> parts(np);
-    if (np == 1) decode_stream_range(c, order, 0, order.size(), parts[0], 0u, tsf);
-    else {
-        std::vector<size_t> cut(np + 1, order.size());
-        cut[0] = 0;
-        for (unsigned t = 1; t < np; t++) {
-            size_t p = order.size() * t / np;
-            while (p < order.size() && p > 0 && entry_key(c, order[p]).stream == entry_key(c, order[p - 1]).stream) p++;
-            cut[t] = std::max(p, cut[t - 1]);
-        }
-        if (!c->pool || c->pool->size() + 1 != nt) c->pool.reset(new WorkerPool(nt - 1));
-        c->pool->run(np, [&](unsigned t) { decode_stream_range(c, order, cut[t], cut[t + 1], parts[t], t, tsf); });
-    }
-    /* Burst storage ran out (a warning): a half-received telegram whose continuation was among the dropped bursts would
-     * otherwise wait for it for ever and take the FIRST chips of the next push for its own -- it is lost, like the
-     * bursts that were dropped. */
-    if (c->tim.warnings & WMBUS_WARN_BURSTS_DROPPED)
-        for (auto &hd : c->decs)
-            if (hd.owed != 0 && hd.fed != c->done.seq) { wm_decoder_abort(&hd.dec); hd.owed = 0; }
-    /* stdout order of the reference: by completing sample, then T1/C1 before S1, run-length before time2 */
-    std::vector<LineRec> all;
-    {
-        size_t n_all = 0, n_text = 0;
-        for (auto &p : parts) { n_all += p.recs.size(); n_text += p.text.size(); }
-        all.reserve(n_all); c->text.reserve(n_text); c->lines.reserve(n_all);
-        for (auto &p : parts) all.insert(all.end(), p.recs.begin(), p.recs.end());
-    }
-    std::stable_sort(all.begin(), all.end(), [](const LineRec &a, const LineRec &b) {
-        if (a.stream != b.stream) return a.stream < b.stream;
-        if (a.sample != b.sample) return a.sample < b.sample;
-        if (a.chain != b.chain) return a.chain < b.chain;
-        if (a.algo != b.algo) return a.algo < b.algo;
-        return a.seq < b.seq;
-    });
-    /* Options (off by default: the drop-in prints what the reference prints).  Both framers work on every burst, so a
-     * clean telegram is printed twice, once per framer (README.md:105-108 "You will eventually get two identical
-     * datagrams"): dedup_twins drops the later of two lines of one capture and mode that carry the same payload, come
-     * from different framers and complete within one longest-telegram time of each other.  only_crc_ok drops what a
-     * consumer like wmbusmeters would discard anyway. */
-    if (c->cfg.dedup_twins || c->cfg.only_crc_ok) {
-        if (c->twins.empty()) c->twins.assign((size_t)c->S * 2 * 2, wm_twin{0, 0, 0, 0});
-        std::vector<LineRec> kept;
-        kept.reserve(all.size());
-        for (auto &r : all) {
-            if (c->cfg.only_crc_ok && !r.crc_ok) continue;
-            if (c->cfg.dedup_twins && wm_twin_check(&c->twins[((size_t)r.stream * 2 + r.chain) * 2], r.chain, r.algo, r.sample, parts[r.part].text.data() + r.off, r.len)) continue;
-            kept.push_back(r);
-        }
-        all.swap(kept);
-    }
-    for (auto &r : all) {
-        wmbus_line l{};
-        l.stream = r.stream; l.chain = r.chain; l.algo = r.algo; l.crc_ok = r.crc_ok; l.sample = r.sample;
-        l.text_off = (uint32_t)c->text.size(); l.text_len = r.len;
-        c->text.append(parts[r.part].text, r.off, r.len);
-        c->lines.push_back(l);
-    }
-    c->tim.host_decode_ms = (float)(now_ms() - t0);
-    if (const uint32_t sb = c->short_burst.load()) {       /* formatted once, after the pool has joined */
-        const WmBurstHdr &h = c->h_hdr[sb - 1u];
-        return fail(c, WMBUS_EDEVICE, "burst too short: stream %u chain %u algo %u chip %u", h.stream, h.chain, h.algo, h.chip0);
-    }
     return WMBUS_OK;
 }
 
@@ -1660,9 +1376,9 @@ long wmbus_read_chips(wmbus_ctx *c, int chain, int algo, unsigned stream, uint32
     }
     /* a context without debug views computes the RSSI only in the tiles a packet decoder reads (RSSI on demand): elsewhere its rows hold
      * nothing, so this view shows 0 there instead of what an earlier push left */
-    hipLaunchKernelGGL(k4_flatten, dim3(1), dim3(1), 0, c->stream, c->last, (uint32_t)algo, c->d_chips[algo], c->d_counts[algo],
+    hipLaunchKernelGGL(k4_flatten, dim3(1), dim3(1), 0, c->stream, c->last, (uint32_t)algo, c->fr[algo].d_chips, c->fr[algo].d_counts,
                        /* no RSSI row where the last push computed it on demand only (a paused or fallen-back push ran the full pass: the row is valid) */
-                       c->rs_this && !c->rs_full_now ? (const uint8_t *)nullptr : c->d_rssi, c->cap[algo], (uint32_t)chain, stream, d_dst, d_pos, (uint32_t)max_elems, d_n);
+                       c->rs_this && !c->rs_full_now ? (const uint8_t *)nullptr : c->d_rssi, c->fr[algo].cap, (uint32_t)chain, stream, d_dst, d_pos, (uint32_t)max_elems, d_n);
     uint32_t n = 0;
     hipStreamSynchronize(c->stream);
     hipMemcpy(&n, d_n, 4, hipMemcpyDeviceToHost);
