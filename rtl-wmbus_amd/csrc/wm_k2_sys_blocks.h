@@ -1,5 +1,5 @@
-/* wm_k2_sys_blocks.h -- the clock-recovery cascade of wm_k2_clock.h cut into ROLES, one wave each (round 6).
- * Device code, included by wm_k2_clock_sys.h (and by tools/sysbench.hip, tests/emu/clock_emu.cpp).
+/* wm_k2_sys_blocks.h -- the clock-recovery cascade (wm_k2_clock_lane.h: clk_step) cut into ROLES, one wave each (round 6).
+ * Device code, included by wm_k2_clock_sys.h (and by tools/clkbench.hip).
  *
  * One wave that carries [DC remover] -> x^2 -> three biquads -> level for its 64 lanes issues 27 VALU instructions per sample,
  * and a wave alone on its SIMD issues one instruction every 4.8 cycles whatever their dependences (tools/lone_wave.hip,
@@ -19,6 +19,8 @@
 #ifndef WM_K2_SYS_BLOCKS_H
 #define WM_K2_SYS_BLOCKS_H
 
+#include "wm_k2_clock_lane.h"
+
 /* A hop buffer holds 32 samples of 64 lanes, sample-quad major: the four samples 4q .. 4q+3 of lane l are the 16 bytes at word
  * (q * 64 + l) * 4 -- a wave's ds_write_b128 / ds_read_b128 covers 1024 consecutive bytes, bank-conflict free.  ONE buffer per hop:
  * a step of the pipeline is  [every role reads its whole input block into registers] barrier [compute, write the output block] barrier,
@@ -34,18 +36,8 @@ __device__ __forceinline__ void sys_hop_read(const float *hop, wm_f4 (&in)[8])
     for (int q = 0; q < 8; q++) in[q] = *(const wm_f4 *)(hop + WM_SYS_HOP_Q * q);
 }
 
-/* one sample through section K (iir.h:57-74; b0 == 1) */
-template <int K>
-__device__ __forceinline__ float sys_biquad(float v, float &h1, float &h2, const IirCoef &c)
-{
-    const float h0 = wm_sub(v, wm_add(wm_mul(c.a1[K], h1), wm_mul(c.a2[K], h2)));
-    const float o = wm_add(wm_add(h0, wm_mul(c.b1[K], h1)), wm_mul(c.b2[K], h2));
-    h2 = h1; h1 = h0;
-    return o;
-}
-
 /* role 0: 32 soft symbols of this lane -> output of section 0 (hop, already offset by 4 * lane).  WARM: a warm-up block whose slicer
- * bits nobody reads (clk_block32's WARM). */
+ * bits nobody reads (clk_warm_short). */
 template <bool DC, bool WARM>
 __device__ __forceinline__ void sys_r0_block32(float &h1, float &h2, float &dcx, float &dcy, const IirCoef &c, const wm_f4 (&x)[8], float *hop, uint32_t &bitw)
 {
@@ -59,7 +51,7 @@ __device__ __forceinline__ void sys_r0_block32(float &h1, float &h2, float &dcx,
             float v = x[q][k];
             if (DC) { const float y = wm_add(wm_mul(kk, wm_sub(v, dcx)), wm_mul(al, dcy)); dcx = v; dcy = y; v = y; }   /* rtl_wmbus.c:501/511 */
             if (!WARM) sgn = __builtin_amdgcn_alignbit(sgn, wm_f2u(v), 31);                                      /* (sgn << 1) | signbit */
-            o[k] = sys_biquad<0>(wm_mul(v, v), h1, h2, c);
+            o[k] = clk_biquad<0>(wm_mul(v, v), h1, h2, c);
         }
         *(wm_f4 *)(hop + WM_SYS_HOP_Q * q) = o;
     }
@@ -73,14 +65,15 @@ __device__ __forceinline__ void sys_r1_block32(float &h1, float &h2, const IirCo
     for (int q = 0; q < 8; q++) {
         wm_f4 o;
 #pragma unroll
-        for (int k = 0; k < 4; k++) o[k] = sys_biquad<1>(in[q][k], h1, h2, c);
+        for (int k = 0; k < 4; k++) o[k] = clk_biquad<1>(in[q][k], h1, h2, c);
         *(wm_f4 *)(hout + WM_SYS_HOP_Q * q) = o;
     }
 }
 
 /* role 2: output of section 1 -> section 2 -> clock levels of the block -> sample mask of the clock lock (rtl_wmbus.c:1092-1111: take the
  * bit at n iff the levels at n-3 .. n are L,H,H,H); clk = the last three levels, newest in bit 0 (WmClkState.clk).  WARM: a warm-up block
- * whose chips nobody looks at: the section's recurrence only (no output, no level; clk is not touched), as clk_block32's WARM. */
+ * whose chips nobody looks at (clk_warm_short): the section's recurrence only -- its output is not used, so the feed-forward half and the
+ * level fall away --, clk is not touched. */
 template <bool WARM>
 __device__ __forceinline__ void sys_r2_block32(float &h1, float &h2, uint32_t &clk, const IirCoef &c, const wm_f4 (&in)[8], uint32_t &smask)
 {
@@ -89,18 +82,12 @@ __device__ __forceinline__ void sys_r2_block32(float &h1, float &h2, uint32_t &c
     for (int q = 0; q < 8; q++) {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            if (WARM) {
-                const float h0 = wm_sub(in[q][k], wm_add(wm_mul(c.a1[2], h1), wm_mul(c.a2[2], h2)));
-                h2 = h1; h1 = h0;
-            } else low = wm_shift_in_level_low(low, wm_f2u(sys_biquad<2>(in[q][k], h1, h2, c)));
+            const float o = clk_biquad<2>(in[q][k], h1, h2, c);
+            if (!WARM) low = wm_shift_in_level_low(low, wm_f2u(o));
         }
     }
     if (WARM) { smask = 0u; return; }
-    const uint32_t prev3 = ((clk & 1u) << 2) | (clk & 2u) | ((clk >> 2) & 1u);
-    const uint64_t H = ((uint64_t)(~__builtin_bitreverse32(low)) << 3) | prev3;           /* bit n+3 = level at n */
-    smask = (uint32_t)((~H) & (H >> 1) & (H >> 2) & (H >> 3));
-    const uint32_t last3 = (uint32_t)(H >> 32) & 7u;                                        /* levels at 29, 30, 31 */
-    clk = ((last3 & 1u) << 2) | (last3 & 2u) | ((last3 >> 2) & 1u);
+    smask = clk_lock_mask(low, clk);
 }
 
 /* the block-wide meeting point between two steps of the pipeline: LDS traffic of this wave done, NOT its global loads (role 1 keeps

@@ -21,7 +21,7 @@ F_DC, F_T1C1, F_S1, F_T2A = 4, 8, 16, 64                   # WM_F_* of wm_dev.h
 
 @pytest.fixture(scope="module")
 def emu():
-    deps = [SRC, os.path.join(HERE, "emu", "block_emu.h")] + [os.path.join(CSRC, f) for f in ("wm_k2_clock.h", "wm_k2_clock_sys.h", "wm_k2_sys_blocks.h", "wm_k2_common.h", "wm_dev.h", "wm_exact.h")]
+    deps = [SRC, os.path.join(HERE, "emu", "block_emu.h")] + [os.path.join(CSRC, f) for f in ("wm_k2_clock_lane.h", "wm_k2_clock.h", "wm_k2_clock_sys.h", "wm_k2_sys_blocks.h", "wm_k2_common.h", "wm_dev.h", "wm_exact.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC, "-I" + os.path.join(HERE, "emu"),
                         "-Wno-unknown-pragmas", "-o", SO, SRC], check=True)

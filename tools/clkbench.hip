@@ -1,7 +1,7 @@
 // clkbench.hip -- one lane-group (64 lanes) of the clock-recovery cascade: how long does a 32-sample block take
 //   ONE   as one wave carrying the whole cascade (clk_block32, wm_k2_clock.h: 27 instructions per sample; blocks of 4 independent waves), or
-//   SYS   as four waves of a block, one per SIMD, each a quarter of the cascade, hops through LDS, one s_barrier per block
-//         (wm_k2_sys_blocks.h; round 6)
+//   SYS   as four waves of a block, one per SIMD, the roles of wm_k2_sys_blocks.h (a section each, the chips in the fourth), hops through
+//         LDS, two s_barriers per block (round 6)
 // at 1 / 2 / 4 lane-groups per SIMD-quad of the chip (256 / 512 / 1024 lane-groups), alone and beside a background kernel shaped like the
 // demodulation kernel's first pass (512-thread blocks, 64 VGPRs, 35 KB LDS, dense VALU): the clock launch's own duration and what
 // it costs the background.  Soft symbols are read the way the product's re-run lanes read them (lane-private 16-byte loads, two
@@ -19,17 +19,10 @@ using std::min;
 #include "wm_k2_clock.h"
 #include "wm_k2_sys_blocks.h"
 
+/* the product's shift-register upkeep loop (T1/C1 access code) */
 __device__ __forceinline__ uint32_t chip_loop(uint32_t smask, uint32_t bitw, uint32_t sr)
 {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const bool has = smask != 0u;
-        if (__ballot(has) == 0ull) break;
-        const uint32_t k = has ? (uint32_t)__ffs((int)smask) - 1u : 0u;
-        smask &= smask - 1u;
-        const uint32_t sr_new = ((sr << 1) | ((bitw >> k) & 1u)) & 0xFFFFu;
-        sr = has ? sr_new : sr;
-    }
+    clk_warm_chips(sr, smask, bitw, ClkSync{WM_SYNC_T1C1, WM_SYNC_T1C1_MASK, true}, 0u);
     return sr;
 }
 
@@ -71,9 +64,10 @@ template <int PRIO> __global__ __launch_bounds__(256) void k_one(const float *x,
 // ---- SYS: four roles ---------------------------------------------------------------------------------------------
 struct SysLds {
     float x[64 * WM_CLK_XROW];
-    float hop[3][WM_SYS_HOP_WORDS];
+    float hop[2][WM_SYS_HOP_WORDS];
     uint32_t bitw[4][64];
-    uint32_t rest[3 * 1024 + 512];        /* what the product's block carries besides: chip and slicer-word staging, state snapshots, control words (47.9 KB in all) */
+    uint32_t smask[64];
+    uint32_t rest[3 * 1024 - 256];        /* what the product's block carries besides: chip and slicer-word staging, state snapshots, control words (sizeof(ClkSysLds) in all) */
 };
 
 // stats (optional): per wave {HW_ID, cycles before the first barrier of a step (input reads), between the barriers (work), at the second barrier}
@@ -113,11 +107,9 @@ template <int PRIO> __global__ __launch_bounds__(256) void k_sys(const float *x,
             }
             wm_sys_barrier(); mark(cb);
             if (b < nblk) {
-                uint32_t sgn = 0;
-                const wm_f4 (&lo)[4] = *(const wm_f4 (*)[4])&in[0], (&hi)[4] = *(const wm_f4 (*)[4])&in[4];
-                sys_r0_half16<false, false, 0>(h1, h2, dcx, dcy, c, lo, lds.hop[0] + 4u * ln, sgn);
-                sys_r0_half16<false, false, 1>(h1, h2, dcx, dcy, c, hi, lds.hop[0] + 4u * ln, sgn);
-                lds.bitw[b & 3u][ln] = ~__builtin_bitreverse32(sgn);
+                uint32_t bitw;
+                sys_r0_block32<false, false>(h1, h2, dcx, dcy, c, in, lds.hop[0] + 4u * ln, bitw);
+                lds.bitw[b & 3u][ln] = bitw;
             }
             mark(cw); wm_sys_barrier(); mark(cb); b++;
         };
@@ -125,42 +117,38 @@ template <int PRIO> __global__ __launch_bounds__(256) void k_sys(const float *x,
         while (b < nblk + 3u) { block(gxA); if (b < nblk + 3u) block(gxB); }
         acc = wm_f2u(h1);
     } else if (role == 1) {
-        float g1 = 0, g2 = 0, h1 = 0, h2 = 0;
+        float h1 = 0, h2 = 0;
         for (uint32_t s = 0; s < nblk + 3u; s++) {
             const uint32_t b = s - 1u;
             wm_f4 in[8];
             if (b < nblk) sys_hop_read(lds.hop[0] + 4u * ln, in);
             wm_sys_barrier(); mark(cb);
-            if (b < nblk) { sys_mid_block32<1>(g1, g2, h1, h2, c, in, lds.hop[1] + 4u * ln); acc += lds.bitw[b & 3u][ln]; }
+            if (b < nblk) { sys_r1_block32(h1, h2, c, in, lds.hop[1] + 4u * ln); acc += lds.bitw[b & 3u][ln]; }
             mark(cw); wm_sys_barrier(); mark(cb);
         }
         acc += wm_f2u(h1);
     } else if (role == 2) {
-        float g1 = 0, g2 = 0, h1 = 0, h2 = 0;
+        float h1 = 0, h2 = 0; uint32_t clk = 0;
         for (uint32_t s = 0; s < nblk + 3u; s++) {
             const uint32_t b = s - 2u;
             wm_f4 in[8];
             if (b < nblk) sys_hop_read(lds.hop[1] + 4u * ln, in);
             wm_sys_barrier(); mark(cb);
-            if (b < nblk) sys_mid_block32<2>(g1, g2, h1, h2, c, in, lds.hop[2] + 4u * ln);
+            if (b < nblk) { uint32_t smask; sys_r2_block32<false>(h1, h2, clk, c, in, smask); lds.smask[ln] = smask; }
             mark(cw); wm_sys_barrier(); mark(cb);
         }
-        acc = wm_f2u(h1);
+        acc = wm_f2u(h1) + clk;
     } else {
-        float g1 = 0, g2 = 0; uint32_t clk = 0, sr = 0;
+        uint32_t sr = 0;
         for (uint32_t s = 0; s < nblk + 3u; s++) {
             const uint32_t b = s - 3u;
-            wm_f4 in[8];
-            if (b < nblk) sys_hop_read(lds.hop[2] + 4u * ln, in);
+            uint32_t smask = 0, bitw = 0;
+            if (b < nblk) { smask = lds.smask[ln]; bitw = lds.bitw[b & 3u][ln]; }
             wm_sys_barrier(); mark(cb);
-            if (b < nblk) {
-                uint32_t smask;
-                sys_r3_block32(g1, g2, clk, c, in, smask);
-                sr = chip_loop(smask, lds.bitw[b & 3u][ln], sr);
-            }
+            if (b < nblk) sr = chip_loop(smask, bitw, sr);
             mark(cw); wm_sys_barrier(); mark(cb);
         }
-        acc = sr + clk + lds.rest[ln];
+        acc = sr + lds.rest[ln];
     }
     out[(group * 4 + role) * 64 + ln] = acc;
     if (stats && ln == 0) {
