@@ -118,6 +118,14 @@ typedef struct wmbus_cfg {
      * the reference drops a partial block.  wmbus_line.sample counts decimated samples of the resampled stream.  A rate equal to
      * decimation x 800 kHz is the same as 0. */
     unsigned input_rate_hz;
+    /* 0 (default): the channel the pipeline expects (868.95 MHz, or 868.625 MHz with cfg.simultaneous) is the centre of the capture, as
+     * the reference demands.  Otherwise the offset in Hz, signed, from the capture's centre to that channel: a capture tuned to 868.70 MHz
+     * is decoded with input_shift_hz = 250000.  The context multiplies the input by e^(-j 2 pi f m / Fin) on the GPU -- inside the resampler
+     * or the conversion kernel, where the samples are staged -- with the exact integer arithmetic defined below next to
+     * wmbus_shift_design().  |f| <= Fin / 2, Fin = input_rate_hz (decimation x 800000 if 0).  A shift alone switches the conversion
+     * kernel on: everything said below about raw bytes, whole blocks and the clip count then holds for a cu8 capture as well.  0 is in
+     * every respect the context without this field. */
+    int input_shift_hz;
     /* Sample format of the input, WMBUS_FMT_* (0 = cu8, what an RTL-SDR delivers and the reference reads), and a linear input gain in
      * Q8, 1 ... 65535 = x 1/256 ... x 256 (0 means 256 = x 1).  The arithmetic is defined below, next to wmbus_resampler_design().
      * With a format other than cu8 or a gain other than x 1 the context converts on the GPU, inside the resampler where cfg.input_rate_hz
@@ -167,7 +175,7 @@ typedef struct wmbus_timing {
     unsigned rssi_mode;         /* WMBUS_RSSI_*: how this push got its RSSI */
     unsigned rssi_tiles;        /* RSSI on demand: (tile, capture) pairs listed in this push */
     unsigned clock_round[4], rla_round[4];   /* segments re-run in the unattended rounds, round by round (beyond the rounds enqueued: 0) */
-    /* a context that resamples or converts (cfg.input_rate_hz, input_format, input_gain_q8): the cu8 bytes this push's input became,
+    /* a context that resamples, shifts or converts (cfg.input_rate_hz, input_shift_hz, input_format, input_gain_q8): the cu8 bytes this push's input became,
      * all streams (whether the pipeline took them in this push or they wait for the next block to fill), and how many of them the
      * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path. */
     uint64_t input_bytes_out, input_clipped;
@@ -277,11 +285,31 @@ long wmbus_debug_replay_decode(wmbus_ctx *ctx, unsigned reps, double *seconds);
  *     byte = clamp((acc + 255 * 16384 + 16384) >> 15, 0, 255)
  * and exists once input floor(n * M / L) has been pushed: integers only, so the bytes do not depend on how the input is cut into pushes. */
 int  wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsigned *M, unsigned *T, int16_t *taps, size_t cap);
-/* Debug read (requires cfg.keep_taps and a context that resamples or converts: cfg.input_rate_hz, input_format, input_gain_q8): the
+/* FREQUENCY SHIFT (cfg.input_shift_hz = f, signed Hz; tests/shift_ref.py restates it in numpy): input sample m of the stream (m counts
+ * from the stream's first sample over all pushes, 64 bits) is multiplied by e^(-j 2 pi f m / Fin), Fin = cfg.input_rate_hz or
+ * decimation x 800000, in integers:
+ *     step  = floor((f * 2^32 + Fin / 2) / Fin) mod 2^32         (floor division, also for f < 0; 64-bit)
+ *     phase = (step * m) mod 2^32                                (a function of m alone: nothing is accumulated across pushes)
+ *     i     = ((phase + 2^21) mod 2^32) >> 22                    (10 bits, rounded; 1024 wraps to 0)
+ *     c[i]  = rint(16384 cos(2 pi i / 1024)),  s[i] = rint(16384 sin(2 pi i / 1024))       (computed in double, stored as int16)
+ *     yi = clamp((xi c + xq s + 8192) >> 14, -32768, 32767),  yq = clamp((xq c - xi s + 8192) >> 14, -32768, 32767)     (int32, >> floors)
+ * With a shift cu8 and cs8 samples are 16 bits wide before the rotation, so that its rounding costs nothing: x = 64 (2 u - 255),
+ * x = 64 (2 s + 1), F = 21 (|x| <= 16320, |x| sqrt 2 < 32768); cs16 and cf32 keep x and F = 22.  y takes the place of x in everything
+ * above: the resampler's sum (history before the stream: y = 0; the history carried between pushes holds rotated samples) or
+ * acc = 16384 y, then the gain and the clamp with that F.  |acc| <= 32768 * sum|taps| < 2^31 is checked for every format when a
+ * context with a shift is opened.  Only integers follow the one rounding of cf32: the bytes do not depend on tile, block or push
+ * boundaries.  Without a shift nothing changes.
+ *
+ * Host only, no device needed: the step, and (table may be NULL; cap = its int16 capacity, >= 2048) the 1024 entries {c[i], s[i]};
+ * entry i + 256 is {-s[i], c[i]}.  WMBUS_EINVAL for |shift_hz| > in_hz / 2 or in_hz < 800000. */
+int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *table, size_t cap);
+/* Debug read (requires cfg.keep_taps and a context that resamples, converts or shifts: cfg.input_rate_hz, input_shift_hz, input_format,
+ * input_gain_q8): the
  * cu8 bytes the last push handed to the pipeline for one stream.  Returns the number of bytes written (0 for a push that completed no
  * block), or a negative error. */
 long wmbus_read_resampled(wmbus_ctx *ctx, unsigned stream, uint8_t *out, size_t cap);
-/* Pushes of this context that launched the resampler or the conversion kernel (0 for ever on the plain cu8 path). */
+/* Pushes of this context that launched the resampler or the conversion kernel (0 for ever on the plain cu8 path, which a context
+ * with cfg.input_shift_hz = 0 and nothing else set is). */
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx);
 
 /* Number of visible HIP devices (0 if none). */

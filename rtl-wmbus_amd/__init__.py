@@ -47,7 +47,7 @@ class Cfg(ctypes.Structure):
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
-                ("input_rate_hz", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
+                ("input_rate_hz", ctypes.c_uint), ("input_shift_hz", ctypes.c_int), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
 
 
 class Line(ctypes.Structure):
@@ -100,7 +100,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
-           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches"]
+           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design"]
 
 _lib = None
 
@@ -129,6 +129,7 @@ def lib():
         L.wmbus_read_chips.argtypes = [vp, ctypes.c_int, ctypes.c_int, u, vp, vp, sz]; L.wmbus_read_chips.restype = ctypes.c_long
         L.wmbus_device_count.restype = ctypes.c_int
         L.wmbus_resampler_design.argtypes = [u, u, ctypes.POINTER(u), ctypes.POINTER(u), ctypes.POINTER(u), vp, sz]
+        L.wmbus_shift_design.argtypes = [u, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), vp, sz]
         L.wmbus_read_resampled.argtypes = [vp, u, vp, sz]; L.wmbus_read_resampled.restype = ctypes.c_long
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
@@ -165,6 +166,17 @@ def resampler_design(in_hz, out_hz):
     if rc:
         raise WmbusError(f"wmbus_resampler_design({in_hz}, {out_hz}) failed: {rc}")
     return L_.value, M_.value, T_.value, taps
+
+
+def shift_design(in_hz, shift_hz):
+    """wmbus_shift_design (host only): (step, table int16 [1024, 2] of {c, s}) of the exact integer frequency shift behind
+    Receiver(input_shift_hz=...); raises WmbusError for a shift beyond half the input rate."""
+    step = ctypes.c_uint32()
+    table = np.zeros((1024, 2), np.int16)
+    rc = lib().wmbus_shift_design(int(in_hz), int(shift_hz), ctypes.byref(step), table.ctypes.data, table.size)
+    if rc:
+        raise WmbusError(f"wmbus_shift_design({in_hz}, {shift_hz}) failed: {rc}")
+    return step.value, table
 
 
 def pinned_array(nbytes):
@@ -208,7 +220,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
-              input_rate_hz=0, input_format=0, input_gain_q8=0):
+              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -229,6 +241,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_rate_hz = int(input_rate_hz)     # 0: the input is at decimation x 800 kHz; else the library resamples it on the GPU
     # raw sample format (FMT_*) and linear gain in Q8 (0: x 1); stage / process / max_push_bytes then count RAW bytes
     c.input_format, c.input_gain_q8 = int(input_format), int(input_gain_q8)
+    c.input_shift_hz = int(input_shift_hz)   # signed Hz from the capture's centre to the channel (0: the capture is centred on it)
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
     return c

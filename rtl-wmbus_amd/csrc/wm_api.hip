@@ -91,14 +91,16 @@ struct wmbus_ctx {
     Owned mem;
     uint64_t in_stride = 0, n0 = 0;
     size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
-    /* cfg.input_rate_hz / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) -- the resampler
-     * (`resample`), which also reads every format and applies the gain, or for an input at the native rate the conversion kernel
-     * alone (L = M = 1, no taps, no history).  wmbus_stage fills the RAW windows; K0
+    /* cfg.input_rate_hz / input_shift_hz / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) --
+     * the resampler (`resample`), which also reads every format, rotates (`shift`) and applies the gain, or for an input at the native
+     * rate the conversion kernel alone (L = M = 1, no taps, no history).  wmbus_stage fills the RAW windows; K0
      * writes the window of d_in the pipeline reads.  hist / rem are double-buffered like every carried state (a push reads half
      * `cur`, writes the other).  Every capture advances in lock step, so the counters live here and travel as launch arguments. */
     struct {
-        bool on = false, resample = false;
+        bool on = false, resample = false, shift = false;  /* shift: cfg.input_shift_hz != 0, the rotating instantiations of either kernel */
         uint32_t fmt = WMBUS_FMT_CU8, bps = 2, gain = 0;   /* cfg.input_format, its raw bytes per sample, cfg.input_gain_q8 */
+        uint32_t step = 0;                             /* the shift's phase advance per input sample (k0_shift_design) */
+        uint32_t *d_shift_tab = nullptr;               /* [1024] {c, s} int16 */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
         uint64_t raw_stride = 0;
         uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
@@ -388,6 +390,11 @@ int wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsigne
     return k0_design(in_hz, out_hz, L, M, T, taps, cap) ? WMBUS_EINVAL : WMBUS_OK;
 }
 
+int wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *table, size_t cap)
+{
+    return k0_shift_design(in_hz, shift_hz, step, table, cap) ? WMBUS_EINVAL : WMBUS_OK;
+}
+
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx) { return ctx ? ctx->k0.launches : 0ull; }
 
 const char *wmbus_last_error(const wmbus_ctx *ctx) { return ctx ? ctx->err : "null context"; }
@@ -412,7 +419,7 @@ void wmbus_close(wmbus_ctx *c)
 }
 
 /* wmbus_open, step 1: is the configuration one the library takes, and is its device there?  Designs the resampler on the way (a rate
- * without a design is a refusal); `k0_taps` keeps its taps for open_init. */
+ * without a design is a refusal; `k0_taps` keeps its taps for open_init) and the phase step of cfg.input_shift_hz. */
 static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
 {
     const wmbus_cfg *cfg = &c->cfg;
@@ -430,13 +437,19 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     if (cfg->input_gain_q8 > 65535u) return fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8);
     auto &k = c->k0;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
+    if (cfg->input_shift_hz) {
+        const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+        const char *why = k0_shift_design(fin, cfg->input_shift_hz, &k.step, nullptr, 0);
+        if (why) return fail(c, WMBUS_EINVAL, "%s (input_shift_hz = %d, limit +-%u at the input rate %u)", why, cfg->input_shift_hz, fin / 2u, fin);
+        k.shift = true;
+    }
     if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
         unsigned L = 0, M = 0, T = 0;
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
         const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
         if (why) return fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u);
-        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32)
-            for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples: |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
+        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32 || k.shift)
+            for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples (a shifted cu8 / cs8 sample is one): |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
                 int64_t abs_total = 0;
                 for (unsigned t = 0; t < T; t++) abs_total += std::abs((int)k0_taps[(size_t)p * T + t]);
                 if (32768ll * abs_total >= (1ll << 31)) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's accumulator bound for 16-bit input is exceeded (phase %u)", p);
@@ -445,8 +458,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k.tile = k0_pick_tile(L, M, T);
         if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
         k.lds = k0_lds_bytes(L, M, T, k.tile);
-    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u)) {
-        /* the native rate in another format or with a gain: the conversion kernel alone */
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift) {
+        /* the native rate in another format, with a gain or with a shift: the conversion kernel alone */
         k.on = true; k.L = k.M = k.T = 1u;
         k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
@@ -584,6 +597,7 @@ static int open_allocate(wmbus_ctx *c)
             A(m.dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
         }
         A(m.dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
+        if (c->k0.shift) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -648,6 +662,12 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
         A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     }
+    std::vector<int16_t> shift_tab;
+    if (c->k0.shift) {                                       /* {c, s} per entry: the dword the kernels read */
+        shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
+        k0_shift_design(800000u, 0, nullptr, shift_tab.data(), shift_tab.size());
+        A(hipMemcpyAsync(c->k0.d_shift_tab, shift_tab.data(), shift_tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    }
     A(hipMemsetAsync(c->d_ema_carry, 0, 2 * rows * sizeof(float), c->stream));
     /* a disabled chain (-p T / -p S) never writes its hand-off records: they must compare equal, not hold what an
      * earlier context left in the recycled allocation */
@@ -670,7 +690,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         lut[32 * WM_MAX_DECIM + n] = -sinf(phi);
     }
     A(hipMemcpyAsync(c->d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    A(hipStreamSynchronize(c->stream));                      /* k0_taps, init and lut leave with this function */
+    A(hipStreamSynchronize(c->stream));                      /* k0_taps, shift_tab, init and lut leave with this function */
     if (e != hipSuccess) return fail(c, WMBUS_EDEVICE, "initialisation failed: %s", hipGetErrorString(e));
 
     c->decs.resize((size_t)c->S * 4);                        /* [stream][chain][algo] */
@@ -910,6 +930,7 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     ka->rem_prev = k.rem; ka->keep_from = (uint32_t)whole;
     ka->L = k.L; ka->M = k.M; ka->T = k.T; ka->tile = k.tile;
     ka->gain_q8 = k.gain; ka->clipped = c->d_scalars + SC_CLIP;
+    ka->step = k.step; ka->shift_tab = k.d_shift_tab;
     k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
     k.last_bytes = whole; k.last_win = c->fill;
@@ -918,9 +939,12 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
-    void (*const resample[4])(K0Args) = {k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>};
-    void (*const convert[4])(K0Args) = {k0_convert<WM_K0_CU8>, k0_convert<WM_K0_CS8>, k0_convert<WM_K0_CS16>, k0_convert<WM_K0_CF32>};      /* [WMBUS_FMT_*] */
-    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
+    /* [cfg.input_shift_hz != 0][WMBUS_FMT_*] */
+    void (*const resample[2][4])(K0Args) = {{k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>},
+                                            {k0_resample_shift<WM_K0_CU8>, k0_resample_shift<WM_K0_CS8>, k0_resample_shift<WM_K0_CS16>, k0_resample_shift<WM_K0_CF32>}};
+    void (*const convert[2][4])(K0Args) = {{k0_convert<WM_K0_CU8>, k0_convert<WM_K0_CS8>, k0_convert<WM_K0_CS16>, k0_convert<WM_K0_CF32>},
+                                           {k0_convert_shift<WM_K0_CU8>, k0_convert_shift<WM_K0_CS8>, k0_convert_shift<WM_K0_CS16>, k0_convert_shift<WM_K0_CF32>}};
+    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
                        c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
@@ -1356,7 +1380,7 @@ long wmbus_read_tap(wmbus_ctx *c, const char *what, int chain, unsigned stream, 
 long wmbus_read_resampled(wmbus_ctx *c, unsigned stream, uint8_t *out, size_t cap)
 {
     if (!c || !out || stream >= c->S) return WMBUS_EINVAL;
-    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples or converts (cfg.input_rate_hz, input_format, input_gain_q8)");
+    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples, converts or shifts (cfg.input_rate_hz, input_shift_hz, input_format, input_gain_q8)");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_resampled: collect the push first");
     const size_t n = std::min(cap, c->k0.last_bytes);
     HIPCHK(c, hipSetDevice(c->cfg.device));

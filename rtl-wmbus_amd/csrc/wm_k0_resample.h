@@ -32,6 +32,14 @@
  * k0_convert_block is the same stage for an input that is already at decimation x 800 kHz (acc = 16384 x): no taps, no LDS span,
  * 16 raw bytes per lane and load, the same remainder / keep_from hand-over.  Both count the bytes the clamp changed (K0Args.clipped):
  * per lane in a register, per block in LDS, one atomic add per block.
+ *
+ * Frequency shift (cfg.input_shift_hz; the contract is in include/wmbus_hip.h): the second template parameter SH of both block
+ * functions.  Every input sample is rotated ONCE, where it is staged -- behind k0_load2 in the loop that fills the LDS span and in
+ * the history hand-over (the carried history holds rotated samples), between the 16-byte load and k0_byte_g in k0_convert_block --
+ * by the table entry of its phase (step m) mod 2^32, m = in_first + its index within the push: a function of m alone, nothing
+ * carried.  One dword {c, s} per entry from the 4 KB table in global memory (K0Args.shift_tab; DESIGN.md section 4 says why not LDS),
+ * {-s, c} built from it with V_PERM_B32, one V_DOT2_I32_I16 per component.  cu8 / cs8 samples are widened to 64 x first and F is
+ * 21 instead of 15.  SH = false compiles to exactly the code there was: every line of the shift sits behind if constexpr (SH).
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -70,11 +78,14 @@ struct K0Args {
     /* sample formats and gain; all zero: cu8, gain x 1, nothing counted */
     uint32_t gain_q8;            /* cfg.input_gain_q8 (0: 256)                                                */
     uint32_t *clipped;           /* += output bytes the clamp changed in this push, all captures (NULL: not counted) */
+    /* frequency shift (the SH instantiations only); all zero: none */
+    uint32_t step;               /* phase advance per input sample, 2^32 = one turn                           */
+    const uint32_t *shift_tab;   /* [1024] {c, s} int16: rint(16384 cos / sin(2 pi i / 1024))                 */
 };
 
 /* raw bytes per sample; F + 8, the shift behind the gain product */
 __host__ __device__ constexpr uint32_t k0_bps(int fmt) { return fmt == WM_K0_CF32 ? 8u : fmt == WM_K0_CS16 ? 4u : 2u; }
-__host__ __device__ constexpr uint32_t k0_shift(int fmt) { return fmt == WM_K0_CS16 || fmt == WM_K0_CF32 ? 30u : 23u; }
+__host__ __device__ constexpr uint32_t k0_shift(int fmt, bool sh = false) { return fmt == WM_K0_CS16 || fmt == WM_K0_CF32 ? 30u : sh ? 29u : 23u; }
 
 struct alignas(8) K0U2 { uint32_t x, y; };
 struct alignas(16) K0U4 { uint32_t x, y, z, w; };
@@ -171,6 +182,30 @@ __device__ __forceinline__ uint32_t k0_hi_pair(uint32_t s0, uint32_t s1)
     return (s0 >> 16) | (s1 & 0xFFFF0000u);
 #endif
 }
+/* Frequency shift.  A cu8 / cs8 sample as k0_pack left it, both halves x 64 (|x| <= 16320: the rotation's rounding costs nothing) */
+__device__ __forceinline__ uint32_t k0_x64(uint32_t v) { return ((v << 6) & 0x0000FFC0u) | ((v & 0xFFFF0000u) << 6); }
+__device__ __forceinline__ int32_t k0_clamp16(int32_t v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
+/* {xi, xq} times e^(-j phase): the table entry {c, s} of the phase rounded to 10 bits (1024 wraps to 0), {-s, c} from it;
+ * yi = (xi c + xq s + 8192) >> 14, yq = (xq c - xi s + 8192) >> 14, each clamped to int16.  |x| (|c| + |s|) < 2^30: exact in int32 */
+__device__ __forceinline__ uint32_t k0_rotate(uint32_t x, uint32_t phase, const uint32_t *tab)
+{
+    const uint32_t cs = tab[(phase + (1u << 21)) >> 22];
+    const uint32_t sc = k0_lo_pair(0u - (cs >> 16), cs);
+    return k0_pair(k0_clamp16(k0_dot2(x, cs, 8192) >> 14), k0_clamp16(k0_dot2(x, sc, 8192) >> 14));
+}
+/* the staged sample v (as k0_load2 / k0_load1 left it) of stream index m, rotated */
+template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m)
+{
+    if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) v = k0_x64(v);
+    return k0_rotate(v, a.step * m, a.shift_tab);
+}
+/* sample k of the four dwords a lane of k0_convert_block loaded, as the {I, Q} int16 pair of the unshifted rules */
+template <int FMT> __device__ __forceinline__ uint32_t k0_sample_of(const uint32_t (&in)[4], uint32_t k)
+{
+    if constexpr (FMT == WM_K0_CS16) return in[k];
+    else if constexpr (FMT == WM_K0_CF32) return k0_pair(k0_f2x(in[2u * k]), k0_f2x(in[2u * k + 1u]));
+    else return k0_pack(((in[k / 2u] >> (16u * (k & 1u))) & 0xFFFFu) ^ (FMT == WM_K0_CS8 ? 0x8080u : 0u));
+}
 __device__ __forceinline__ uint32_t k0_byte(int32_t acc)
 {
     const int32_t v = (acc + WM_K0_OUT_BIAS) >> 15;
@@ -179,11 +214,11 @@ __device__ __forceinline__ uint32_t k0_byte(int32_t acc)
 
 /* the output stage of every format: g = 256 at F = 15 stays on the 32-bit line above (the branch is uniform); nclip counts the
  * values the clamp changed */
-template <int FMT> __device__ __forceinline__ uint32_t k0_byte_g(int32_t acc, uint32_t g, uint32_t &nclip)
+template <int FMT, bool SH = false> __device__ __forceinline__ uint32_t k0_byte_g(int32_t acc, uint32_t g, uint32_t &nclip)
 {
     int32_t v;
-    if (k0_shift(FMT) == 23u && g == 256u) v = (acc + WM_K0_OUT_BIAS) >> 15;
-    else v = (int32_t)(((int64_t)acc * (int64_t)g + ((int64_t)128 << k0_shift(FMT))) >> k0_shift(FMT));
+    if (k0_shift(FMT, SH) == 23u && g == 256u) v = (acc + WM_K0_OUT_BIAS) >> 15;
+    else v = (int32_t)(((int64_t)acc * (int64_t)g + ((int64_t)128 << k0_shift(FMT, SH))) >> k0_shift(FMT, SH));
     nclip += (v < 0 || v > 255) ? 1u : 0u;
     return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
@@ -218,7 +253,7 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
 }
 
 /* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
-template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
+template <int FMT, bool SH = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
     const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -248,6 +283,10 @@ template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0A
         if (r >= 0) {
             if (r < (int64_t)a.n_in) {                           /* n_in is even: r + 1 lies inside too */
                 k0_load2<FMT>(raw + BPS * (uint64_t)r, v0, v1);
+                if constexpr (SH) {                              /* only the low 32 bits of the stream index reach the phase */
+                    const uint32_t m = (uint32_t)a.in_first + (uint32_t)r;
+                    v0 = k0_shifted<FMT>(a, v0, m); v1 = k0_shifted<FMT>(a, v1, m + 1u);
+                }
             }
         } else {                                                 /* r <= -2: both samples are history (the oldest slot, index -T, is never read) */
             const int64_t h = r + (int64_t)(T - 1u);
@@ -267,7 +306,9 @@ template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0A
         uint32_t *hist_out = a.hist_out + (uint64_t)s * (T - 1u);
         for (uint32_t j = tid; j < T - 1u; j += nthr) {
             const uint32_t r = a.n_in - (T - 1u) + j;
-            hist_out[j] = k0_load1<FMT>(raw + BPS * (uint64_t)r);
+            uint32_t v = k0_load1<FMT>(raw + BPS * (uint64_t)r);
+            if constexpr (SH) v = k0_shifted<FMT>(a, v, (uint32_t)a.in_first + r);
+            hist_out[j] = v;
         }
         k0_carry_rem(a, s, out);
     }
@@ -296,7 +337,7 @@ template <int FMT> __device__ __forceinline__ void k0_resample_block_t(const K0A
 #pragma unroll
         for (uint32_t i = 0; i < WM_K0_OPL; i++) {
             const uint32_t t = t0 + i * L;
-            if (t < ntile) ob[t] = (uint16_t)(k0_byte_g<FMT>(ai[i], gain, nclip) | (k0_byte_g<FMT>(aq[i], gain, nclip) << 8));
+            if (t < ntile) ob[t] = (uint16_t)(k0_byte_g<FMT, SH>(ai[i], gain, nclip) | (k0_byte_g<FMT, SH>(aq[i], gain, nclip) << 8));
         }
     }
     __syncthreads();
@@ -318,7 +359,7 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
  * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
  * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
  * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
-template <int FMT> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+template <int FMT, bool SH = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -344,7 +385,29 @@ template <int FMT> __device__ __forceinline__ void k0_convert_block(const K0Args
             const uint32_t o = a.rem_prev + 2u * (t_first + i);
             uint8_t *dst = o >= a.keep_from ? rout + (o - a.keep_from) : nullptr;
             const uint32_t in[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-            if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) {
+            if constexpr (SH) {                                  /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
+                const uint32_t m0 = (uint32_t)a.in_first + t_first + i;
+                uint32_t r[SPL / 2u];
+#pragma unroll
+                for (uint32_t k = 0; k < SPL; k++) {
+                    const uint32_t y = k0_shifted<FMT>(a, k0_sample_of<FMT>(in, k), m0 + k);
+                    const uint32_t pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
+                                          (k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), gain, nclip) << 8);
+                    r[k / 2u] = k & 1u ? r[k / 2u] | (pair << 16) : pair;
+                }
+                if constexpr (SPL == 8u) {
+                    const K0U4 y = {r[0], r[1], r[2], r[3]};
+                    *(K0U4 *)(out + o) = y;
+                    if (dst) *(K0U4 *)dst = y;
+                } else if constexpr (SPL == 4u) {
+                    const K0U2 y = {r[0], r[1]};
+                    *(K0U2 *)(out + o) = y;
+                    if (dst) *(K0U2 *)dst = y;
+                } else {
+                    *(uint32_t *)(out + o) = r[0];
+                    if (dst) *(uint32_t *)dst = r[0];
+                }
+            } else if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) {
                 uint32_t r[4];
 #pragma unroll
                 for (uint32_t k = 0; k < 4u; k++) {
@@ -394,6 +457,17 @@ template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert(K
 {
     __shared__ uint32_t word;
     k0_convert_block<FMT>(a, &word);
+}
+/* cfg.input_shift_hz: the same two stages with the rotation in their staging */
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_shift(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, true>(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_shift(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, true>(a, &word);
 }
 #endif
 

@@ -6,6 +6,8 @@
  *   k0_resample_fmt<cs8 | cs16 | cf32>  the same for cfg.input_format, with cfg.input_gain_q8 in the output stage;
  *   k0_convert<fmt>  the format / gain conversion alone for an input that is at decimation x 800 kHz already; both count the
  *                bytes their clamp changed (wmbus_timing.input_clipped).
+ *   k0_resample_shift<fmt> / k0_convert_shift<fmt>  the same two with cfg.input_shift_hz: every input sample rotated once, where it is
+ *                staged, by an exact integer rule (a capture tuned off the channel; no counterpart in the reference).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.

@@ -57,6 +57,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t   (output rate / input rate = L / M in lowest terms with L <= 32, M <= 1024; at least 800k; with -P only to 1.6 MS/s)\n");
     fprintf(stdout, "\t-I cu8|cs8|cs16|cf32 sample format of the input (default cu8; cs16 and cf32 little-endian, cf32 full scale +-1.0): converted on the GPU\n");
     fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
+    fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -346,6 +347,22 @@ static unsigned parse_rate(const char *arg)
     return (double)r - v * mul > 1e-3 || v * mul - (double)r > 1e-3 ? 0 : r;      /* a whole number of Hz */
 }
 
+/* -O: a signed rate, "-250k" | "1e5" | "0.25M" -> Hz; 0 is a valid answer, so *ok says whether it is one */
+static int parse_shift(const char *arg, int *ok)
+{
+    const int neg = arg[0] == '-';
+    *ok = 0;
+    if (arg[0] == '-' || arg[0] == '+') arg++;
+    if (arg[0] == '-' || arg[0] == '+') return 0;
+    char *end;
+    const double v = strtod(arg, &end);
+    if (end != arg && v == 0. && (!*end || ((*end == 'k' || *end == 'K' || *end == 'M' || *end == 'm') && !end[1]))) { *ok = 1; return 0; }
+    const unsigned hz = parse_rate(arg);
+    if (!hz || hz > 2147483647u) return 0;
+    *ok = 1;
+    return neg ? -(int)hz : (int)hz;
+}
+
 /* -I: the format's WMBUS_FMT_*, or -1 */
 static int parse_format(const char *arg)
 {
@@ -415,7 +432,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -457,6 +474,12 @@ int main(int argc, char **argv)
             cfg.input_format = (unsigned)f;
             break;
         }
+        case 'O': {
+            int ok;
+            cfg.input_shift_hz = parse_shift(optarg, &ok);
+            if (!ok) { print_usage(argv[0]); return EXIT_FAILURE; }
+            break;
+        }
         case 'g':
             cfg.input_gain_q8 = parse_gain_db(optarg);
             if (!cfg.input_gain_q8) { print_usage(argv[0]); return EXIT_FAILURE; }
@@ -477,6 +500,13 @@ int main(int argc, char **argv)
     /* -R: a ratio the resampler does not take is a bad option (usage text), decided here without a device */
     if (cfg.input_rate_hz && wmbus_resampler_design(cfg.input_rate_hz, cfg.decimation * 800000u, NULL, NULL, NULL, NULL, 0)) {
         print_usage(argv[0]);
+        return EXIT_FAILURE;
+    }
+
+    /* -O: beyond half the input rate is a bad option too */
+    if (cfg.input_shift_hz && wmbus_shift_design(cfg.input_rate_hz ? cfg.input_rate_hz : cfg.decimation * 800000u, cfg.input_shift_hz, NULL, NULL, 0)) {
+        fprintf(stderr, "rtl_wmbus_hip: -O %d: the offset must lie within +- half the input rate (%u Hz)\n", cfg.input_shift_hz,
+                (cfg.input_rate_hz ? cfg.input_rate_hz : cfg.decimation * 800000u) / 2u);
         return EXIT_FAILURE;
     }
 

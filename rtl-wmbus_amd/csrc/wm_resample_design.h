@@ -87,5 +87,28 @@ const char *k0_design(unsigned in_hz, unsigned out_hz, unsigned *pL, unsigned *p
     return nullptr;
 }
 
+/* The frequency shift of cfg.input_shift_hz (the arithmetic is in include/wmbus_hip.h): the phase step per input sample as a
+ * fraction of 2^32, rounded to nearest with floor division (also for a negative shift), and the 1024-entry table {c, s} =
+ * rint(16384 cos / sin(2 pi i / 1024)) in double.  0, or a message for WMBUS_EINVAL.  table may be NULL (the step only). */
+#define WM_K0_SHIFT_ENTRIES 1024u
+const char *k0_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *table, size_t cap)
+{
+    if (in_hz < 800000u) return "the input rate must be at least 800000";
+    const int64_t f = shift_hz, fin = in_hz;
+    if (2 * (f < 0 ? -f : f) > fin) return "input_shift_hz must lie within +- half the input rate";
+    const int64_t num = f * ((int64_t)1 << 32) + fin / 2;       /* |f| <= 2^31 - 1: inside int64 */
+    int64_t q = num / fin;
+    if (num % fin < 0) q--;                                      /* floor, not C's truncation */
+    if (step) *step = (uint32_t)(uint64_t)q;
+    if (!table) return nullptr;
+    if (cap < 2u * WM_K0_SHIFT_ENTRIES) return "shift design: table buffer too small";
+    for (unsigned i = 0; i < WM_K0_SHIFT_ENTRIES; i++) {
+        const double w = 2. * M_PI * (double)i / (double)WM_K0_SHIFT_ENTRIES;
+        table[2u * i] = (int16_t)rint(16384. * cos(w));
+        table[2u * i + 1u] = (int16_t)rint(16384. * sin(w));
+    }
+    return nullptr;
+}
+
 }  // namespace
 #endif

@@ -7,6 +7,11 @@ section 6: one box visit, interleaved).  Legs:
     parent-rs-cu8                      rs-cu8 on another build of the library (--parent-lib: the parent commit's), the A/B of the cu8 path
     native                             cu8 at 1.6 MS/s, no K0 stage at all
     cv-cu8 cv-cs8 cv-cs16 cv-cf32      1.6 MS/s in that format through the conversion kernel (cu8: gain 257 / 256, which switches it on)
+    rs25-cs16 (not in the default list) cs16 at 2.5 MS/s through the resampler
+    LEG+shift                          any leg but native / parent-*: the same with cfg.input_shift_hz = --shift-hz, i.e. the rotating
+                                       instantiation of its kernel (cv-cu8+shift: the shift alone switches the conversion kernel on, gain x 1).
+                                       The captures are NOT mixed up to match, so nothing decodes behind K0: read a +shift leg's K0 kernel
+                                       time below, not its job rate
 
 Prints one JSON line per leg and round: raw input Msamples/s, and the clipped share.  `--copy-bandwidth` also times a device-to-device
 copy of 1 GiB (hipMemcpyAsync; read + write bytes per second), the yardstick for the conversion kernel.  Needs a GPU.
@@ -38,6 +43,7 @@ ap.add_argument("--streams", type=int, default=128)
 ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic captures (the others repeat them)")
 ap.add_argument("--log2-samples", type=int, default=22)
 ap.add_argument("--parent-lib", default=None, help="libwmbus_hip.so of the parent commit (leg parent-rs-cu8; skipped without it)")
+ap.add_argument("--shift-hz", type=int, default=200000, help="cfg.input_shift_hz of the +shift legs")
 ap.add_argument("--copy-bandwidth", action="store_true")
 a = ap.parse_args()
 if wm.device_count() < 1:
@@ -45,9 +51,11 @@ if wm.device_count() < 1:
 
 
 def second_copy(lib_path):
-    """The package again, bound to another build of the library (the configuration's new fields lie behind the ones that build reads)."""
+    """The package again, bound to another build of the library (with the __init__.py of that build where one lies next to the
+    library: a build of another commit may miss exports this mirror binds, or lay wmbus_cfg out differently)."""
     os.environ["WMBUS_HIP_LIB"] = lib_path
-    spec = importlib.util.spec_from_file_location("wm_parent", os.path.join(ROOT, "rtl-wmbus_amd", "__init__.py"))
+    mirror = os.path.join(os.path.dirname(os.path.abspath(lib_path)), "__init__.py")      # that build's own ctypes mirror, if it lies beside it
+    spec = importlib.util.spec_from_file_location("wm_parent", mirror if os.path.exists(mirror) else os.path.join(ROOT, "rtl-wmbus_amd", "__init__.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     del os.environ["WMBUS_HIP_LIB"]
@@ -72,6 +80,8 @@ def capture(fs_khz, s, fmt):
 batches, meta = {}, {}
 for leg in a.legs.split(","):
     mod, kw, fs = wm, {}, 1600
+    shifted = leg.endswith("+shift")
+    leg_name, leg = leg, leg[:-len("+shift")] if shifted else leg
     if leg == "native":
         fmt = FR.CU8
     else:
@@ -79,18 +89,23 @@ for leg in a.legs.split(","):
         fmt = FMT[name]
         if kind.endswith("rs"):
             fs, kw = 2048, dict(input_rate_hz=2048000)
+        elif kind == "rs25":
+            fs, kw = 2500, dict(input_rate_hz=2500000)
         if kind == "parent-rs":
             if not a.parent_lib:
                 continue
             mod = second_copy(a.parent_lib)
         else:
-            gain = 64 * 256 if fmt in (FR.CS16, FR.CF32) else 257 if leg == "cv-cu8" else 0
+            gain = 64 * 256 if fmt in (FR.CS16, FR.CF32) else 257 if leg == "cv-cu8" and not shifted else 0
             kw.update(input_format=fmt, input_gain_q8=gain)
+            if shifted:
+                kw.update(input_shift_hz=a.shift_hz)
     bps = FR.BPS[fmt]
     b = mod.Batch(n_streams=a.streams, max_push_bytes=bps * n, **kw)
     for s in range(a.streams):
         b.stage(s, capture(fs, s % a.distinct, fmt))
     b.run_resident(bps * n, a.warmup)
+    leg = leg_name
     batches[leg], meta[leg] = b, dict(fmt=FR.NAMES[fmt], bytes_per_sample=bps, fs_khz=fs, **{k: int(v) for k, v in kw.items()})
 for r in range(a.rounds):
     for leg, b in batches.items():
