@@ -126,6 +126,14 @@ typedef struct wmbus_cfg {
      * kernel on: everything said below about raw bytes, whole blocks and the clip count then holds for a cu8 capture as well.  0 is in
      * every respect the context without this field. */
     int input_shift_hz;
+    /* 0 (default): off.  R = 1 ... 12: the I/Q DC offset of the input (zero-IF receivers: HackRF, E4000 dongles, Pluto, Lime) is estimated
+     * and subtracted on the GPU, per I and Q, in front of everything else that happens to a sample, with the exact integer arithmetic
+     * defined below next to wmbus_read_input_dc(): a one-pole average over level blocks of 512 input samples, time constant 2^R blocks
+     * (R = 6: 32768 input samples, 20 ms at 1.6 MS/s -- the value recommended for zero-IF receivers; it rests on synthetic captures and CPU
+     * runs of the reference on the restated arithmetic only).  This is NOT the reference's -o (cfg.remove_dc), which removes the DC of the
+     * discriminator's output, a frequency offset.  input_dc alone switches the conversion kernel on, as a shift alone does; 0 is in every
+     * respect the context without this field.  Anything above 12 is WMBUS_EINVAL. */
+    unsigned input_dc;
     /* Sample format of the input, WMBUS_FMT_* (0 = cu8, what an RTL-SDR delivers and the reference reads), and a linear input gain in
      * Q8, 1 ... 65535 = x 1/256 ... x 256 (0 means 256 = x 1).  The arithmetic is defined below, next to wmbus_resampler_design().
      * With a format other than cu8 or a gain other than x 1 the context converts on the GPU, inside the resampler where cfg.input_rate_hz
@@ -175,7 +183,7 @@ typedef struct wmbus_timing {
     unsigned rssi_mode;         /* WMBUS_RSSI_*: how this push got its RSSI */
     unsigned rssi_tiles;        /* RSSI on demand: (tile, capture) pairs listed in this push */
     unsigned clock_round[4], rla_round[4];   /* segments re-run in the unattended rounds, round by round (beyond the rounds enqueued: 0) */
-    /* a context that resamples, shifts or converts (cfg.input_rate_hz, input_shift_hz, input_format, input_gain_q8): the cu8 bytes this push's input became,
+    /* a context that resamples, shifts, removes the input's DC or converts (cfg.input_rate_hz, input_shift_hz, input_dc, input_format, input_gain_q8): the cu8 bytes this push's input became,
      * all streams (whether the pipeline took them in this push or they wait for the next block to fill), and how many of them the
      * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path. */
     uint64_t input_bytes_out, input_clipped;
@@ -303,13 +311,30 @@ int  wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsign
  * Host only, no device needed: the step, and (table may be NULL; cap = its int16 capacity, >= 2048) the 1024 entries {c[i], s[i]};
  * entry i + 256 is {-s[i], c[i]}.  WMBUS_EINVAL for |shift_hz| > in_hz / 2 or in_hz < 800000. */
 int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *table, size_t cap);
-/* Debug read (requires cfg.keep_taps and a context that resamples, converts or shifts: cfg.input_rate_hz, input_shift_hz, input_format,
- * input_gain_q8): the
+/* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
+ * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
+ * level block k = m >> 9 (512 input samples):
+ *     S[k]  = sum of x over block k                                              (per I and Q; |S| <= 2^24)
+ *     A[0]  = S[0] << R;   A[k] = A[k-1] - (A[k-1] >> R) + S[k]                  (int64; >> floors, also for A < 0)
+ *     dc[k] = clamp((A[k] + (1 << (8 + R))) >> (9 + R), -32768, 32767)
+ *     x'    = clamp(x - dc[k], -32768, 32767)
+ * x' takes the place of x in everything above: the x 64 widening of cu8 / cs8 under a shift (|x'| <= 510: 64 x' still fits), the
+ * rotation, the resampler's sum or acc = 16384 x', the gain, the clamp and the clip count.  The resampler's carried history holds x'
+ * (rotated where there is a shift); history before the stream is 0.  A push is a multiple of 4096 raw bytes = 2048 / 2048 / 1024 / 512
+ * samples, so it always holds whole level blocks.  dc[k] includes block k itself: nothing is delayed.  Only integers follow the one
+ * rounding of cf32: the bytes do not depend on tile, block or push boundaries.  The time constant is 2^R blocks.
+ *
+ * Debug read (requires a context with cfg.input_dc, not cfg.keep_taps: it is the offset's feedback, as wmbus_timing.input_clipped is the
+ * gain's): {dc_I, dc_Q} of every level block of the last push for one stream, in units of x.  Returns the number of pairs written, or a
+ * negative error. */
+long wmbus_read_input_dc(wmbus_ctx *ctx, unsigned stream, int16_t *iq, size_t cap_pairs);
+/* Debug read (requires cfg.keep_taps and a context that resamples, converts, shifts or removes the input's DC: cfg.input_rate_hz,
+ * input_shift_hz, input_dc, input_format, input_gain_q8): the
  * cu8 bytes the last push handed to the pipeline for one stream.  Returns the number of bytes written (0 for a push that completed no
  * block), or a negative error. */
 long wmbus_read_resampled(wmbus_ctx *ctx, unsigned stream, uint8_t *out, size_t cap);
 /* Pushes of this context that launched the resampler or the conversion kernel (0 for ever on the plain cu8 path, which a context
- * with cfg.input_shift_hz = 0 and nothing else set is). */
+ * with cfg.input_shift_hz = 0, cfg.input_dc = 0 and nothing else set is). */
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx);
 
 /* Number of visible HIP devices (0 if none). */

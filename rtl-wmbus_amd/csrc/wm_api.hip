@@ -91,7 +91,7 @@ struct wmbus_ctx {
     Owned mem;
     uint64_t in_stride = 0, n0 = 0;
     size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
-    /* cfg.input_rate_hz / input_shift_hz / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) --
+    /* cfg.input_rate_hz / input_shift_hz / input_dc / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) --
      * the resampler (`resample`), which also reads every format, rotates (`shift`) and applies the gain, or for an input at the native
      * rate the conversion kernel alone (L = M = 1, no taps, no history).  wmbus_stage fills the RAW windows; K0
      * writes the window of d_in the pipeline reads.  hist / rem are double-buffered like every carried state (a push reads half
@@ -101,6 +101,12 @@ struct wmbus_ctx {
         uint32_t fmt = WMBUS_FMT_CU8, bps = 2, gain = 0;   /* cfg.input_format, its raw bytes per sample, cfg.input_gain_q8 */
         uint32_t step = 0;                             /* the shift's phase advance per input sample (k0_shift_design) */
         uint32_t *d_shift_tab = nullptr;               /* [1024] {c, s} int16 */
+        /* cfg.input_dc != 0: the I/Q DC blocker -- k0_dc_sums and k0_dc_plan in front of the DC instantiation of either kernel */
+        uint32_t dc = 0, dc_stride = 0;                /* R; level blocks (512 input samples) of a full push */
+        K0S2 *d_dc_sums = nullptr;                     /* [S][dc_stride] */
+        uint32_t *d_dc_tab = nullptr;                  /* [S][dc_stride] {dc_I, dc_Q} int16 of the last push's level blocks */
+        K0DcState *d_dc_state = nullptr;               /* [2][S] */
+        K0DcArgs dca{};                                /* this push's arguments of the two kernels (k0_plan) */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
         uint64_t raw_stride = 0;
         uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
@@ -109,6 +115,7 @@ struct wmbus_ctx {
         uint8_t *d_rem = nullptr;                      /* [2][S][4096] */
         uint64_t n_in = 0, n_out = 0;                  /* raw samples pushed / outputs produced so far */
         size_t last_bytes = 0; uint32_t last_win = 0;  /* what the last push handed to the pipeline, and in which window */
+        uint32_t last_dc_blocks = 0;                   /* level blocks of the last push (wmbus_read_input_dc) */
         uint64_t last_out = 0;                         /* bytes the last push produced, all captures (wmbus_timing.input_bytes_out) */
         unsigned long long launches = 0;
     } k0;
@@ -395,6 +402,17 @@ int wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *ta
     return k0_shift_design(in_hz, shift_hz, step, table, cap) ? WMBUS_EINVAL : WMBUS_OK;
 }
 
+long wmbus_read_input_dc(wmbus_ctx *c, unsigned stream, int16_t *iq, size_t cap_pairs)
+{
+    if (!c || stream >= c->S || !iq) return WMBUS_EINVAL;
+    if (!c->k0.dc) return fail(c, WMBUS_EINVAL, "read_input_dc: the context was opened without cfg.input_dc");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_dc: collect the push first");
+    const size_t n = std::min(cap_pairs, (size_t)c->k0.last_dc_blocks);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n) HIPCHK(c, hipMemcpy(iq, c->k0.d_dc_tab + (size_t)stream * c->k0.dc_stride, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return (long)n;
+}
+
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx) { return ctx ? ctx->k0.launches : 0ull; }
 
 const char *wmbus_last_error(const wmbus_ctx *ctx) { return ctx ? ctx->err : "null context"; }
@@ -435,7 +453,9 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         return fail(c, WMBUS_EINVAL, "the polyphase pre-filter is the 1.6 MS/s design of rtl_wmbus.c:258-294: decimation 2, no -s");
     if (cfg->input_format > WMBUS_FMT_CF32) return fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format);
     if (cfg->input_gain_q8 > 65535u) return fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8);
+    if (cfg->input_dc > WM_K0_DC_MAX_R) return fail(c, WMBUS_EINVAL, "input_dc must be 0 (off) or 1 ... %u (time constant 2^input_dc x 512 input samples), got %u", WM_K0_DC_MAX_R, cfg->input_dc);
     auto &k = c->k0;
+    k.dc = cfg->input_dc;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
     if (cfg->input_shift_hz) {
         const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
@@ -458,8 +478,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k.tile = k0_pick_tile(L, M, T);
         if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
         k.lds = k0_lds_bytes(L, M, T, k.tile);
-    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift) {
-        /* the native rate in another format, with a gain or with a shift: the conversion kernel alone */
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc) {
+        /* the native rate in another format, with a gain, with a shift or with the DC blocker: the conversion kernel alone */
         k.on = true; k.L = k.M = k.T = 1u;
         k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
@@ -482,6 +502,7 @@ static int open_geometry(wmbus_ctx *c)
         const uint64_t most = ((uint64_t)(cfg->max_push_bytes / c->k0.bps) * c->k0.L + c->k0.M - 1u) / c->k0.M * 2u;
         c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
         c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
+        c->k0.dc_stride = (uint32_t)(cfg->max_push_bytes / c->k0.bps) >> WM_K0_DC_LOG2;
     }
     /* Time segments: 32768 / 8192 decimated samples for batches of whole waves (r02 / r03 A/Bs: clock 65536 -8 %, 16384 -25 %;
      * run-length 16384 -9 %, 4096 -20 %).  A batch with fewer captures than a wave has lanes is bound by how long ONE lane
@@ -598,6 +619,11 @@ static int open_allocate(wmbus_ctx *c)
         }
         A(m.dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
         if (c->k0.shift) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));
+        if (c->k0.dc) {
+            A(m.dalloc(&c->k0.d_dc_sums, (size_t)c->S * c->k0.dc_stride));
+            A(m.dalloc(&c->k0.d_dc_tab, (size_t)c->S * c->k0.dc_stride));
+            A(m.dalloc(&c->k0.d_dc_state, (size_t)2 * c->S));
+        }
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -662,6 +688,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
         A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     }
+    if (c->k0.dc) A(hipMemsetAsync(c->k0.d_dc_state, 0, (size_t)2 * c->S * sizeof(K0DcState), c->stream));      /* started = 0: A[0] = S[0] << R */
     std::vector<int16_t> shift_tab;
     if (c->k0.shift) {                                       /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
@@ -931,6 +958,11 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     ka->L = k.L; ka->M = k.M; ka->T = k.T; ka->tile = k.tile;
     ka->gain_q8 = k.gain; ka->clipped = c->d_scalars + SC_CLIP;
     ka->step = k.step; ka->shift_tab = k.d_shift_tab;
+    if (k.dc) {                                          /* a push is whole 4096-byte blocks: whole level blocks */
+        ka->dc_tab = k.d_dc_tab; ka->dc_stride = k.dc_stride;
+        k.dca = K0DcArgs{ka->raw, k.raw_stride, k.d_dc_sums, k.d_dc_tab, k.d_dc_state + (size_t)k.cur * c->S, k.d_dc_state + (size_t)(k.cur ^ 1u) * c->S,
+                         k.dc_stride, n_in >> WM_K0_DC_LOG2, k.dc};
+    }
     k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
     k.last_bytes = whole; k.last_win = c->fill;
@@ -939,12 +971,25 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
-    /* [cfg.input_shift_hz != 0][WMBUS_FMT_*] */
-    void (*const resample[2][4])(K0Args) = {{k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>},
-                                            {k0_resample_shift<WM_K0_CU8>, k0_resample_shift<WM_K0_CS8>, k0_resample_shift<WM_K0_CS16>, k0_resample_shift<WM_K0_CF32>}};
-    void (*const convert[2][4])(K0Args) = {{k0_convert<WM_K0_CU8>, k0_convert<WM_K0_CS8>, k0_convert<WM_K0_CS16>, k0_convert<WM_K0_CF32>},
-                                           {k0_convert_shift<WM_K0_CU8>, k0_convert_shift<WM_K0_CS8>, k0_convert_shift<WM_K0_CS16>, k0_convert_shift<WM_K0_CF32>}};
-    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
+    /* [cfg.input_dc != 0][cfg.input_shift_hz != 0][WMBUS_FMT_*] */
+    void (*const resample[2][2][4])(K0Args) = {
+        {{k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>},
+         {k0_resample_shift<WM_K0_CU8>, k0_resample_shift<WM_K0_CS8>, k0_resample_shift<WM_K0_CS16>, k0_resample_shift<WM_K0_CF32>}},
+        {{k0_resample_dc<WM_K0_CU8, false>, k0_resample_dc<WM_K0_CS8, false>, k0_resample_dc<WM_K0_CS16, false>, k0_resample_dc<WM_K0_CF32, false>},
+         {k0_resample_dc<WM_K0_CU8, true>, k0_resample_dc<WM_K0_CS8, true>, k0_resample_dc<WM_K0_CS16, true>, k0_resample_dc<WM_K0_CF32, true>}}};
+    void (*const convert[2][2][4])(K0Args) = {
+        {{k0_convert<WM_K0_CU8>, k0_convert<WM_K0_CS8>, k0_convert<WM_K0_CS16>, k0_convert<WM_K0_CF32>},
+         {k0_convert_shift<WM_K0_CU8>, k0_convert_shift<WM_K0_CS8>, k0_convert_shift<WM_K0_CS16>, k0_convert_shift<WM_K0_CF32>}},
+        {{k0_convert_dc<WM_K0_CU8, false>, k0_convert_dc<WM_K0_CS8, false>, k0_convert_dc<WM_K0_CS16, false>, k0_convert_dc<WM_K0_CF32, false>},
+         {k0_convert_dc<WM_K0_CU8, true>, k0_convert_dc<WM_K0_CS8, true>, k0_convert_dc<WM_K0_CS16, true>, k0_convert_dc<WM_K0_CF32, true>}}};
+    if (c->k0.dc) {                                      /* the level blocks' sums, then the recurrence over them: the table the K0 kernel subtracts */
+        void (*const sums[4])(K0DcArgs) = {k0_dc_sums<WM_K0_CU8>, k0_dc_sums<WM_K0_CS8>, k0_dc_sums<WM_K0_CS16>, k0_dc_sums<WM_K0_CF32>};
+        const K0DcArgs &da = c->k0.dca;
+        hipLaunchKernelGGL(sums[c->k0.fmt], dim3((da.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->S), dim3(WM_K0_THREADS), 0, c->stream, da);
+        hipLaunchKernelGGL(k0_dc_plan, dim3(c->S), dim3(128), 0, c->stream, da);
+        c->k0.last_dc_blocks = da.n_blk;
+    }
+    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.dc != 0u][c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
                        c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
@@ -1380,7 +1425,7 @@ long wmbus_read_tap(wmbus_ctx *c, const char *what, int chain, unsigned stream, 
 long wmbus_read_resampled(wmbus_ctx *c, unsigned stream, uint8_t *out, size_t cap)
 {
     if (!c || !out || stream >= c->S) return WMBUS_EINVAL;
-    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples, converts or shifts (cfg.input_rate_hz, input_shift_hz, input_format, input_gain_q8)");
+    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples, converts, shifts or removes the input's DC (cfg.input_rate_hz, input_shift_hz, input_dc, input_format, input_gain_q8)");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_resampled: collect the push first");
     const size_t n = std::min(cap, c->k0.last_bytes);
     HIPCHK(c, hipSetDevice(c->cfg.device));

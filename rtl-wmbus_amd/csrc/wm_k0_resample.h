@@ -40,6 +40,15 @@
  * carried.  One dword {c, s} per entry from the 4 KB table in global memory (K0Args.shift_tab; DESIGN.md section 4 says why not LDS),
  * {-s, c} built from it with V_PERM_B32, one V_DOT2_I32_I16 per component.  cu8 / cs8 samples are widened to 64 x first and F is
  * 21 instead of 15.  SH = false compiles to exactly the code there was: every line of the shift sits behind if constexpr (SH).
+ *
+ * I/Q DC blocker (cfg.input_dc = R; the contract is in include/wmbus_hip.h): the third template parameter DC of both block functions,
+ * and two small kernels in front of them.  k0_dc_sums adds up x per level block of 512 input samples (one wave per block, 16-byte
+ * loads, the wave reduced with __shfl_xor); k0_dc_plan walks the push's blocks in order -- A[k] = A[k-1] - (A[k-1] >> R) + S[k] is
+ * sequential by definition: one wave per component, on the scalar unit -- from the carried {A_I, A_Q, started} of the stream and leaves
+ * one dword {dc_I, dc_Q} per block in K0Args.dc_tab.  The block functions subtract it, saturating, where a sample is staged: in front of k0_x64 and the rotation, in the
+ * loop that fills the LDS span, in the history hand-over (the carried history holds x') and in k0_convert_block.  The two samples of
+ * a k0_load2 and the samples of a conversion lane's 16 bytes share a level block (index within the push >> 9): one table read per
+ * group.  DC = false compiles to exactly the code there was: every line of the blocker sits behind if constexpr (DC).
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -58,6 +67,8 @@
 #define WM_K0_CS16  2
 #define WM_K0_CF32  3
 #define WM_K0_CONV_UNROLL 4u       /* k0_convert_block: 16-byte loads a lane has in flight */
+#define WM_K0_DC_LOG2   9u         /* a level block of the DC blocker: 512 input samples */
+#define WM_K0_DC_MAX_R  12u
 
 struct K0Args {
     const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
@@ -81,6 +92,23 @@ struct K0Args {
     /* frequency shift (the SH instantiations only); all zero: none */
     uint32_t step;               /* phase advance per input sample, 2^32 = one turn                           */
     const uint32_t *shift_tab;   /* [1024] {c, s} int16: rint(16384 cos / sin(2 pi i / 1024))                 */
+    /* I/Q DC blocker (the DC instantiations only); all zero: none */
+    const uint32_t *dc_tab;      /* [S][dc_stride] {dc_I, dc_Q} int16 of this push's level blocks (k0_dc_plan) */
+    uint32_t dc_stride;
+};
+
+/* the carried state of the DC blocker, per capture */
+struct alignas(8) K0DcState { int64_t a_i, a_q; uint64_t started; };
+struct alignas(8) K0S2 { int32_t i, q; };
+/* k0_dc_sums and k0_dc_plan: what they read and leave for a push of n_blk level blocks per capture */
+struct K0DcArgs {
+    const uint8_t *raw;          /* [S][raw_stride] the raw bytes of this push                                */
+    uint64_t raw_stride;
+    K0S2 *sums;                  /* [S][stride] sum of x over each level block                                */
+    uint32_t *tab;               /* [S][stride] K0Args.dc_tab                                                 */
+    const K0DcState *st_in;      /* [S] the state in front of this push                                       */
+    K0DcState *st_out;           /* the same for the next push                                                */
+    uint32_t stride, n_blk, R;
 };
 
 /* raw bytes per sample; F + 8, the shift behind the gain product */
@@ -193,6 +221,17 @@ __device__ __forceinline__ uint32_t k0_rotate(uint32_t x, uint32_t phase, const 
     const uint32_t sc = k0_lo_pair(0u - (cs >> 16), cs);
     return k0_pair(k0_clamp16(k0_dot2(x, cs, 8192) >> 14), k0_clamp16(k0_dot2(x, sc, 8192) >> 14));
 }
+/* I/Q DC blocker: {I - dc_I, Q - dc_Q}, each clamped to int16 (V_PK_SUB_I16 with clamp) */
+__device__ __forceinline__ uint32_t k0_sub_dc(uint32_t v, uint32_t dc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short k0_s2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(k0_s2, v), __builtin_bit_cast(k0_s2, dc)));
+#else
+    return k0_pair(k0_clamp16((int32_t)(int16_t)(v & 0xFFFFu) - (int32_t)(int16_t)(dc & 0xFFFFu)),
+                   k0_clamp16((int32_t)(int16_t)(v >> 16) - (int32_t)(int16_t)(dc >> 16)));
+#endif
+}
 /* the staged sample v (as k0_load2 / k0_load1 left it) of stream index m, rotated */
 template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m)
 {
@@ -253,7 +292,7 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
 }
 
 /* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
-template <int FMT, bool SH = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
+template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
     const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -283,6 +322,10 @@ template <int FMT, bool SH = false> __device__ __forceinline__ void k0_resample_
         if (r >= 0) {
             if (r < (int64_t)a.n_in) {                           /* n_in is even: r + 1 lies inside too */
                 k0_load2<FMT>(raw + BPS * (uint64_t)r, v0, v1);
+                if constexpr (DC) {                              /* r is even: both samples lie in one level block */
+                    const uint32_t dc = a.dc_tab[(uint64_t)s * a.dc_stride + ((uint32_t)r >> WM_K0_DC_LOG2)];
+                    v0 = k0_sub_dc(v0, dc); v1 = k0_sub_dc(v1, dc);
+                }
                 if constexpr (SH) {                              /* only the low 32 bits of the stream index reach the phase */
                     const uint32_t m = (uint32_t)a.in_first + (uint32_t)r;
                     v0 = k0_shifted<FMT>(a, v0, m); v1 = k0_shifted<FMT>(a, v1, m + 1u);
@@ -307,6 +350,7 @@ template <int FMT, bool SH = false> __device__ __forceinline__ void k0_resample_
         for (uint32_t j = tid; j < T - 1u; j += nthr) {
             const uint32_t r = a.n_in - (T - 1u) + j;
             uint32_t v = k0_load1<FMT>(raw + BPS * (uint64_t)r);
+            if constexpr (DC) v = k0_sub_dc(v, a.dc_tab[(uint64_t)s * a.dc_stride + (r >> WM_K0_DC_LOG2)]);
             if constexpr (SH) v = k0_shifted<FMT>(a, v, (uint32_t)a.in_first + r);
             hist_out[j] = v;
         }
@@ -359,7 +403,7 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
  * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
  * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
  * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
-template <int FMT, bool SH = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -385,12 +429,16 @@ template <int FMT, bool SH = false> __device__ __forceinline__ void k0_convert_b
             const uint32_t o = a.rem_prev + 2u * (t_first + i);
             uint8_t *dst = o >= a.keep_from ? rout + (o - a.keep_from) : nullptr;
             const uint32_t in[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-            if constexpr (SH) {                                  /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
+            if constexpr (SH || DC) {                            /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
                 const uint32_t m0 = (uint32_t)a.in_first + t_first + i;
                 uint32_t r[SPL / 2u];
+                uint32_t dc = 0u;                                /* t_first + i is a multiple of SPL: the lane's samples lie in one level block */
+                if constexpr (DC) dc = a.dc_tab[(uint64_t)s * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
 #pragma unroll
                 for (uint32_t k = 0; k < SPL; k++) {
-                    const uint32_t y = k0_shifted<FMT>(a, k0_sample_of<FMT>(in, k), m0 + k);
+                    uint32_t y = k0_sample_of<FMT>(in, k);
+                    if constexpr (DC) y = k0_sub_dc(y, dc);
+                    if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k);
                     const uint32_t pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
                                           (k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), gain, nclip) << 8);
                     r[k / 2u] = k & 1u ? r[k / 2u] | (pair << 16) : pair;
@@ -442,7 +490,129 @@ template <int FMT, bool SH = false> __device__ __forceinline__ void k0_convert_b
     k0_count_clips(a, word, nclip);
 }
 
+/* I/Q DC blocker, step 1: S[k] = sum of x over level block k of the push, per I and Q.  blockIdx.x = four level blocks, one per wave;
+ * blockIdx.y = capture.  A lane takes 16 raw bytes per load, consecutive lanes consecutive memory: 1 / 1 / 2 / 4 loads cover the 512
+ * samples of cu8 / cs8 / cs16 / cf32.  |S| <= 512 * 32768 = 2^24: int32 holds it.  Lanes of a wave leave together or not at all. */
+template <int FMT> __device__ __forceinline__ void k0_dc_sums_block(const K0DcArgs &a)
+{
+    constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS, LOADS = (BPS << WM_K0_DC_LOG2) / (64u * 16u);
+    const uint32_t lane = threadIdx.x & 63u, blk = blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u, s = blockIdx.y;
+    if (blk >= a.n_blk) return;
+    const uint8_t *p = a.raw + (uint64_t)s * a.raw_stride + ((uint64_t)blk << WM_K0_DC_LOG2) * BPS;
+    K0U4 w[LOADS];
+#pragma unroll
+    for (uint32_t j = 0; j < LOADS; j++) w[j] = *(const K0U4 *)(p + 16u * (64u * j + lane));
+    int32_t si = 0, sq = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < LOADS; j++) {
+        const uint32_t in[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
+#pragma unroll
+        for (uint32_t k = 0; k < SPL; k++) {
+            const uint32_t v = k0_sample_of<FMT>(in, k);
+            si += (int32_t)(int16_t)(v & 0xFFFFu); sq += (int32_t)(int16_t)(v >> 16);
+        }
+    }
+    uint32_t ui = (uint32_t)si, uq = (uint32_t)sq;               /* wrap-around sums: the order does not matter */
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { ui += __shfl_xor(ui, m); uq += __shfl_xor(uq, m); }
+    if (lane == 0) a.sums[(uint64_t)s * a.stride + blk] = K0S2{(int32_t)ui, (int32_t)uq};
+}
+
+/* Lane i's v, the same in every lane of the wave (i is wave-uniform), and the wave's number.  On the device V_READLANE_B32 /
+ * V_READFIRSTLANE_B32: what they return lives in scalar registers, so the recurrence below runs on the scalar unit.  On the block
+ * emulator the wave meets in a shuffle. */
+__device__ __forceinline__ int32_t k0_lane_get(int32_t v, uint32_t i)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readlane(v, (int)i);
+#else
+    return __shfl(v, (int)i);
+#endif
+}
+__device__ __forceinline__ uint32_t k0_wave_id()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#else
+    return threadIdx.x >> 6;
+#endif
+}
+/* One component (c = 0: I, 1: Q) of one capture: the recurrence over the push's level blocks, in order, by ONE wave.  Its lanes fetch
+ * 64 sums at a time; step i takes lane i's sum, moves A -- three scalar instructions in int32, five in int64 -- and puts A[k] into
+ * slot i of the wave's 64 slots of LDS (every lane stores the same value: no exec juggling, and the chain never waits for the store);
+ * then every lane rounds the A[k] of its own slot to dc[k] and stores it: consecutive lanes, consecutive table entries.  ACC: int32_t
+ * where |A| <= 2^(24 + R) fits (R <= 6: the recommended R among them), else int64_t.  |dc| <= 32768 follows from |S| <= 2^24; the
+ * clamp is the contract's.  Both waves of the block make the same number of trips: the barrier is uniform. */
+template <typename ACC> __device__ __forceinline__ void k0_dc_walk(const K0DcArgs &a, uint32_t s, uint32_t c, uint32_t lane, ACC *slot)
+{
+    const int32_t *sums = (const int32_t *)(a.sums + (uint64_t)s * a.stride) + c;        /* block k: sums[2 k] */
+    int16_t *tab = (int16_t *)(a.tab + (uint64_t)s * a.stride) + c;                       /* block k: tab[2 k] */
+    const uint32_t R = a.R;
+    ACC acc = (ACC)(c ? a.st_in[s].a_q : a.st_in[s].a_i);
+    bool started = a.st_in[s].started != 0u;
+    for (uint32_t k0 = 0; k0 < a.n_blk; k0 += 64u) {
+        const uint32_t n = a.n_blk - k0 < 64u ? a.n_blk - k0 : 64u;
+        const int32_t v = lane < n ? sums[2u * (k0 + lane)] : 0;
+        uint32_t i = 0;
+        if (!started) {                                          /* A[0] = S[0] << R */
+            acc = (ACC)k0_lane_get(v, 0u) * ((ACC)1 << R);
+            slot[0] = acc;
+            started = true; i = 1u;
+        }
+        if (i == 0u && n == 64u) {                               /* a whole group: lane numbers and slots are constants */
+#pragma unroll
+            for (uint32_t j = 0; j < 64u; j += 8u) {             /* eight sums to scalar registers, then eight steps: the chain does not wait for a lane read */
+                int32_t sv[8];
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) sv[q] = k0_lane_get(v, j + q);
+#if defined(__HIP_DEVICE_COMPILE__)
+                __builtin_amdgcn_sched_barrier(0);               /* keep the reads in front: the scheduler would put each back before its use */
+#endif
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) {
+                    acc = (ACC)(acc + (ACC)sv[q]) - (acc >> R);  /* >> of a negative value floors */
+                    slot[j + q] = acc;
+                }
+            }
+        } else {
+            for (; i < n; i++) {
+                acc = (ACC)(acc + (ACC)k0_lane_get(v, i)) - (acc >> R);
+                slot[i] = acc;
+            }
+        }
+        if (lane < n) tab[2u * (k0 + lane)] = (int16_t)k0_clamp16((int32_t)((slot[lane] + ((ACC)1 << (8u + R))) >> (9u + R)));
+        __syncthreads();                                         /* the slots are free again */
+    }
+    if (lane == 0) {
+        if (c) a.st_out[s].a_q = (int64_t)acc; else { a.st_out[s].a_i = (int64_t)acc; a.st_out[s].started = started ? 1u : 0u; }
+    }
+}
+/* step 2: blockIdx.x = capture, two waves: wave 0 walks I, wave 1 walks Q (the recurrence is sequential by definition -- the floor
+ * makes it no scan -- so a push's 8192 steps are latency, and the two components at least run side by side).  slots: 128 int64_t */
+__device__ __forceinline__ void k0_dc_plan_block(const K0DcArgs &a, int64_t *slots)
+{
+    const uint32_t lane = threadIdx.x & 63u, c = k0_wave_id(), s = blockIdx.x;
+    if (a.R <= 6u) k0_dc_walk<int32_t>(a, s, c, lane, (int32_t *)slots + 64u * c); else k0_dc_walk<int64_t>(a, s, c, lane, slots + 64u * c);
+}
+
 #if defined(__HIPCC__)
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_dc_sums(K0DcArgs a) { k0_dc_sums_block<FMT>(a); }
+__global__ void __launch_bounds__(128) k0_dc_plan(K0DcArgs a)
+{
+    __shared__ int64_t slots[128];
+    k0_dc_plan_block(a, slots);
+}
+/* cfg.input_dc: the two stages with the subtraction in their staging, with and without the rotation */
+template <int FMT, bool SH> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_dc(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, SH, true>(a, k0_lds);
+}
+template <int FMT, bool SH> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_dc(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, SH, true>(a, &word);
+}
 __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {
     extern __shared__ uint32_t k0_lds[];

@@ -8,6 +8,8 @@
  *                bytes their clamp changed (wmbus_timing.input_clipped).
  *   k0_resample_shift<fmt> / k0_convert_shift<fmt>  the same two with cfg.input_shift_hz: every input sample rotated once, where it is
  *                staged, by an exact integer rule (a capture tuned off the channel; no counterpart in the reference).
+ *   k0_dc_sums<fmt> -> k0_dc_plan -> k0_resample_dc<fmt, shift> / k0_convert_dc<fmt, shift>  cfg.input_dc: the I/Q DC offset of a zero-IF
+ *                receiver, estimated per level block of 512 input samples and subtracted where a sample is staged (no counterpart).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.

@@ -9,7 +9,7 @@
  * reached through the C ABI in include/wmbus_hip.h.
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
- * -I sample format of the input and -g input gain in dB (converted on the GPU), -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
+ * -I sample format of the input and -g input gain in dB (converted on the GPU), -C I/Q DC blocker of the input, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
  * A batch is a wmbus_batch of the library per device: the files are split over several receiver contexts (whole groups
@@ -58,6 +58,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-I cu8|cs8|cs16|cf32 sample format of the input (default cu8; cs16 and cf32 little-endian, cf32 full scale +-1.0): converted on the GPU\n");
     fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
     fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
+    fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -432,7 +433,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -478,6 +479,13 @@ int main(int argc, char **argv)
             int ok;
             cfg.input_shift_hz = parse_shift(optarg, &ok);
             if (!ok) { print_usage(argv[0]); return EXIT_FAILURE; }
+            break;
+        }
+        case 'C': {
+            char *end;
+            const long r = strtol(optarg, &end, 10);
+            if (end == optarg || *end || r < 1 || r > 12) { print_usage(argv[0]); return EXIT_FAILURE; }
+            cfg.input_dc = (unsigned)r;
             break;
         }
         case 'g':
