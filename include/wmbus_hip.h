@@ -110,6 +110,12 @@ typedef struct wmbus_cfg {
     unsigned clock_waves;       /* how a clock-recovery lane group's filter cascade (iir.h:49-77 behind rtl_wmbus.c:1089-1111) is laid onto
                                    waves: 4 = systolic, the sections on the four waves of a block (round 6; 0: the default); 1 = one wave,
                                    software-pipelined across the sections (rounds 1-5).  Same records in memory, same datagrams; A/B */
+    /* 0 (default): off.  1: every datagram line comes with a level record (wmbus_level, wmbus_line_levels() below): the frequency offset
+     * and the deviation of its telegram, measured on the GPU from the soft symbols of the preamble in front of the access code, in the
+     * integer arithmetic defined below under LINE LEVELS -- the feedback cfg.input_shift_hz needs.  The lines themselves do not change.
+     * 0 is in every respect the context without this field: the same kernels, the same buffers, the same lines.  (The newest field, in front
+     * of the input stage's five, which close the struct.) */
+    unsigned line_levels;
     /* 0 (default): the input is at decimation x 800 kHz, as the reference demands ("use a multiple of 800kHz", rtl_wmbus.c:1274-1292).
      * Otherwise the rate of the cu8 input in Hz (>= 800000): the context resamples it on the GPU to decimation x 800 kHz with the exact
      * integer polyphase filter of wmbus_resampler_design() and decodes that stream.  wmbus_stage / wmbus_device_input /
@@ -163,12 +169,37 @@ typedef struct wmbus_line {
     uint32_t text_off, text_len;/* into the buffer returned by wmbus_lines_text()        */
 } wmbus_line;
 
+/* LINE LEVELS (cfg.line_levels = 1; tests/level_ref.py restates the arithmetic in numpy).  One record per line of wmbus_lines().
+ *   s[m]   the soft symbol of decimated sample m of the line's chain: the FIR output wmbus_read_tap("dphi") shows, IN FRONT of the -o DC
+ *          remover -- offset_hz is what -o removes -- and independent of -o, -a, -r, -t beyond the symbols themselves.  With
+ *          cfg.tolerance_mode the levels are computed from THAT mode's soft symbols (within 2e-6 of the reference's), so they may differ
+ *          by a unit from an exact context's.
+ *   a      sync_sample: the global decimated-sample index of the access-code chip, the chip carrying the sync flag that started the
+ *          decoder which printed the line.
+ *   window [a - lo, a - hi), N = lo - hi samples.  T1/C1 chain: lo = 256, hi = 128 (16 chips of the alternating preamble, ending 16 chips
+ *          in front of the 0x543D hit).  S1 chain: lo = 782, hi = 586 (N = 196, about 8 chips, ending 24 chips in front of the 0x547696
+ *          hit).  a - lo < 0 (the window would begin before the stream's first sample): the record is invalid, n = 0, both values 0.
+ *   q[m]   = clamp(rint(s[m] 2^20), -2^20, 2^20); the product is exact in f32, rint rounds half to even, NaN gives 0.
+ *   sum    = sum of q;   mean = floor((2 sum + N) / (2 N));   adev = sum of |q - mean|                       (integers only)
+ *   One unit of s is 400 kHz and 400000 / 2^20 = 3125 / 8192; both divisions floor, also for negative numerators:
+ *   offset_hz = floor((sum 3125 + N 4096) / (N 8192)),   dev_hz = floor((adev 3125 + N 4096) / (N 8192)),   n = N.
+ * dev_hz is a MEAN ABSOLUTE deviation over the band-limited preamble, not a peak deviation: a clean +-50 kHz preamble reads about 32 kHz.
+ * Integer sums do not depend on the order of a reduction, nor on tile, block or push boundaries: the records do not depend on how the
+ * input is cut into pushes (the context carries the last 782 soft symbols of every chain and capture from push to push). */
+typedef struct wmbus_level {
+    uint64_t sync_sample;
+    int32_t  offset_hz;
+    uint32_t dev_hz;
+    uint32_t n;
+    uint32_t pad;
+} wmbus_level;
+
 /* Per-push timings measured with HIP events on the library's own stream (ms). */
 typedef struct wmbus_timing {
     float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it */
     float clock_ms;             /* IIR clock recovery + time2 framer (incl. re-runs)  */
     float rla_ms;               /* run-length framer (incl. re-runs)                  */
-    float gather_ms;            /* burst extraction (and, without debug views, the RSSI of the tiles the bursts touch) */
+    float gather_ms;            /* burst extraction (and, without debug views, the RSSI of the tiles the bursts touch; with cfg.line_levels the level kernels) */
     float d2h_ms;               /* burst copy to pinned host memory                   */
     float gpu_total_ms;         /* first kernel start -> last copy done               */
     float host_decode_ms;       /* packet decoders + formatting (wall clock)          */
@@ -239,6 +270,9 @@ int  wmbus_collect(wmbus_ctx *ctx);
 
 size_t wmbus_lines(const wmbus_ctx *ctx, const wmbus_line **lines);
 const char *wmbus_lines_text(const wmbus_ctx *ctx, size_t *len);
+/* The level records of the last push's lines: the same count and the same order as wmbus_lines() (cfg.dedup_twins / only_crc_ok drop a
+ * level with its line).  A context opened without cfg.line_levels: 0, and *levels = NULL. */
+size_t wmbus_line_levels(const wmbus_ctx *ctx, const wmbus_level **levels);
 
 int  wmbus_get_timing(const wmbus_ctx *ctx, wmbus_timing *t);
 
@@ -396,6 +430,11 @@ int  wmbus_batch_stage(wmbus_batch *b, unsigned stream, const uint8_t *cu8, size
 void *wmbus_batch_device_input(wmbus_batch *b, unsigned stream);
 /* Runs until every group's source has ended (or `passes` pushes per context).  Returns 0 or the first error. */
 int  wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats *stats);
+/* For the SINK of a batch opened with cfg.line_levels: the level records of the lines the `lines` callback has just been handed, in
+ * their order.  Valid only during that callback, with the first_stream it was called with (the group's context is decoding nothing else
+ * meanwhile and the calls are serialised: no race).  Returns the count; 0 with *levels = NULL for any other first_stream or without
+ * cfg.line_levels. */
+size_t wmbus_batch_line_levels(const wmbus_batch *b, unsigned first_stream, const wmbus_level **levels);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ class Cfg(ctypes.Structure):
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
+                ("line_levels", ctypes.c_uint),
                 ("input_rate_hz", ctypes.c_uint), ("input_shift_hz", ctypes.c_int), ("input_dc", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
 
 
@@ -54,6 +55,15 @@ class Line(ctypes.Structure):
     _fields_ = [("stream", ctypes.c_uint32), ("chain", ctypes.c_uint8), ("algo", ctypes.c_uint8),
                 ("crc_ok", ctypes.c_uint8), ("pad", ctypes.c_uint8), ("sample", ctypes.c_uint64),
                 ("text_off", ctypes.c_uint32), ("text_len", ctypes.c_uint32)]
+
+
+class Level(ctypes.Structure):
+    """wmbus_level: the frequency offset and the mean absolute deviation of a line's telegram (cfg.line_levels); n = 0: not measured."""
+    _fields_ = [("sync_sample", ctypes.c_uint64), ("offset_hz", ctypes.c_int32), ("dev_hz", ctypes.c_uint32), ("n", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return dict(sync_sample=int(self.sync_sample), offset_hz=int(self.offset_hz), dev_hz=int(self.dev_hz), n=int(self.n))
 
 
 class Timing(ctypes.Structure):
@@ -100,7 +110,8 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
-           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc"]
+           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc",
+           "wmbus_line_levels", "wmbus_batch_line_levels"]
 
 _lib = None
 
@@ -124,6 +135,8 @@ def lib():
         L.wmbus_collect.argtypes = [vp]
         L.wmbus_lines.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Line))]; L.wmbus_lines.restype = sz
         L.wmbus_lines_text.argtypes = [vp, ctypes.POINTER(sz)]; L.wmbus_lines_text.restype = vp
+        L.wmbus_line_levels.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Level))]; L.wmbus_line_levels.restype = sz
+        L.wmbus_batch_line_levels.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Level))]; L.wmbus_batch_line_levels.restype = sz
         L.wmbus_get_timing.argtypes = [vp, ctypes.POINTER(Timing)]
         L.wmbus_read_tap.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, u, vp, sz]; L.wmbus_read_tap.restype = ctypes.c_long
         L.wmbus_read_chips.argtypes = [vp, ctypes.c_int, ctypes.c_int, u, vp, vp, sz]; L.wmbus_read_chips.restype = ctypes.c_long
@@ -221,7 +234,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
-              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0):
+              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, line_levels=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -244,6 +257,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_format, c.input_gain_q8 = int(input_format), int(input_gain_q8)
     c.input_shift_hz = int(input_shift_hz)   # signed Hz from the capture's centre to the channel (0: the capture is centred on it)
     c.input_dc = int(input_dc)               # 0: off; R = 1 ... 12: the I/Q DC blocker, time constant 2^R x 512 input samples
+    c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
     return c
@@ -328,6 +342,11 @@ class Batch:
                     ln = lines[k]
                     recs.append(dict(stream=ln.stream, chain=ln.chain, algo=ln.algo, crc_ok=ln.crc_ok, sample=ln.sample,
                                      text=ctypes.string_at(text + ln.text_off, ln.text_len).decode()))
+                if self.cfg.line_levels:               # the accessor is valid during this callback: every record gets its level
+                    p = ctypes.POINTER(Level)()
+                    assert lib().wmbus_batch_line_levels(self._h, first, ctypes.byref(p)) == n_lines
+                    for k, r in enumerate(recs):
+                        r["level"] = p[k].as_dict()
             on_push(first, n, recs, timing.contents.as_dict())
         return LINES_FN(c_lines)
 
@@ -410,6 +429,12 @@ class Receiver:
         text = ctypes.string_at(t, sz.value) if sz.value else b""
         return [dict(stream=p[i].stream, chain=p[i].chain, algo=p[i].algo, crc_ok=p[i].crc_ok, sample=p[i].sample,
                      text=text[p[i].text_off:p[i].text_off + p[i].text_len].decode()) for i in range(n)]
+
+    def line_levels(self):
+        """The level records of the last push's lines, in the order of lines() (a context opened with line_levels=1; else [])."""
+        p = ctypes.POINTER(Level)()
+        n = lib().wmbus_line_levels(self._h, ctypes.byref(p))
+        return [p[i].as_dict() for i in range(n)]
 
     def lines_count(self):
         return int(lib().wmbus_lines(self._h, None))

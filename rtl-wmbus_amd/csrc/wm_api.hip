@@ -40,6 +40,7 @@ struct HostDecoder {           /* persistent across pushes */
     wm_decoder dec;
     uint32_t owed;             /* chips to request at the start of the next push */
     uint64_t fed;              /* push in which the decoder last took chips (see the dropped-burst clean-up in wmbus_collect) */
+    wmbus_level lev;           /* cfg.line_levels: the level of the burst it is receiving, measured in the push that held its access code */
 };
 
 /* Every device and page-locked allocation of a context is made here and recorded; wmbus_close -- and with it every refused open --
@@ -162,6 +163,14 @@ struct wmbus_ctx {
     WmPkt *h_pkts = nullptr; uint8_t *h_bytes = nullptr;
     void *dv_hdr = nullptr, *dv_words = nullptr, *dv_pkts = nullptr, *dv_bytes = nullptr;    /* their device views */
     uint32_t n_hdr = 0, n_words = 0, n_pkts = 0;
+    /* cfg.line_levels (wm_k3_levels.h): the soft-symbol tail [2][2 S][WM_LEV_TAIL], double-buffered with carry_in like every carried state, and
+     * the level records k3_levels writes beside h_pkts / h_hdr (pinned, zero-copy like those).  All nullptr without the option. */
+    bool lev_on = false;
+    float *d_lev_tail = nullptr;
+    uint2 *d_lev_src_pkts = nullptr, *d_lev_src_hdr = nullptr;   /* [pkts_cap], [hdr_cap]: where k3_bursts tells k3_levels each record's access-code sample and row */
+    WmLevel *h_lev_pkts = nullptr, *h_lev_hdr = nullptr;
+    void *dv_lev_pkts = nullptr, *dv_lev_hdr = nullptr;
+    std::vector<wmbus_level> levels;                    /* parallel to `lines` */
     K1Entry k1[K1_ROLES];                               /* the demodulation kernels of this context */
     K1Args k1a{}; uint32_t ntiles = 0;                  /* this push's launch arguments (collect's slow path re-uses them) */
     std::vector<HostDecoder> decs;                      /* [stream][chain][algo] */
@@ -454,6 +463,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     if (cfg->input_format > WMBUS_FMT_CF32) return fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format);
     if (cfg->input_gain_q8 > 65535u) return fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8);
     if (cfg->input_dc > WM_K0_DC_MAX_R) return fail(c, WMBUS_EINVAL, "input_dc must be 0 (off) or 1 ... %u (time constant 2^input_dc x 512 input samples), got %u", WM_K0_DC_MAX_R, cfg->input_dc);
+    if (cfg->line_levels > 1u) return fail(c, WMBUS_EINVAL, "line_levels must be 0 or 1, got %u", cfg->line_levels);
+    c->lev_on = cfg->line_levels != 0u;
     auto &k = c->k0;
     k.dc = cfg->input_dc;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
@@ -667,6 +678,14 @@ static int open_allocate(wmbus_ctx *c)
     A(m.halloc(&c->h_pkts, (size_t)c->pkts_cap));
     A(m.halloc(&c->h_bytes, (size_t)c->bytes_cap));
     A(m.halloc(&c->h_pending, (size_t)4 * c->S));
+    if (c->lev_on) {
+        A(m.dalloc(&c->d_lev_tail, (size_t)2 * rows * WM_LEV_TAIL));
+        A(m.dalloc(&c->d_lev_src_pkts, (size_t)c->pkts_cap));
+        A(m.dalloc(&c->d_lev_src_hdr, (size_t)c->hdr_cap));
+        A(m.halloc(&c->h_lev_pkts, (size_t)c->pkts_cap));
+        A(m.halloc(&c->h_lev_hdr, (size_t)c->hdr_cap));
+        if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_lev_pkts, c->h_lev_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_lev_hdr, c->h_lev_hdr, 0)); }
+    }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_hdr, c->h_hdr, 0)); A(hipHostGetDevicePointer(&c->dv_words, c->h_words, 0)); }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_pkts, c->h_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_bytes, c->h_bytes, 0)); }
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e));
@@ -696,6 +715,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemcpyAsync(c->k0.d_shift_tab, shift_tab.data(), shift_tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     }
     A(hipMemsetAsync(c->d_ema_carry, 0, 2 * rows * sizeof(float), c->stream));
+    if (c->lev_on) A(hipMemsetAsync(c->d_lev_tail, 0, (size_t)2 * rows * WM_LEV_TAIL * sizeof(float), c->stream));      /* no window reaches in front of the stream: never read */
     /* a disabled chain (-p T / -p S) never writes its hand-off records: they must compare equal, not hold what an
      * earlier context left in the recycled allocation */
     A(hipMemsetAsync(c->d_ema_head, 0, (size_t)rows * c->ntiles_cap * sizeof(float), c->stream));
@@ -723,7 +743,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
     c->decs.resize((size_t)c->S * 4);                        /* [stream][chain][algo] */
     for (size_t i = 0; i < c->decs.size(); i++) {
         wm_decoder_init(&c->decs[i].dec, (i >> 1) & 1u ? WM_MODE_S1 : WM_MODE_T1C1);
-        c->decs[i].owed = 0; c->decs[i].fed = 0;
+        c->decs[i].owed = 0; c->decs[i].fed = 0; c->decs[i].lev = wmbus_level{};
     }
     return WMBUS_OK;
 }
@@ -916,6 +936,7 @@ static int launch_k3(wmbus_ctx *c, bool again)
         k3.pkts = (WmPkt *)c->dv_pkts; k3.pkts_cap = c->pkts_cap; k3.bytes = (uint8_t *)c->dv_bytes; k3.bytes_cap = c->bytes_cap;
         k3.n_pkts = c->d_scalars + SC_NPKTS; k3.n_bytes = c->d_scalars + SC_NBYTES;
     }
+    if (c->lev_on) { k3.lev_pkt = c->d_lev_src_pkts; k3.lev_hdr = c->d_lev_src_hdr; }
     if (c->rs_this && !c->rs_full_now) {
         k3.plans = c->d_plans;
         /* RSSI on demand: which tiles do the bursts touch (k3_spans), then their RSSI (an RS = 2 launch of the demodulation
@@ -934,6 +955,18 @@ static int launch_k3(wmbus_ctx *c, bool again)
      * for as long as it lives; 256 blocks put one on every SIMD of the chip (r02 sweep: 256 -> 64 blocks + 6 %, 16 blocks - 9 %: then the kernel itself becomes the longest link of the chain) */
     const uint32_t most = 4 * c->S + c->hits_cap;
     hipLaunchKernelGGL(k3_bursts, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, k3, 0xFFFFFFFFu);
+    if (c->lev_on) {
+        /* cfg.line_levels: a level per record k3_bursts has written (it left every record's access-code sample in d_lev_src_*), from this push's soft symbols and the tail in front of them; then the
+         * tail for the next push (into the other half: collect's slow path comes through here again and must find the same tail) */
+        K3LevArgs lv{};
+        lv.g = g; lv.dphi = c->d_dphi;
+        lv.tail_in = c->d_lev_tail + (size_t)c->carry_in * 2 * c->S * WM_LEV_TAIL; lv.tail_out = c->d_lev_tail + (size_t)(c->carry_in ^ 1u) * 2 * c->S * WM_LEV_TAIL;
+        lv.src_pkts = k3.pkts ? k3.lev_pkt : nullptr; lv.n_pkts = k3.n_pkts; lv.pkts_cap = k3.pkts_cap;
+        lv.src_hdr = k3.lev_hdr; lv.n_hdr = k3.n_hdr; lv.hdr_cap = k3.hdr_cap;
+        lv.lev_pkts = (WmLevel *)c->dv_lev_pkts; lv.lev_hdr = (WmLevel *)c->dv_lev_hdr;
+        hipLaunchKernelGGL(k3_levels, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, lv);
+        hipLaunchKernelGGL(k3_level_tail, dim3((WM_LEV_TAIL + 255u) / 256u, 2u * c->S), dim3(256), 0, c->stream, lv);
+    }
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1357,7 +1390,7 @@ int wmbus_collect(wmbus_ctx *c)
 {
     if (!c) return WMBUS_EINVAL;
     const int rc = wait_gpu(c);
-    if (rc) { c->lines.clear(); c->text.clear(); return rc; }
+    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); return rc; }
     return decode_host(c);
 }
 
@@ -1387,6 +1420,12 @@ size_t wmbus_lines(const wmbus_ctx *c, const wmbus_line **lines)
     if (!c) return 0;
     if (lines) *lines = c->lines.data();
     return c->lines.size();
+}
+
+size_t wmbus_line_levels(const wmbus_ctx *c, const wmbus_level **levels)
+{
+    if (levels) *levels = c && c->lev_on ? c->levels.data() : nullptr;
+    return c && c->lev_on ? c->levels.size() : 0;
 }
 
 const char *wmbus_lines_text(const wmbus_ctx *c, size_t *len)

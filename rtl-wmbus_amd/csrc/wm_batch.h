@@ -232,6 +232,15 @@ void *wmbus_batch_device_input(wmbus_batch *b, unsigned stream)
     return wmbus_device_input(b->ctx[i], stream - b->first[i]);
 }
 
+size_t wmbus_batch_line_levels(const wmbus_batch *b, unsigned first_stream, const wmbus_level **levels)
+{
+    if (levels) *levels = nullptr;
+    if (!b || !b->opened) return 0;
+    for (size_t i = 0; i < b->ctx.size(); i++)
+        if (b->first[i] == first_stream) return wmbus_line_levels(b->ctx[i], levels);
+    return 0;
+}
+
 int wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats *stats)
 {
     if (!b || !io) return WMBUS_EINVAL;

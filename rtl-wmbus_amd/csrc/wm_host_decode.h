@@ -11,8 +11,9 @@ namespace {
  * 18 ms instead of 2.8: tools/host_replay.py) */
 struct LineRec {
     uint64_t sample; uint32_t stream; uint8_t chain, algo, crc_ok; uint32_t seq; uint32_t part, off, len;
+    uint32_t lev;              /* cfg.line_levels: its level record in its part's `levs` */
 };
-struct LinePart { std::vector<LineRec> recs; std::string text; };
+struct LinePart { std::vector<LineRec> recs; std::string text; std::vector<wmbus_level> levs; };
 
 /* Persistent host worker pool of a context (packet decoders): run(n, f) executes f(0..n-1) on the
  * workers and the caller; threads are created once, not per push. */
@@ -108,8 +109,11 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                                 LinePart &part, uint32_t part_no, const char *ts_fixed)
 {
     std::vector<LineRec> &out = part.recs;
-    auto keep = [&](LineRec &r, const char *line, size_t n) {
+    /* the level travels with its item to the line it produces: a packet's is record idx of h_lev_pkts, a burst's the one its decoder keeps */
+    auto keep = [&](LineRec &r, const char *line, size_t n, const wmbus_level *lev) {
         r.part = part_no; r.off = (uint32_t)part.text.size(); r.len = (uint32_t)n;
+        r.lev = (uint32_t)part.levs.size();
+        if (c->lev_on) part.levs.push_back(*lev);
         part.text.append(line, n);
         out.push_back(r);
     };
@@ -143,12 +147,13 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                                                   (p.flags & WM_PKTF_ERR3OF6) != 0, ok, p.L, pkt, p.pkt_rssi, p.rssi_now, tag, ts, line, sizeof line);
                 LineRec r; r.sample = p.sample; r.stream = p.stream; r.chain = p.chain; r.algo = p.algo;
                 r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                keep(r, line, n);
+                keep(r, line, n, c->lev_on ? &c->h_lev_pkts[order[j].idx] : nullptr);
                 continue;
             }
             const WmBurstHdr &h = c->h_hdr[order[j].idx];
             const bool cont = h.flags & 1u;
             if (cont ? hd.owed == 0 : (hd.owed != 0 || h.chip0 < next_free)) continue;   /* the access code passed while the decoder was busy */
+            if (c->lev_on && !cont) hd.lev = c->h_lev_hdr[order[j].idx];      /* the decoder takes this burst: its level stays with it until the line, in a later push if need be */
             const uint32_t *w = c->h_words + h.word_off;
             int st = cont ? WM_DEC_RECEIVING : WM_DEC_IDLE;
             uint32_t k = 0;
@@ -167,7 +172,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                     const size_t n = wm_decoder_format(&hd.dec, tag, ts, rssi, line, sizeof line, &ok);
                     LineRec r; r.sample = h.pos0 + (word >> 11); r.stream = h.stream; r.chain = h.chain; r.algo = h.algo;
                     r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                    keep(r, line, n);
+                    keep(r, line, n, &hd.lev);
                     st = WM_DEC_IDLE;
                 }
                 if (st == WM_DEC_IDLE) { k++; break; }
@@ -189,7 +194,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
  * and the decoders only, so the NEXT push's front may already be on the GPU. */
 static int decode_host(wmbus_ctx *c)
 {
-    c->lines.clear(); c->text.clear();
+    c->lines.clear(); c->text.clear(); c->levels.clear();
     c->short_burst.store(0);
     if (!c->done.valid) return WMBUS_OK;
     c->done.valid = false;
@@ -271,6 +276,7 @@ static int decode_host(wmbus_ctx *c)
         l.text_off = (uint32_t)c->text.size(); l.text_len = r.len;
         c->text.append(parts[r.part].text, r.off, r.len);
         c->lines.push_back(l);
+        if (c->lev_on) c->levels.push_back(parts[r.part].levs[r.lev]);
     }
     c->tim.host_decode_ms = (float)(now_ms() - t0);
     if (const uint32_t sb = c->short_burst.load()) {       /* formatted once, after the pool has joined */

@@ -22,6 +22,8 @@ struct K3Args {
     uint32_t *err;
     struct WmItemRec *plans;     /* [4 S + hits_cap] what k3_spans has found out about every item (RSSI on demand: it runs before k3_bursts
                                     and needs the same facts); nullptr: k3_bursts finds out itself */
+    uint2 *lev_pkt, *lev_hdr;    /* cfg.line_levels (wm_k3_levels.h): per packet / header slot {the access-code chip's sample within the push (~0: a
+                                    continuation), row = chain * S + capture}, device memory for k3_levels; nullptr: off */
 };
 
 __device__ static const uint8_t D3OF6[64] = {
@@ -284,7 +286,7 @@ __device__ void burst_item(const K3Args &a, const uint32_t item, const uint32_t 
     if (!cont && a.pkts != nullptr && plan.need + 1u <= avail) {
         /* ---- the whole burst is here: decode it -------------------------------------------------- */
         uint32_t ev = n;                         /* chips consumed if nothing stops the decoder early */
-        uint32_t r_first = 0, r_last = 0, pm_last = 0;
+        uint32_t r_first = 0, r_last = 0, pm_last = 0, pm_sync = 0;
         for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
             const uint32_t j = j0 + ln;
             uint32_t w = 0, pm = 0, rs = 255u;
@@ -298,6 +300,7 @@ __device__ void burst_item(const K3Args &a, const uint32_t item, const uint32_t 
             }
             const unsigned long long m = __ballot(w & 1u);
             if (ln == 0) s_bits[j0 >> 6] = m;
+            if (j == 0u) pm_sync = pm;                           /* lane 0, which writes the record */
             if (j == 1u) r_first = rs;
             if (j + 1u == n) { r_last = rs; pm_last = pm; }
         }
@@ -371,6 +374,7 @@ __device__ void burst_item(const K3Args &a, const uint32_t item, const uint32_t 
             p.chip0 = chip0; p.consumed = ev; p.sample = g.m0 + pm_last; p.off = boff; p.L = plan.L;
             p.pkt_rssi = (uint8_t)r_first; p.rssi_now = (uint8_t)r_last;
             a.pkts[slot] = p;
+            if (a.lev_pkt) a.lev_pkt[slot] = make_uint2(pm_sync, (uint32_t)row);
         }
         WM_WAVE_SYNC();                                      /* the scratch is reused by the wave's next item */
         return;
@@ -403,6 +407,7 @@ __device__ void burst_item(const K3Args &a, const uint32_t item, const uint32_t 
         h.stream = stream; h.chain = (uint8_t)ch; h.algo = (uint8_t)algo; h.flags = (uint16_t)cont;
         h.chip0 = chip0; h.n_chips = n; h.pos0 = pos0; h.word_off = woff; h.avail = avail;
         a.hdr[hslot] = h;
+        if (a.lev_hdr) a.lev_hdr[hslot] = make_uint2(cont ? 0xFFFFFFFFu : (uint32_t)(pos0 - g.m0), (uint32_t)row);
     }
 }
 

@@ -27,6 +27,9 @@
  *                stops at the first checkpoint of the speculative pass it reproduces).
  *   k3_bursts    access-code hits -> the chips (with their RSSI bytes) a host packet decoder
  *                consumes.   k4_flatten: debug/parity view of a whole chip stream.
+ *   k3_levels    option (cfg.line_levels): frequency offset and deviation of every candidate telegram from the soft symbols of its
+ *                preamble, in integers; k3_level_tail carries the last 782 soft symbols of every row to the next push.
+ *                                  (no counterpart: the reference prints two RSSI bytes only)
  *
  * Exactness: every float operation the reference performs is performed here in the same order
  * with separate roundings (wm_exact.h; the file is also built with -ffp-contract=off).  The
@@ -108,3 +111,4 @@ __global__ void k2_finish(WmPush g, K2Finish f)
 }
 
 #include "wm_k3_bursts.h"
+#include "wm_k3_levels.h"

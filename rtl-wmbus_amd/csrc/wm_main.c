@@ -9,7 +9,8 @@
  * reached through the C ABI in include/wmbus_hip.h.
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
- * -I sample format of the input and -g input gain in dB (converted on the GPU), -C I/Q DC blocker of the input, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
+ * -I sample format of the input and -g input gain in dB (converted on the GPU), -C I/Q DC blocker of the input, -l frequency offset and
+ * deviation of every telegram appended to its line, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
  * A batch is a wmbus_batch of the library per device: the files are split over several receiver contexts (whole groups
@@ -59,6 +60,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
     fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
+    fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -105,7 +107,8 @@ struct batch_job {
     wmbus_cfg cfg; int n; char **names; FILE **f; int *live; int rc;
     unsigned fill_threads;                               /* readers per fill call (a context's files are read side by side) */
     unsigned told;                                       /* warnings already reported for this device */
-    int stats, fast_exit;
+    int stats, fast_exit, lev_missing;                   /* lev_missing: -l and a push came without its levels (the run fails) */
+    wmbus_batch *b;                                      /* -l: the sink asks it for the levels of the lines it is handed */
     wmbus_batch_stats st;
     unsigned long long bytes_out, clipped;               /* wmbus_timing.input_bytes_out / input_clipped over the run */
 };
@@ -216,16 +219,33 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
     return most;
 }
 
+/* -l: the line with ";offset_hz;dev_hz" in front of its newline, both fields empty for a level that could not be measured */
+static void write_line(const char *text, size_t len, const wmbus_level *lev)
+{
+    if (!lev) { fwrite(text, 1, len, stdout); return; }
+    if (len && text[len - 1] == '\n') len--;
+    fwrite(text, 1, len, stdout);
+    if (lev->n) fprintf(stdout, ";%d;%u\n", (int)lev->offset_hz, (unsigned)lev->dev_hz);
+    else fputs(";;\n", stdout);
+}
+
 static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line *ln, size_t nl, const char *text, const wmbus_timing *t)
 {
     struct batch_job *j = user;
-    (void)first; (void)n;
+    (void)n;
+    const wmbus_level *lev = NULL;
     pthread_mutex_lock(&out_lock);
+    if (j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+        fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing; the lines are not printed\n", nl);
+        j->lev_missing = 1;
+        pthread_mutex_unlock(&out_lock);
+        return;
+    }
     report_warnings(t->warnings, &j->told);
     j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
-        fwrite(text + ln[i].text_off, 1, ln[i].text_len, stdout);
+        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL);
     }
     if (nl) fflush(stdout);
     pthread_mutex_unlock(&out_lock);
@@ -251,6 +271,7 @@ static int run_batch(struct batch_job *j)
         goto out;
     }
     clock_gettime(CLOCK_MONOTONIC, &t_open1);
+    j->b = b;
     if (j->stats) fprintf(stderr, "rtl_wmbus_hip: device %d: contexts open after %.3f s\n", j->cfg.device, (double)(t_open1.tv_sec - t_open0.tv_sec) + (t_open1.tv_nsec - t_open0.tv_nsec) * 1e-9);
     wmbus_batch_io io;
     memset(&io, 0, sizeof io);
@@ -263,7 +284,7 @@ static int run_batch(struct batch_job *j)
     if (j->stats && j->bytes_out)                            /* a converting path is active: what the gain did */
         fprintf(stderr, "rtl_wmbus_hip: device %d: input conversion: %llu of %llu bytes clipped (%.4f %%)\n", j->cfg.device, j->clipped, j->bytes_out,
                 100.0 * (double)j->clipped / (double)j->bytes_out);
-    rc = EXIT_SUCCESS;
+    rc = j->lev_missing ? EXIT_FAILURE : EXIT_SUCCESS;
 out:
     if (!j->fast_exit || rc != EXIT_SUCCESS) wmbus_batch_close(b);      /* every exit path closes what it opened, unless the process is about to end anyway */
     for (int s = 0; j->f && s < j->n; s++) if (j->f[s]) fclose(j->f[s]);
@@ -405,7 +426,7 @@ static int parse_devices(const char *arg, int *devs, int cap)
 }
 
 /* ---- live stream (stdin / TCP): wm_reader.c stages the bytes, this is where a push leaves -------- */
-struct live { wmbus_ctx *ctx; unsigned told; };
+struct live { wmbus_ctx *ctx; unsigned told; int levels; };
 
 static int live_push(void *user, const unsigned char *buf, size_t n)
 {
@@ -418,7 +439,16 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     if (!wmbus_get_timing(lv->ctx, &t)) report_warnings(t.warnings, &lv->told);
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
-    if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
+    if (len && lv->levels) {
+        const wmbus_line *ln; const wmbus_level *lev;
+        const size_t nl = wmbus_lines(lv->ctx, &ln);
+        if (wmbus_line_levels(lv->ctx, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+            fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
+            return -1;
+        }
+        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lev + i);
+        fflush(stdout);
+    } else if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
     return 0;
 }
 
@@ -433,7 +463,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:l")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -464,6 +494,7 @@ int main(int argc, char **argv)
         case 'T': tcp = optarg; break;
         case 'L': max_latency_ms = (unsigned)strtoul(optarg, NULL, 10); break;
         case 'S': stats = 1; break;
+        case 'l': cfg.line_levels = 1; break;
         case 'F': cfg.tolerance_mode = 1; break;
         case 'R':
             cfg.input_rate_hz = parse_rate(optarg);
@@ -538,7 +569,7 @@ int main(int argc, char **argv)
     int fd = 0;
     if (tcp && (fd = open_tcp(tcp)) < 0) return EXIT_FAILURE;
 
-    struct live lv = {NULL, 0};
+    struct live lv = {NULL, 0, (int)cfg.line_levels};
     int rc = wmbus_open(&cfg, &lv.ctx);
     if (rc) {
         fprintf(stderr, "rtl_wmbus_hip: cannot open GPU back end: %s\n", lv.ctx ? wmbus_last_error(lv.ctx) : "out of memory");
