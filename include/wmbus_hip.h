@@ -107,6 +107,14 @@ typedef struct wmbus_cfg {
                                    512 threads is available (decimation 2, no -s, RSSI on demand); A/B */
     unsigned k1_tiles_per_block;/* consecutive tiles a block of that first pass takes, each tile's input loaded while the one before
                                    is computed (0: the default; 1: one tile per block, no prefetch) */
+    /* 0 (default): off.  1: PER-BLOCK AGC -- the input gain is found on the GPU, for every level block of 512 input samples from that
+     * block's own peak, with the exact integer arithmetic defined below next to wmbus_read_input_gain(); it takes the place of
+     * input_gain_q8, which must then be 0 or 256 (anything else together with input_agc is WMBUS_EINVAL, as is an input_agc above 1).
+     * For captures whose level does not suit the pipeline's 8 bits -- a weak 16-bit or float capture, a weak cu8 / cs8 one, weak and strong
+     * transmitters in one capture -- which otherwise decode nothing and give no hint why.  input_agc alone switches the conversion kernel
+     * on, as a shift or the DC blocker alone does; 0 is in every respect the context without this field: the same kernels, buffers and
+     * bytes.  (Placed in front of clock_waves; the fields behind it keep their order.) */
+    unsigned input_agc;
     unsigned clock_waves;       /* how a clock-recovery lane group's filter cascade (iir.h:49-77 behind rtl_wmbus.c:1089-1111) is laid onto
                                    waves: 4 = systolic, the sections on the four waves of a block (round 6; 0: the default); 1 = one wave,
                                    software-pipelined across the sections (rounds 1-5).  Same records in memory, same datagrams; A/B */
@@ -214,7 +222,7 @@ typedef struct wmbus_timing {
     unsigned rssi_mode;         /* WMBUS_RSSI_*: how this push got its RSSI */
     unsigned rssi_tiles;        /* RSSI on demand: (tile, capture) pairs listed in this push */
     unsigned clock_round[4], rla_round[4];   /* segments re-run in the unattended rounds, round by round (beyond the rounds enqueued: 0) */
-    /* a context that resamples, shifts, removes the input's DC or converts (cfg.input_rate_hz, input_shift_hz, input_dc, input_format, input_gain_q8): the cu8 bytes this push's input became,
+    /* a context that resamples, shifts, removes the input's DC, levels it or converts (cfg.input_rate_hz, input_shift_hz, input_dc, input_agc, input_format, input_gain_q8): the cu8 bytes this push's input became,
      * all streams (whether the pipeline took them in this push or they wait for the next block to fill), and how many of them the
      * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path. */
     uint64_t input_bytes_out, input_clipped;
@@ -362,13 +370,38 @@ int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *t
  * gain's): {dc_I, dc_Q} of every level block of the last push for one stream, in units of x.  Returns the number of pairs written, or a
  * negative error. */
 long wmbus_read_input_dc(wmbus_ctx *ctx, unsigned stream, int16_t *iq, size_t cap_pairs);
-/* Debug read (requires cfg.keep_taps and a context that resamples, converts, shifts or removes the input's DC: cfg.input_rate_hz,
- * input_shift_hz, input_dc, input_format, input_gain_q8): the
+/* PER-BLOCK AGC (cfg.input_agc = 1; tests/agc_ref.py restates it in numpy).  With x' the format's int16 sample behind the DC blocker
+ * where cfg.input_dc is set (else x, by the UNSHIFTED rules above), m the sample's index within the stream and level block k = m >> 9
+ * (the blocker's block of 512 input samples):
+ *     P[k] = max over block k of (|x'_I| + |x'_Q|)                                (0 ... 65536)
+ *     U    = 9 for cu8 / cs8, 16 for cs16 / cf32                                  (with or without a shift: the x 64 widening of the 8-bit
+ *                                                                                  formats cancels against F = 21)
+ *     g[k] = clamp(floor((96 << U) / max(P[k], 1)), 1, 65535)                     (uint32 division; 96 << 16 < 2^32)
+ * g[k] takes the place of cfg.input_gain_q8 in the output rule: the byte of an output whose NEWEST input sample lies in block k (at the
+ * native rate: the sample itself; behind the resampler: input floor(n M / L) of output n) is
+ *     clamp((acc g[k] + (128 << (F + 8))) >> (F + 8), 0, 255),  the product in int64, F as above (15 / 22; 21 / 22 under a shift).
+ * So the block's peak lands on +-96 of the byte's +-127: |I| + |Q| bounds either component after any rotation, and the resampler's
+ * pass-band ripple and the gain's floor stay inside the rest.  Only integers follow the one rounding of cf32 and g[k] depends on block k
+ * alone -- nothing is carried, there is no attack and no release: FSK has a constant envelope, a block's own peak is the estimate, and
+ * an envelope that decays over several blocks loses weak telegrams behind strong ones -- so the bytes do not depend
+ * on tile, block or push boundaries; a push always holds whole level blocks.  Consequences:
+ *   - every block is brought to the same level, so the rssi a line prints is RELATIVE under AGC: it no longer tells a strong
+ *     transmitter from a weak one;
+ *   - a silent block is amplified up to the clamp of g: all-128 cu8 (x = 1, P = 2, g = 24576) gives the constant byte 176, all-zero
+ *     cs16 the byte 128 -- constants, which the discriminator does not see;
+ *   - behind the resampler an output's sum reaches back T - 1 samples, across a block edge too: a few outputs behind a strong-to-weak
+ *     edge carry the strong block's samples under the weak block's gain and may clip; wmbus_timing.input_clipped counts them.
+ *
+ * Debug read (requires a context with cfg.input_agc, not cfg.keep_taps): g[k] of every level block of the last push for one stream.
+ * Returns the number of values written, or a negative error. */
+long wmbus_read_input_gain(wmbus_ctx *ctx, unsigned stream, uint16_t *g, size_t cap);
+/* Debug read (requires cfg.keep_taps and a context that resamples, converts, shifts, removes the input's DC or levels it:
+ * cfg.input_rate_hz, input_shift_hz, input_dc, input_agc, input_format, input_gain_q8): the
  * cu8 bytes the last push handed to the pipeline for one stream.  Returns the number of bytes written (0 for a push that completed no
  * block), or a negative error. */
 long wmbus_read_resampled(wmbus_ctx *ctx, unsigned stream, uint8_t *out, size_t cap);
 /* Pushes of this context that launched the resampler or the conversion kernel (0 for ever on the plain cu8 path, which a context
- * with cfg.input_shift_hz = 0, cfg.input_dc = 0 and nothing else set is). */
+ * with cfg.input_shift_hz = 0, cfg.input_dc = 0, cfg.input_agc = 0 and nothing else set is). */
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx);
 
 /* Number of visible HIP devices (0 if none). */

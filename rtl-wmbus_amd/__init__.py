@@ -46,7 +46,7 @@ class Cfg(ctypes.Structure):
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
-                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
+                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
                 ("line_levels", ctypes.c_uint),
                 ("input_rate_hz", ctypes.c_uint), ("input_shift_hz", ctypes.c_int), ("input_dc", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
 
@@ -110,7 +110,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
-           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc",
+           "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
            "wmbus_line_levels", "wmbus_batch_line_levels"]
 
 _lib = None
@@ -145,6 +145,7 @@ def lib():
         L.wmbus_shift_design.argtypes = [u, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), vp, sz]
         L.wmbus_read_resampled.argtypes = [vp, u, vp, sz]; L.wmbus_read_resampled.restype = ctypes.c_long
         L.wmbus_read_input_dc.argtypes = [vp, u, vp, sz]; L.wmbus_read_input_dc.restype = ctypes.c_long
+        L.wmbus_read_input_gain.argtypes = [vp, u, vp, sz]; L.wmbus_read_input_gain.restype = ctypes.c_long
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -234,7 +235,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
-              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, line_levels=0):
+              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -257,6 +258,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_format, c.input_gain_q8 = int(input_format), int(input_gain_q8)
     c.input_shift_hz = int(input_shift_hz)   # signed Hz from the capture's centre to the channel (0: the capture is centred on it)
     c.input_dc = int(input_dc)               # 0: off; R = 1 ... 12: the I/Q DC blocker, time constant 2^R x 512 input samples
+    c.input_agc = int(input_agc)             # 0: off; 1: the gain of every level block of 512 input samples from its own peak (not with input_gain_q8)
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
@@ -496,6 +498,16 @@ class Receiver:
         r = lib().wmbus_read_input_dc(self._h, stream, out.ctypes.data, cap)
         if r < 0:
             raise WmbusError(f"read_input_dc failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
+        return out[:r]
+
+    def read_input_gain(self, stream, cap=None):
+        """uint16 [n]: the gain g (as input_gain_q8 counts it for the 8-bit formats; x 1 / 2^16 for cs16 / cf32) the AGC gave each level
+        block (512 input samples) of the last push (a context with input_agc)."""
+        cap = cap or (int(self.cfg.max_push_bytes) // 1024 + 1 if self.cfg is not None else 1 << 16)
+        out = np.zeros(cap, np.uint16)
+        r = lib().wmbus_read_input_gain(self._h, stream, out.ctypes.data, cap)
+        if r < 0:
+            raise WmbusError(f"read_input_gain failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
         return out[:r]
 
     def resampler_launches(self):

@@ -92,7 +92,7 @@ struct wmbus_ctx {
     Owned mem;
     uint64_t in_stride = 0, n0 = 0;
     size_t push_cap = 0;                               /* bytes of a push the pipeline is sized for: cfg.max_push_bytes, or what that many raw bytes resample to at most */
-    /* cfg.input_rate_hz / input_shift_hz / input_dc / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) --
+    /* cfg.input_rate_hz / input_shift_hz / input_dc / input_agc / input_format / input_gain_q8: the stage in front of the demodulation kernel (wm_k0_resample.h) --
      * the resampler (`resample`), which also reads every format, rotates (`shift`) and applies the gain, or for an input at the native
      * rate the conversion kernel alone (L = M = 1, no taps, no history).  wmbus_stage fills the RAW windows; K0
      * writes the window of d_in the pipeline reads.  hist / rem are double-buffered like every carried state (a push reads half
@@ -108,6 +108,10 @@ struct wmbus_ctx {
         uint32_t *d_dc_tab = nullptr;                  /* [S][dc_stride] {dc_I, dc_Q} int16 of the last push's level blocks */
         K0DcState *d_dc_state = nullptr;               /* [2][S] */
         K0DcArgs dca{};                                /* this push's arguments of the two kernels (k0_plan) */
+        /* cfg.input_agc: the per-block AGC -- k0_agc_gain (behind the blocker's two) in front of the AG instantiation of either kernel */
+        bool agc = false;
+        uint16_t *d_agc_tab = nullptr;                 /* [S][dc_stride] g of the last push's level blocks */
+        K0AgcArgs aga{};                               /* this push's arguments of k0_agc_gain (k0_plan) */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
         uint64_t raw_stride = 0;
         uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
@@ -116,7 +120,7 @@ struct wmbus_ctx {
         uint8_t *d_rem = nullptr;                      /* [2][S][4096] */
         uint64_t n_in = 0, n_out = 0;                  /* raw samples pushed / outputs produced so far */
         size_t last_bytes = 0; uint32_t last_win = 0;  /* what the last push handed to the pipeline, and in which window */
-        uint32_t last_dc_blocks = 0;                   /* level blocks of the last push (wmbus_read_input_dc) */
+        uint32_t last_dc_blocks = 0;                   /* level blocks of the last push (wmbus_read_input_dc, wmbus_read_input_gain) */
         uint64_t last_out = 0;                         /* bytes the last push produced, all captures (wmbus_timing.input_bytes_out) */
         unsigned long long launches = 0;
     } k0;
@@ -422,6 +426,17 @@ long wmbus_read_input_dc(wmbus_ctx *c, unsigned stream, int16_t *iq, size_t cap_
     return (long)n;
 }
 
+long wmbus_read_input_gain(wmbus_ctx *c, unsigned stream, uint16_t *g, size_t cap)
+{
+    if (!c || stream >= c->S || !g) return WMBUS_EINVAL;
+    if (!c->k0.agc) return fail(c, WMBUS_EINVAL, "read_input_gain: the context was opened without cfg.input_agc");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_gain: collect the push first");
+    const size_t n = std::min(cap, (size_t)c->k0.last_dc_blocks);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n) HIPCHK(c, hipMemcpy(g, c->k0.d_agc_tab + (size_t)stream * c->k0.dc_stride, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return (long)n;
+}
+
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx) { return ctx ? ctx->k0.launches : 0ull; }
 
 const char *wmbus_last_error(const wmbus_ctx *ctx) { return ctx ? ctx->err : "null context"; }
@@ -463,10 +478,13 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     if (cfg->input_format > WMBUS_FMT_CF32) return fail(c, WMBUS_EINVAL, "input_format must be WMBUS_FMT_CU8, _CS8, _CS16 or _CF32 (got %u)", cfg->input_format);
     if (cfg->input_gain_q8 > 65535u) return fail(c, WMBUS_EINVAL, "input_gain_q8 must be 1 ... 65535 (x 1/256 ... x 256; 0: x 1), got %u", cfg->input_gain_q8);
     if (cfg->input_dc > WM_K0_DC_MAX_R) return fail(c, WMBUS_EINVAL, "input_dc must be 0 (off) or 1 ... %u (time constant 2^input_dc x 512 input samples), got %u", WM_K0_DC_MAX_R, cfg->input_dc);
+    if (cfg->input_agc > 1u) return fail(c, WMBUS_EINVAL, "input_agc must be 0 (off) or 1, got %u", cfg->input_agc);
+    if (cfg->input_agc && cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u)
+        return fail(c, WMBUS_EINVAL, "input_agc takes the place of input_gain_q8: leave that 0 or 256 (got %u)", cfg->input_gain_q8);
     if (cfg->line_levels > 1u) return fail(c, WMBUS_EINVAL, "line_levels must be 0 or 1, got %u", cfg->line_levels);
     c->lev_on = cfg->line_levels != 0u;
     auto &k = c->k0;
-    k.dc = cfg->input_dc;
+    k.dc = cfg->input_dc; k.agc = cfg->input_agc != 0u;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
     if (cfg->input_shift_hz) {
         const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
@@ -489,8 +507,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k.tile = k0_pick_tile(L, M, T);
         if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
         k.lds = k0_lds_bytes(L, M, T, k.tile);
-    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc) {
-        /* the native rate in another format, with a gain, with a shift or with the DC blocker: the conversion kernel alone */
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc || k.agc) {
+        /* the native rate in another format, with a gain, with a shift, with the DC blocker or with the AGC: the conversion kernel alone */
         k.on = true; k.L = k.M = k.T = 1u;
         k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
@@ -635,6 +653,7 @@ static int open_allocate(wmbus_ctx *c)
             A(m.dalloc(&c->k0.d_dc_tab, (size_t)c->S * c->k0.dc_stride));
             A(m.dalloc(&c->k0.d_dc_state, (size_t)2 * c->S));
         }
+        if (c->k0.agc) A(m.dalloc(&c->k0.d_agc_tab, (size_t)c->S * c->k0.dc_stride));
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -996,6 +1015,10 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
         k.dca = K0DcArgs{ka->raw, k.raw_stride, k.d_dc_sums, k.d_dc_tab, k.d_dc_state + (size_t)k.cur * c->S, k.d_dc_state + (size_t)(k.cur ^ 1u) * c->S,
                          k.dc_stride, n_in >> WM_K0_DC_LOG2, k.dc};
     }
+    if (k.agc) {
+        ka->agc_tab = k.d_agc_tab; ka->dc_stride = k.dc_stride;
+        k.aga = K0AgcArgs{ka->raw, k.raw_stride, k.d_dc_tab, k.d_agc_tab, k.dc_stride, n_in >> WM_K0_DC_LOG2};
+    }
     k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
     k.last_bytes = whole; k.last_win = c->fill;
@@ -1004,7 +1027,14 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
-    /* [cfg.input_dc != 0][cfg.input_shift_hz != 0][WMBUS_FMT_*] */
+    /* [cfg.input_dc != 0][cfg.input_shift_hz != 0][WMBUS_FMT_*]; cfg.input_agc: the same three in the tables below */
+#define K0_FORMATS(K, ...) {K<WM_K0_CU8, __VA_ARGS__>, K<WM_K0_CS8, __VA_ARGS__>, K<WM_K0_CS16, __VA_ARGS__>, K<WM_K0_CF32, __VA_ARGS__>}
+    void (*const resample_agc[2][2][4])(K0Args) = {{K0_FORMATS(k0_resample_agc, false, false), K0_FORMATS(k0_resample_agc, true, false)},
+                                                   {K0_FORMATS(k0_resample_agc, false, true), K0_FORMATS(k0_resample_agc, true, true)}};
+    void (*const convert_agc[2][2][4])(K0Args) = {{K0_FORMATS(k0_convert_agc, false, false), K0_FORMATS(k0_convert_agc, true, false)},
+                                                  {K0_FORMATS(k0_convert_agc, false, true), K0_FORMATS(k0_convert_agc, true, true)}};
+    void (*const gain[2][4])(K0AgcArgs) = {K0_FORMATS(k0_agc_gain, false), K0_FORMATS(k0_agc_gain, true)};
+#undef K0_FORMATS
     void (*const resample[2][2][4])(K0Args) = {
         {{k0_resample, k0_resample_fmt<WM_K0_CS8>, k0_resample_fmt<WM_K0_CS16>, k0_resample_fmt<WM_K0_CF32>},
          {k0_resample_shift<WM_K0_CU8>, k0_resample_shift<WM_K0_CS8>, k0_resample_shift<WM_K0_CS16>, k0_resample_shift<WM_K0_CF32>}},
@@ -1022,7 +1052,13 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
         hipLaunchKernelGGL(k0_dc_plan, dim3(c->S), dim3(128), 0, c->stream, da);
         c->k0.last_dc_blocks = da.n_blk;
     }
-    hipLaunchKernelGGL((c->k0.resample ? resample : convert)[c->k0.dc != 0u][c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
+    if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
+        const K0AgcArgs &ga = c->k0.aga;
+        hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->S), dim3(WM_K0_THREADS), 0, c->stream, ga);
+        c->k0.last_dc_blocks = ga.n_blk;
+    }
+    const auto &stage = c->k0.agc ? (c->k0.resample ? resample_agc : convert_agc) : (c->k0.resample ? resample : convert);
+    hipLaunchKernelGGL(stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
                        c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
@@ -1464,7 +1500,7 @@ long wmbus_read_tap(wmbus_ctx *c, const char *what, int chain, unsigned stream, 
 long wmbus_read_resampled(wmbus_ctx *c, unsigned stream, uint8_t *out, size_t cap)
 {
     if (!c || !out || stream >= c->S) return WMBUS_EINVAL;
-    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples, converts, shifts or removes the input's DC (cfg.input_rate_hz, input_shift_hz, input_dc, input_format, input_gain_q8)");
+    if (!c->cfg.keep_taps || !c->k0.on) return fail(c, WMBUS_EINVAL, "read_resampled: needs cfg.keep_taps and a context that resamples, converts, shifts, removes the input's DC or levels it (cfg.input_rate_hz, input_shift_hz, input_dc, input_agc, input_format, input_gain_q8)");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_resampled: collect the push first");
     const size_t n = std::min(cap, c->k0.last_bytes);
     HIPCHK(c, hipSetDevice(c->cfg.device));

@@ -49,6 +49,15 @@
  * loop that fills the LDS span, in the history hand-over (the carried history holds x') and in k0_convert_block.  The two samples of
  * a k0_load2 and the samples of a conversion lane's 16 bytes share a level block (index within the push >> 9): one table read per
  * group.  DC = false compiles to exactly the code there was: every line of the blocker sits behind if constexpr (DC).
+ *
+ * Per-block AGC (cfg.input_agc; the contract is in include/wmbus_hip.h): the fourth template parameter AG of both block functions, and
+ * one small kernel in front of them, behind the blocker's two where there is a blocker (it needs x').  k0_agc_gain takes the peak
+ * P = max(|x'_I| + |x'_Q|) of each level block -- one wave per block, 16-byte loads, the wave reduced with __shfl_xor -- and leaves
+ * g = clamp(floor((96 << U) / max(P, 1)), 1, 65535) per block as one uint16 in K0Args.agc_tab.  It is stateless: FSK has a constant
+ * envelope, a block's own peak is the estimate, nothing is carried.  The output stage takes g from the table instead of cfg.input_gain_q8:
+ * k0_convert_block once per lane group (its samples share a level block, as they share dc), the resampler per output, from the level
+ * block of that output's newest input sample.  g differs from lane to lane, so the product is always the 64-bit one.  AG = false compiles
+ * to exactly the code there was: every line of the AGC sits behind if constexpr (AG).
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -69,6 +78,7 @@
 #define WM_K0_CONV_UNROLL 4u       /* k0_convert_block: 16-byte loads a lane has in flight */
 #define WM_K0_DC_LOG2   9u         /* a level block of the DC blocker: 512 input samples */
 #define WM_K0_DC_MAX_R  12u
+#define WM_K0_AGC_TARGET 96u       /* a level block's peak |I| + |Q| lands on +-96 of the byte's +-127 */
 
 struct K0Args {
     const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
@@ -94,7 +104,9 @@ struct K0Args {
     const uint32_t *shift_tab;   /* [1024] {c, s} int16: rint(16384 cos / sin(2 pi i / 1024))                 */
     /* I/Q DC blocker (the DC instantiations only); all zero: none */
     const uint32_t *dc_tab;      /* [S][dc_stride] {dc_I, dc_Q} int16 of this push's level blocks (k0_dc_plan) */
-    uint32_t dc_stride;
+    uint32_t dc_stride;          /* level blocks per capture in dc_tab and agc_tab                            */
+    /* per-block AGC (the AG instantiations only); NULL: none */
+    const uint16_t *agc_tab;     /* [S][dc_stride] g of this push's level blocks (k0_agc_gain): takes gain_q8's place */
 };
 
 /* the carried state of the DC blocker, per capture */
@@ -109,6 +121,15 @@ struct K0DcArgs {
     const K0DcState *st_in;      /* [S] the state in front of this push                                       */
     K0DcState *st_out;           /* the same for the next push                                                */
     uint32_t stride, n_blk, R;
+};
+
+/* k0_agc_gain: what it reads and leaves for a push of n_blk level blocks per capture */
+struct K0AgcArgs {
+    const uint8_t *raw;          /* [S][raw_stride] the raw bytes of this push                                */
+    uint64_t raw_stride;
+    const uint32_t *dc_tab;      /* [S][stride] K0Args.dc_tab (the DC instantiations only)                    */
+    uint16_t *tab;               /* [S][stride] K0Args.agc_tab                                                */
+    uint32_t stride, n_blk;
 };
 
 /* raw bytes per sample; F + 8, the shift behind the gain product */
@@ -261,6 +282,20 @@ template <int FMT, bool SH = false> __device__ __forceinline__ uint32_t k0_byte_
     nclip += (v < 0 || v > 255) ? 1u : 0u;
     return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
+/* the same under the per-block AGC: g is the level block's, not the same in every lane, so there is no 32-bit line to stay on */
+template <int FMT, bool SH = false> __device__ __forceinline__ uint32_t k0_byte_ag(int32_t acc, uint32_t g, uint32_t &nclip)
+{
+    const int32_t v = (int32_t)(((int64_t)acc * (int64_t)g + ((int64_t)128 << k0_shift(FMT, SH))) >> k0_shift(FMT, SH));
+    nclip += (v < 0 || v > 255) ? 1u : 0u;
+    return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v);
+}
+/* U of the AGC rule: g = (96 << U) / P brings a component of size P to 96 (acc g >> (F + 8) is x g / 2^U, with or without a shift) */
+__host__ __device__ constexpr uint32_t k0_agc_u(int fmt) { return fmt == WM_K0_CS16 || fmt == WM_K0_CF32 ? 16u : 9u; }
+__host__ __device__ __forceinline__ uint32_t k0_agc_rule(uint32_t P, uint32_t U)
+{
+    const uint32_t g = (WM_K0_AGC_TARGET << U) / (P ? P : 1u);
+    return g < 1u ? 1u : g > 65535u ? 65535u : g;
+}
 __device__ __forceinline__ void k0_add(uint32_t *p, uint32_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -292,7 +327,7 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
 }
 
 /* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
-template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
+template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
     const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -381,7 +416,11 @@ template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ 
 #pragma unroll
         for (uint32_t i = 0; i < WM_K0_OPL; i++) {
             const uint32_t t = t0 + i * L;
-            if (t < ntile) ob[t] = (uint16_t)(k0_byte_g<FMT, SH>(ai[i], gain, nclip) | (k0_byte_g<FMT, SH>(aq[i], gain, nclip) << 8));
+            if (t >= ntile) continue;
+            if constexpr (AG) {                                  /* LDS sample j is input base + j of the push; for an output of the push 0 <= that < n_in */
+                const uint32_t g = a.agc_tab[(uint64_t)s * a.dc_stride + ((uint32_t)(base + (int64_t)(b0 + i * M)) >> WM_K0_DC_LOG2)];
+                ob[t] = (uint16_t)(k0_byte_ag<FMT, SH>(ai[i], g, nclip) | (k0_byte_ag<FMT, SH>(aq[i], g, nclip) << 8));
+            } else ob[t] = (uint16_t)(k0_byte_g<FMT, SH>(ai[i], gain, nclip) | (k0_byte_g<FMT, SH>(aq[i], gain, nclip) << 8));
         }
     }
     __syncthreads();
@@ -403,7 +442,7 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
  * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
  * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
  * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
-template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
@@ -429,18 +468,23 @@ template <int FMT, bool SH = false, bool DC = false> __device__ __forceinline__ 
             const uint32_t o = a.rem_prev + 2u * (t_first + i);
             uint8_t *dst = o >= a.keep_from ? rout + (o - a.keep_from) : nullptr;
             const uint32_t in[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-            if constexpr (SH || DC) {                            /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
+            if constexpr (SH || DC || AG) {                      /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
                 const uint32_t m0 = (uint32_t)a.in_first + t_first + i;
                 uint32_t r[SPL / 2u];
                 uint32_t dc = 0u;                                /* t_first + i is a multiple of SPL: the lane's samples lie in one level block */
                 if constexpr (DC) dc = a.dc_tab[(uint64_t)s * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
+                uint32_t ag = 0u;
+                if constexpr (AG) ag = a.agc_tab[(uint64_t)s * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
 #pragma unroll
                 for (uint32_t k = 0; k < SPL; k++) {
                     uint32_t y = k0_sample_of<FMT>(in, k);
                     if constexpr (DC) y = k0_sub_dc(y, dc);
                     if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k);
-                    const uint32_t pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
-                                          (k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), gain, nclip) << 8);
+                    uint32_t pair;
+                    if constexpr (AG) pair = k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), ag, nclip) |
+                                             (k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), ag, nclip) << 8);
+                    else pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
+                                (k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), gain, nclip) << 8);
                     r[k / 2u] = k & 1u ? r[k / 2u] | (pair << 16) : pair;
                 }
                 if constexpr (SPL == 8u) {
@@ -516,6 +560,39 @@ template <int FMT> __device__ __forceinline__ void k0_dc_sums_block(const K0DcAr
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) { ui += __shfl_xor(ui, m); uq += __shfl_xor(uq, m); }
     if (lane == 0) a.sums[(uint64_t)s * a.stride + blk] = K0S2{(int32_t)ui, (int32_t)uq};
+}
+
+/* Per-block AGC: g[k] of level block k of the push from its peak P = max(|x'_I| + |x'_Q|), x' behind the blocker where DC is set (the
+ * table k0_dc_plan left).  The shape of k0_dc_sums_block: blockIdx.x = four level blocks, one per wave; blockIdx.y = capture; 16 raw
+ * bytes per lane and load, all loads of a lane in flight before the first is looked at.  P <= 65536 and maxima do not depend on the
+ * order of the reduction.  Lane 0 divides (uint32: 96 << 16 < 2^32) and stores.  Lanes of a wave leave together or not at all. */
+template <int FMT, bool DC> __device__ __forceinline__ void k0_agc_gain_block(const K0AgcArgs &a)
+{
+    constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS, LOADS = (BPS << WM_K0_DC_LOG2) / (64u * 16u);
+    const uint32_t lane = threadIdx.x & 63u, blk = blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u, s = blockIdx.y;
+    if (blk >= a.n_blk) return;
+    const uint8_t *p = a.raw + (uint64_t)s * a.raw_stride + ((uint64_t)blk << WM_K0_DC_LOG2) * BPS;
+    K0U4 w[LOADS];
+#pragma unroll
+    for (uint32_t j = 0; j < LOADS; j++) w[j] = *(const K0U4 *)(p + 16u * (64u * j + lane));
+    uint32_t dc = 0u;
+    if constexpr (DC) dc = a.dc_tab[(uint64_t)s * a.stride + blk];
+    uint32_t peak = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < LOADS; j++) {
+        const uint32_t in[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
+#pragma unroll
+        for (uint32_t k = 0; k < SPL; k++) {
+            uint32_t v = k0_sample_of<FMT>(in, k);
+            if constexpr (DC) v = k0_sub_dc(v, dc);
+            const int32_t xi = (int32_t)(int16_t)(v & 0xFFFFu), xq = (int32_t)(int16_t)(v >> 16);
+            const uint32_t m = (uint32_t)(xi < 0 ? -xi : xi) + (uint32_t)(xq < 0 ? -xq : xq);
+            peak = m > peak ? m : peak;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(peak, m); peak = o > peak ? o : peak; }
+    if (lane == 0) a.tab[(uint64_t)s * a.stride + blk] = (uint16_t)k0_agc_rule(peak, k0_agc_u(FMT));
 }
 
 /* Lane i's v, the same in every lane of the wave (i is wave-uniform), and the wave's number.  On the device V_READLANE_B32 /
@@ -612,6 +689,18 @@ template <int FMT, bool SH> __global__ void __launch_bounds__(WM_K0_THREADS) k0_
 {
     __shared__ uint32_t word;
     k0_convert_block<FMT, SH, true>(a, &word);
+}
+/* cfg.input_agc: the gain kernel, and the two stages with the level block's gain in their output stage */
+template <int FMT, bool DC> __global__ void __launch_bounds__(WM_K0_THREADS) k0_agc_gain(K0AgcArgs a) { k0_agc_gain_block<FMT, DC>(a); }
+template <int FMT, bool SH, bool DC> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_agc(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, SH, DC, true>(a, k0_lds);
+}
+template <int FMT, bool SH, bool DC> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_agc(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, SH, DC, true>(a, &word);
 }
 __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {

@@ -10,6 +10,8 @@
  *                staged, by an exact integer rule (a capture tuned off the channel; no counterpart in the reference).
  *   k0_dc_sums<fmt> -> k0_dc_plan -> k0_resample_dc<fmt, shift> / k0_convert_dc<fmt, shift>  cfg.input_dc: the I/Q DC offset of a zero-IF
  *                receiver, estimated per level block of 512 input samples and subtracted where a sample is staged (no counterpart).
+ *   k0_agc_gain<fmt, dc> -> k0_resample_agc<fmt, shift, dc> / k0_convert_agc<fmt, shift, dc>  cfg.input_agc: the gain of every level block
+ *                of 512 input samples from the block's own peak, in the place of cfg.input_gain_q8 in the output stage (no counterpart).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.

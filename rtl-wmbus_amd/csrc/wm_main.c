@@ -9,7 +9,7 @@
  * reached through the C ABI in include/wmbus_hip.h.
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
- * -I sample format of the input and -g input gain in dB (converted on the GPU), -C I/Q DC blocker of the input, -l frequency offset and
+ * -I sample format of the input and -g input gain in dB or auto (converted on the GPU), -C I/Q DC blocker of the input, -l frequency offset and
  * deviation of every telegram appended to its line, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
@@ -58,6 +58,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t   (output rate / input rate = L / M in lowest terms with L <= 32, M <= 1024; at least 800k; with -P only to 1.6 MS/s)\n");
     fprintf(stdout, "\t-I cu8|cs8|cs16|cf32 sample format of the input (default cu8; cs16 and cf32 little-endian, cf32 full scale +-1.0): converted on the GPU\n");
     fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
+    fprintf(stdout, "\t-g auto the gain found on the GPU, per block of 512 input samples from the block's own peak (weak and mixed-level captures; not together with -g dB; the rssi of a line is then relative)\n");
     fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
@@ -460,7 +461,7 @@ int main(int argc, char **argv)
     wmbus_cfg cfg;
     wmbus_default_cfg(&cfg);
     cfg.max_push_bytes = 0;                                  /* 0: the mode's default, see below */
-    int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0;
+    int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0, gain_given = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
     while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:l")) != -1) {
@@ -520,12 +521,15 @@ int main(int argc, char **argv)
             break;
         }
         case 'g':
+            if (!strcmp(optarg, "auto")) { cfg.input_agc = 1; break; }
             cfg.input_gain_q8 = parse_gain_db(optarg);
             if (!cfg.input_gain_q8) { print_usage(argv[0]); return EXIT_FAILURE; }
+            gain_given = 1;
             break;
         default: print_usage(argv[0]); return EXIT_FAILURE;
         }
     }
+    if (cfg.input_agc && gain_given) { print_usage(argv[0]); return EXIT_FAILURE; }      /* -g auto takes the place of a gain in dB */
     if (getenv("WMBUS_FIXED_TS")) cfg.fixed_timestamp = 1;
     /* -d is taken unchecked like the reference takes it (rtl_wmbus.c:950).  There `-d 0` keeps every sample, exactly like
      * `-d 1` (the counter test at :1350-1352 is `++index < rate`), so that is what it means here; with -s it indexes a
