@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 #define WMBUS_BLOCK_BYTES 4096u   /* the reference consumes stdin in 4096-byte units (rtl_wmbus.c:1249,1301) */
+#define WMBUS_MAX_CHANNELS 8      /* channels of one wideband capture decoded by one context (cfg.input_channels) */
 
 enum {
     WMBUS_OK = 0,
@@ -105,6 +106,15 @@ typedef struct wmbus_cfg {
                                    WMBUS_WARN_BURSTS_DROPPED paths */
     unsigned k1_small_tile;     /* 1: the first pass of the demodulation kernel on 976-sample tiles even where the 2000-sample tile of
                                    512 threads is available (decimation 2, no -s, RSSI on demand); A/B */
+    /* 0 (default): one capture holds one channel.  C = 1 ... WMBUS_MAX_CHANNELS: every capture of the context is a wideband capture that is
+     * decoded C times, channel c shifted by input_channel_hz[c] -- signed Hz with the meaning and the range of input_shift_hz below
+     * (|f| <= Fin / 2); 0 Hz and duplicates are allowed.  The raw bytes are staged once per capture, the DC estimate and the AGC gain are
+     * taken once per capture, in front of the rotation; the contract is below under CHANNELS.  input_shift_hz must be 0 with channels, C
+     * above WMBUS_MAX_CHANNELS and a shift beyond Fin / 2 are WMBUS_EINVAL.  0 is in every respect the context without these two fields:
+     * the same kernels, buffers and bytes.  (The newest fields: in front of
+     * k1_tiles_per_block, so that every field from there on -- the input stage's among them -- keeps its place from the end of the struct.) */
+    unsigned input_channels;
+    int input_channel_hz[WMBUS_MAX_CHANNELS];
     unsigned k1_tiles_per_block;/* consecutive tiles a block of that first pass takes, each tile's input loaded while the one before
                                    is computed (0: the default; 1: one tile per block, no prefetch) */
     /* 0 (default): off.  1: PER-BLOCK AGC -- the input gain is found on the GPU, for every level block of 512 input samples from that
@@ -121,7 +131,7 @@ typedef struct wmbus_cfg {
     /* 0 (default): off.  1: every datagram line comes with a level record (wmbus_level, wmbus_line_levels() below): the frequency offset
      * and the deviation of its telegram, measured on the GPU from the soft symbols of the preamble in front of the access code, in the
      * integer arithmetic defined below under LINE LEVELS -- the feedback cfg.input_shift_hz needs.  The lines themselves do not change.
-     * 0 is in every respect the context without this field: the same kernels, the same buffers, the same lines.  (The newest field, in front
+     * 0 is in every respect the context without this field: the same kernels, the same buffers, the same lines.  (In front
      * of the input stage's five, which close the struct.) */
     unsigned line_levels;
     /* 0 (default): the input is at decimation x 800 kHz, as the reference demands ("use a multiple of 800kHz", rtl_wmbus.c:1274-1292).
@@ -171,8 +181,9 @@ typedef struct wmbus_ctx wmbus_ctx;
 /* One datagram line as the reference prints it (t1_c1_packet_decoder.h:671-699,
  * s1_packet_decoder.h:248-269), plus the keys that define its place in stdout. */
 typedef struct wmbus_line {
-    uint32_t stream;
-    uint8_t  chain, algo, crc_ok, pad;
+    uint32_t stream;            /* the capture */
+    uint8_t  chain, algo, crc_ok;
+    uint8_t  channel;           /* cfg.input_channels: the channel of the capture the line was decoded on; 0 without channels */
     uint64_t sample;            /* global decimated-sample index of the completing chip */
     uint32_t text_off, text_len;/* into the buffer returned by wmbus_lines_text()        */
 } wmbus_line;
@@ -224,7 +235,8 @@ typedef struct wmbus_timing {
     unsigned clock_round[4], rla_round[4];   /* segments re-run in the unattended rounds, round by round (beyond the rounds enqueued: 0) */
     /* a context that resamples, shifts, removes the input's DC, levels it or converts (cfg.input_rate_hz, input_shift_hz, input_dc, input_agc, input_format, input_gain_q8): the cu8 bytes this push's input became,
      * all streams (whether the pipeline took them in this push or they wait for the next block to fill), and how many of them the
-     * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path. */
+     * clamp to 0 ... 255 changed -- the feedback an input gain needs.  Both 0 on the plain cu8 path.  With cfg.input_channels both count
+     * all channels of all captures. */
     uint64_t input_bytes_out, input_clipped;
 } wmbus_timing;
 
@@ -353,6 +365,24 @@ int  wmbus_resampler_design(unsigned in_hz, unsigned out_hz, unsigned *L, unsign
  * Host only, no device needed: the step, and (table may be NULL; cap = its int16 capacity, >= 2048) the 1024 entries {c[i], s[i]};
  * entry i + 256 is {-s[i], c[i]}.  WMBUS_EINVAL for |shift_hz| > in_hz / 2 or in_hz < 800000. */
 int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *table, size_t cap);
+/* CHANNELS (cfg.input_channels = C, cfg.input_channel_hz): several channels of one wideband capture in one context -- S1 at 868.30 MHz and
+ * T1/C1 at 868.95 MHz from one Airspy / HackRF capture, each at its own centre.  No new arithmetic: channel c of capture k is decoded
+ * EXACTLY as a context with input_shift_hz = input_channel_hz[c] and otherwise the same configuration decodes capture k -- the bytes handed
+ * to the pipeline, the lines, the level records, chips and taps.  Format, rate, gain, input_dc and input_agc combine with channels as
+ * they do with a shift; a 0 Hz channel goes through the rotating rule with step 0 (table entry 0 = {16384, 0}; cu8 / cs8 widened x 64,
+ * F = 21), which gives exactly the bytes and the clip count of the unshifted rule.  The DC estimate and the AGC gain are taken in front
+ * of the rotation: they are per capture and computed once, not per channel.
+ *   pipeline width  S = n_streams x C; pipeline stream v = k C + c.  n_streams stays the context's captures.
+ *   per capture     wmbus_stage, wmbus_device_input, max_push_bytes, the fill callback of a batch, wmbus_read_input_dc,
+ *                   wmbus_read_input_gain: `stream` is the capture k.
+ *   per pipeline stream   wmbus_read_resampled, wmbus_read_tap, wmbus_read_chips: `stream` is v.
+ *   defaults        everything the library chooses by batch width (seg_len, storage sizes, RSSI on demand) takes S.
+ *   lines           wmbus_line.stream is the capture, wmbus_line.channel the channel; captures ascending, within a capture channels
+ *                   ascending, within a channel the reference's stdout order.  dedup_twins works per (capture, channel); the level
+ *                   records follow the lines as they always do.
+ *   timing          wmbus_timing.input_bytes_out and input_clipped count all channels.
+ *   batch           wmbus_batch_* count captures and wmbus_batch_plan splits captures, as ever; each context carries all channels of its
+ *                   captures; the sink's wmbus_line.stream is the batch-wide capture, with `channel` beside it. */
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):

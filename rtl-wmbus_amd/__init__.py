@@ -34,6 +34,9 @@ def build(force=False):
     subprocess.run(["make", "-s", "-C", HERE], check=True)
 
 
+MAX_CHANNELS = 8                                    # WMBUS_MAX_CHANNELS
+
+
 class Cfg(ctypes.Structure):
     _fields_ = [("decimation", ctypes.c_uint), ("simultaneous", ctypes.c_int), ("accurate_atan", ctypes.c_int),
                 ("remove_dc", ctypes.c_int), ("t1c1_enabled", ctypes.c_int), ("s1_enabled", ctypes.c_int),
@@ -46,7 +49,9 @@ class Cfg(ctypes.Structure):
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
-                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint), ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
+                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint),
+                ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
+                ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
                 ("line_levels", ctypes.c_uint),
                 ("input_rate_hz", ctypes.c_uint), ("input_shift_hz", ctypes.c_int), ("input_dc", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
 
@@ -55,6 +60,8 @@ class Line(ctypes.Structure):
     _fields_ = [("stream", ctypes.c_uint32), ("chain", ctypes.c_uint8), ("algo", ctypes.c_uint8),
                 ("crc_ok", ctypes.c_uint8), ("pad", ctypes.c_uint8), ("sample", ctypes.c_uint64),
                 ("text_off", ctypes.c_uint32), ("text_len", ctypes.c_uint32)]
+    # wmbus_line.channel: the byte that was wmbus_line.pad (same offset and size; this mirror keeps the byte's old name as its storage)
+    channel = property(lambda self: int(self.pad))
 
 
 class Level(ctypes.Structure):
@@ -235,7 +242,8 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               seg_len=0, rla_seg_len=0, warmup_t1c1=0, warmup_s1=0, rla_lookback=0, host_threads=0, fixed_timestamp=True,
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
-              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0):
+              input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
+              input_channel_hz=None):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -260,6 +268,12 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_dc = int(input_dc)               # 0: off; R = 1 ... 12: the I/Q DC blocker, time constant 2^R x 512 input samples
     c.input_agc = int(input_agc)             # 0: off; 1: the gain of every level block of 512 input samples from its own peak (not with input_gain_q8)
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
+    # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
+    # more entries than the library takes are passed on as a count, so that wmbus_open refuses them with its message
+    hz = [int(f) for f in (input_channel_hz if input_channel_hz is not None else ())]
+    c.input_channels = len(hz)
+    for i, f in enumerate(hz[:MAX_CHANNELS]):
+        c.input_channel_hz[i] = f
     for i, v in enumerate(burst_caps or ()):
         c.burst_caps[i] = int(v)
     return c
@@ -293,7 +307,7 @@ class Batch:
         for i in range(L.wmbus_batch_contexts(self._h)):
             f, n = ctypes.c_uint(), ctypes.c_uint()
             h = L.wmbus_batch_context(self._h, i, ctypes.byref(f), ctypes.byref(n))
-            self.contexts.append((Receiver._view(h, n.value), f.value, n.value))
+            self.contexts.append((Receiver._view(h, n.value, self.cfg.input_channels), f.value, n.value))
 
     def close(self):
         if self._h:
@@ -342,7 +356,7 @@ class Batch:
                 recs = []
                 for k in range(n_lines):
                     ln = lines[k]
-                    recs.append(dict(stream=ln.stream, chain=ln.chain, algo=ln.algo, crc_ok=ln.crc_ok, sample=ln.sample,
+                    recs.append(dict(stream=ln.stream, channel=ln.channel, chain=ln.chain, algo=ln.algo, crc_ok=ln.crc_ok, sample=ln.sample,
                                      text=ctypes.string_at(text + ln.text_off, ln.text_len).decode()))
                 if self.cfg.line_levels:               # the accessor is valid during this callback: every record gets its level
                     p = ctypes.POINTER(Level)()
@@ -365,6 +379,12 @@ class Receiver:
     Keyword arguments mirror the reference's switches: decimation (-d), simultaneous (-s),
     accurate_atan (not -a), remove_dc (-o), t1c1 / s1 (not -p T / -p S), rla (-r), time2 (-t),
     show_algorithm (-v).
+
+    input_channel_hz=[f0, f1, ...] (up to MAX_CHANNELS signed offsets in Hz, spelled as input_shift_hz): every capture is a wideband
+    capture decoded once per channel.  stage() / push() / device_input() / read_input_dc() / read_input_gain() still count captures;
+    the pipeline behind the input stage is n_streams x channels wide and read_resampled() / read_tap() / read_chips() take the
+    pipeline stream v = capture * channels + channel; lines() records carry `stream` (the capture) and `channel`; run() returns one
+    text per PIPELINE STREAM v, not per capture.
     """
 
     def __init__(self, n_streams=1, **kw):
@@ -372,6 +392,7 @@ class Receiver:
         c = _make_cfg(n_streams=n_streams, **kw)
         self.cfg = c
         self.n_streams = n_streams
+        self.n_channels = max(1, int(c.input_channels))
         self._h = ctypes.c_void_p()
         rc = L.wmbus_open(ctypes.byref(c), ctypes.byref(self._h))
         if rc:
@@ -381,10 +402,10 @@ class Receiver:
             raise WmbusError(f"wmbus_open failed ({rc}): {msg}")
 
     @classmethod
-    def _view(cls, handle, n_streams):
+    def _view(cls, handle, n_streams, n_channels=1):
         """A Receiver over a context someone else owns (a wmbus_batch): never closed from here."""
         r = cls.__new__(cls)
-        r._h, r._borrowed, r.n_streams, r.cfg = ctypes.c_void_p(handle), True, n_streams, None
+        r._h, r._borrowed, r.n_streams, r.cfg, r.n_channels = ctypes.c_void_p(handle), True, n_streams, None, max(1, int(n_channels))
         return r
 
     def close(self):
@@ -429,7 +450,7 @@ class Receiver:
         sz = ctypes.c_size_t()
         t = L.wmbus_lines_text(self._h, ctypes.byref(sz))
         text = ctypes.string_at(t, sz.value) if sz.value else b""
-        return [dict(stream=p[i].stream, chain=p[i].chain, algo=p[i].algo, crc_ok=p[i].crc_ok, sample=p[i].sample,
+        return [dict(stream=p[i].stream, channel=p[i].channel, chain=p[i].chain, algo=p[i].algo, crc_ok=p[i].crc_ok, sample=p[i].sample,
                      text=text[p[i].text_off:p[i].text_off + p[i].text_len].decode()) for i in range(n)]
 
     def line_levels(self):
@@ -460,17 +481,18 @@ class Receiver:
 
     def run(self, cu8, push_bytes=None):
         """Whole capture(s) through the receiver in pushes of `push_bytes`; partial tail dropped
-        like the reference does at EOF (rtl_wmbus.c:1304-1308).  cu8: one array or a list."""
+        like the reference does at EOF (rtl_wmbus.c:1304-1308).  cu8: one array or a list.  Returns one text per capture -- with
+        input_channel_hz one per pipeline stream v = capture * channels + channel."""
         streams = [cu8] if isinstance(cu8, np.ndarray) and cu8.ndim == 1 else list(cu8)
         streams = [np.ascontiguousarray(a, dtype=np.uint8) for a in streams]
         total = streams[0].size // BLOCK_BYTES * BLOCK_BYTES
         step = push_bytes or self.cfg.max_push_bytes
-        per_stream = [[] for _ in streams]
+        per_stream = [[] for _ in range(len(streams) * self.n_channels)]
         for off in range(0, total, step):
             n = min(step, total - off)
             self.push([a[off:off + n] for a in streams])
             for ln in self.lines():
-                per_stream[ln["stream"]].append(ln["text"])
+                per_stream[ln["stream"] * self.n_channels + ln["channel"]].append(ln["text"])
         return ["".join(x) for x in per_stream]
 
     def read_tap(self, what, chain, stream, n):

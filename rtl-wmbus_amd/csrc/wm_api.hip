@@ -88,6 +88,9 @@ struct wmbus_ctx {
     uint32_t n_win = 1, fill = 0;                      /* input windows (cfg.input_windows) and the one wmbus_stage fills now */
     /* geometry */
     uint32_t d = 2, S = 1, Mcap = 0, ntiles_cap = 0, T = WM_K1_TILE2, flags = 0;
+    /* cfg.input_channels: S = NC x CH is the pipeline's width, pipeline stream v = capture * CH + channel; NC = cfg.n_streams captures own
+     * the raw windows and the level tables of K0, everything behind K0 is indexed by v.  Without channels CH = 1 and NC = S. */
+    uint32_t NC = 1, CH = 1;
     Framer fr[2];
     Owned mem;
     uint64_t in_stride = 0, n0 = 0;
@@ -99,22 +102,24 @@ struct wmbus_ctx {
      * `cur`, writes the other).  Every capture advances in lock step, so the counters live here and travel as launch arguments. */
     struct {
         bool on = false, resample = false, shift = false;  /* shift: cfg.input_shift_hz != 0, the rotating instantiations of either kernel */
+        bool chan = false;                             /* cfg.input_channels != 0: the channels instantiations (they always rotate) */
+        uint32_t steps[WMBUS_MAX_CHANNELS] = {};       /* the phase step of every channel */
         uint32_t fmt = WMBUS_FMT_CU8, bps = 2, gain = 0;   /* cfg.input_format, its raw bytes per sample, cfg.input_gain_q8 */
         uint32_t step = 0;                             /* the shift's phase advance per input sample (k0_shift_design) */
         uint32_t *d_shift_tab = nullptr;               /* [1024] {c, s} int16 */
         /* cfg.input_dc != 0: the I/Q DC blocker -- k0_dc_sums and k0_dc_plan in front of the DC instantiation of either kernel */
         uint32_t dc = 0, dc_stride = 0;                /* R; level blocks (512 input samples) of a full push */
-        K0S2 *d_dc_sums = nullptr;                     /* [S][dc_stride] */
-        uint32_t *d_dc_tab = nullptr;                  /* [S][dc_stride] {dc_I, dc_Q} int16 of the last push's level blocks */
-        K0DcState *d_dc_state = nullptr;               /* [2][S] */
+        K0S2 *d_dc_sums = nullptr;                     /* [NC][dc_stride] */
+        uint32_t *d_dc_tab = nullptr;                  /* [NC][dc_stride] {dc_I, dc_Q} int16 of the last push's level blocks */
+        K0DcState *d_dc_state = nullptr;               /* [2][NC] */
         K0DcArgs dca{};                                /* this push's arguments of the two kernels (k0_plan) */
         /* cfg.input_agc: the per-block AGC -- k0_agc_gain (behind the blocker's two) in front of the AG instantiation of either kernel */
         bool agc = false;
-        uint16_t *d_agc_tab = nullptr;                 /* [S][dc_stride] g of the last push's level blocks */
+        uint16_t *d_agc_tab = nullptr;                 /* [NC][dc_stride] g of the last push's level blocks */
         K0AgcArgs aga{};                               /* this push's arguments of k0_agc_gain (k0_plan) */
         uint32_t L = 1, M = 1, T = 16, tile = 0, lds = 0, cur = 0, rem = 0;
         uint64_t raw_stride = 0;
-        uint8_t *d_raw = nullptr;                      /* [n_win][S][raw_stride] */
+        uint8_t *d_raw = nullptr;                      /* [n_win][NC][raw_stride] */
         int16_t *d_taps = nullptr;                     /* [L][T] */
         uint32_t *d_hist = nullptr;                    /* [2][S][T - 1] {I, Q} int16 */
         uint8_t *d_rem = nullptr;                      /* [2][S][4096] */
@@ -417,7 +422,7 @@ int wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *ta
 
 long wmbus_read_input_dc(wmbus_ctx *c, unsigned stream, int16_t *iq, size_t cap_pairs)
 {
-    if (!c || stream >= c->S || !iq) return WMBUS_EINVAL;
+    if (!c || stream >= c->NC || !iq) return WMBUS_EINVAL;
     if (!c->k0.dc) return fail(c, WMBUS_EINVAL, "read_input_dc: the context was opened without cfg.input_dc");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_dc: collect the push first");
     const size_t n = std::min(cap_pairs, (size_t)c->k0.last_dc_blocks);
@@ -428,7 +433,7 @@ long wmbus_read_input_dc(wmbus_ctx *c, unsigned stream, int16_t *iq, size_t cap_
 
 long wmbus_read_input_gain(wmbus_ctx *c, unsigned stream, uint16_t *g, size_t cap)
 {
-    if (!c || stream >= c->S || !g) return WMBUS_EINVAL;
+    if (!c || stream >= c->NC || !g) return WMBUS_EINVAL;
     if (!c->k0.agc) return fail(c, WMBUS_EINVAL, "read_input_gain: the context was opened without cfg.input_agc");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_gain: collect the push first");
     const size_t n = std::min(cap, (size_t)c->k0.last_dc_blocks);
@@ -486,6 +491,16 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     auto &k = c->k0;
     k.dc = cfg->input_dc; k.agc = cfg->input_agc != 0u;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
+    static_assert(WMBUS_MAX_CHANNELS == WM_K0_MAX_CH, "K0Args.steps holds a step per channel");
+    if (cfg->input_channels > WMBUS_MAX_CHANNELS) return fail(c, WMBUS_EINVAL, "input_channels must be 0 (off) or 1 ... %d, got %u", WMBUS_MAX_CHANNELS, cfg->input_channels);
+    if (cfg->input_channels && cfg->input_shift_hz)
+        return fail(c, WMBUS_EINVAL, "input_shift_hz must be 0 with input_channels: every channel has its own shift in input_channel_hz (got input_shift_hz = %d)", cfg->input_shift_hz);
+    for (unsigned ch = 0; ch < cfg->input_channels; ch++) {
+        const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+        const char *why = k0_shift_design(fin, cfg->input_channel_hz[ch], &k.steps[ch], nullptr, 0);
+        if (why) return fail(c, WMBUS_EINVAL, "%s (input_channel_hz[%u] = %d, limit +-%u at the input rate %u)", why, ch, cfg->input_channel_hz[ch], fin / 2u, fin);
+        k.chan = true;
+    }
     if (cfg->input_shift_hz) {
         const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
         const char *why = k0_shift_design(fin, cfg->input_shift_hz, &k.step, nullptr, 0);
@@ -497,7 +512,7 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
         const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
         if (why) return fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u);
-        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32 || k.shift)
+        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32 || k.shift || k.chan)
             for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples (a shifted cu8 / cs8 sample is one): |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
                 int64_t abs_total = 0;
                 for (unsigned t = 0; t < T; t++) abs_total += std::abs((int)k0_taps[(size_t)p * T + t]);
@@ -507,8 +522,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k.tile = k0_pick_tile(L, M, T);
         if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
         k.lds = k0_lds_bytes(L, M, T, k.tile);
-    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc || k.agc) {
-        /* the native rate in another format, with a gain, with a shift, with the DC blocker or with the AGC: the conversion kernel alone */
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc || k.agc || k.chan) {
+        /* the native rate in another format, with a gain, with a shift, with the DC blocker, with the AGC or with channels: the conversion kernel alone */
         k.on = true; k.L = k.M = k.T = 1u;
         k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
@@ -523,7 +538,11 @@ static int open_geometry(wmbus_ctx *c)
 {
     const wmbus_cfg *cfg = &c->cfg;
     Framer &rla = c->fr[WMBUS_ALGO_RLA], &clk = c->fr[WMBUS_ALGO_T2A];
-    c->d = cfg->decimation; c->S = cfg->n_streams;
+    c->d = cfg->decimation;
+    c->NC = cfg->n_streams; c->CH = cfg->input_channels ? cfg->input_channels : 1u;
+    if ((uint64_t)c->NC * c->CH > 0x7FFFFFFFull / 4u)            /* 4 S decoder rows and 2 S x segments lanes are counted in 32 bits */
+        return fail(c, WMBUS_EINVAL, "n_streams x input_channels = %u x %u is more pipeline streams than a context takes", c->NC, c->CH);
+    c->S = c->NC * c->CH;                                    /* the pipeline's width: every default below that goes by batch width takes it */
     c->n_win = cfg->input_windows == 2 ? 2u : 1u;
     /* the pipeline behind K0 is sized for what a full raw push resamples (converts) to, plus the remainder in front of it */
     c->push_cap = cfg->max_push_bytes;
@@ -641,19 +660,19 @@ static int open_allocate(wmbus_ctx *c)
     A(m.dalloc(&c->d_in, (size_t)c->in_stride * c->S * c->n_win));
     A(m.dalloc(&c->d_hist, (size_t)WM_HIST_BYTES * c->S));
     if (c->k0.on) {
-        A(m.dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->S * c->n_win));
+        A(m.dalloc(&c->k0.d_raw, (size_t)c->k0.raw_stride * c->NC * c->n_win));
         if (c->k0.resample) {
             A(m.dalloc(&c->k0.d_taps, (size_t)c->k0.L * c->k0.T));
             A(m.dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
         }
         A(m.dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
-        if (c->k0.shift) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));
+        if (c->k0.shift || c->k0.chan) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));
         if (c->k0.dc) {
-            A(m.dalloc(&c->k0.d_dc_sums, (size_t)c->S * c->k0.dc_stride));
-            A(m.dalloc(&c->k0.d_dc_tab, (size_t)c->S * c->k0.dc_stride));
-            A(m.dalloc(&c->k0.d_dc_state, (size_t)2 * c->S));
+            A(m.dalloc(&c->k0.d_dc_sums, (size_t)c->NC * c->k0.dc_stride));
+            A(m.dalloc(&c->k0.d_dc_tab, (size_t)c->NC * c->k0.dc_stride));
+            A(m.dalloc(&c->k0.d_dc_state, (size_t)2 * c->NC));
         }
-        if (c->k0.agc) A(m.dalloc(&c->k0.d_agc_tab, (size_t)c->S * c->k0.dc_stride));
+        if (c->k0.agc) A(m.dalloc(&c->k0.d_agc_tab, (size_t)c->NC * c->k0.dc_stride));
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -726,9 +745,9 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemsetAsync(c->k0.d_hist, 0, (size_t)2 * c->S * (c->k0.T - 1u) * sizeof(uint32_t), c->stream));
         A(hipMemcpyAsync(c->k0.d_taps, k0_taps.data(), (size_t)c->k0.L * c->k0.T * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     }
-    if (c->k0.dc) A(hipMemsetAsync(c->k0.d_dc_state, 0, (size_t)2 * c->S * sizeof(K0DcState), c->stream));      /* started = 0: A[0] = S[0] << R */
+    if (c->k0.dc) A(hipMemsetAsync(c->k0.d_dc_state, 0, (size_t)2 * c->NC * sizeof(K0DcState), c->stream));      /* started = 0: A[0] = S[0] << R */
     std::vector<int16_t> shift_tab;
-    if (c->k0.shift) {                                       /* {c, s} per entry: the dword the kernels read */
+    if (c->k0.shift || c->k0.chan) {                         /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
         k0_shift_design(800000u, 0, nullptr, shift_tab.data(), shift_tab.size());
         A(hipMemcpyAsync(c->k0.d_shift_tab, shift_tab.data(), shift_tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
@@ -807,20 +826,20 @@ static int wm_stage_all(wmbus_ctx *c, const uint8_t *slab, size_t pitch, size_t 
 {
     if (!c || !slab) return WMBUS_EINVAL;
     if (const int rc = stage_check(c, nbytes, pitch)) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(wmbus_device_input(c, 0), c->k0.on ? c->k0.raw_stride : c->in_stride, slab, pitch, nbytes, c->S, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipMemcpy2DAsync(wmbus_device_input(c, 0), c->k0.on ? c->k0.raw_stride : c->in_stride, slab, pitch, nbytes, c->NC, hipMemcpyHostToDevice, c->copy_stream));
     return WMBUS_OK;
 }
 
 void *wmbus_device_input(wmbus_ctx *c, unsigned stream)
 {
-    if (!c || stream >= c->S) return nullptr;
-    if (c->k0.on) return c->k0.d_raw + ((size_t)c->fill * c->S + stream) * c->k0.raw_stride;      /* raw bytes: K0 fills the pipeline's window */
+    if (!c || stream >= c->NC) return nullptr;               /* by capture; a context with channels always has a K0 stage */
+    if (c->k0.on) return c->k0.d_raw + ((size_t)c->fill * c->NC + stream) * c->k0.raw_stride;     /* raw bytes: K0 fills the pipeline's window */
     return c->d_in + ((size_t)c->fill * c->S + stream) * c->in_stride + WM_HIST_BYTES;
 }
 
 int wmbus_stage(wmbus_ctx *c, unsigned stream, const uint8_t *cu8, size_t nbytes)
 {
-    if (!c || stream >= c->S || !cu8) return WMBUS_EINVAL;
+    if (!c || stream >= c->NC || !cu8) return WMBUS_EINVAL;
     if (const int rc = stage_check(c, nbytes, nbytes)) return rc;
     HIPCHK(c, hipMemcpyAsync(wmbus_device_input(c, stream), cu8, nbytes, hipMemcpyHostToDevice, c->copy_stream));
     return WMBUS_OK;
@@ -1000,7 +1019,7 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     const uint32_t n_out = (uint32_t)(out_end - k.n_out);
     const size_t total = (size_t)k.rem + 2u * (size_t)n_out, whole = total / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES;
     *ka = K0Args{};
-    ka->raw = k.d_raw + (size_t)c->fill * c->S * k.raw_stride; ka->raw_stride = k.raw_stride;
+    ka->raw = k.d_raw + (size_t)c->fill * c->NC * k.raw_stride; ka->raw_stride = k.raw_stride;
     ka->out = c->d_in + (size_t)c->fill * c->S * c->in_stride + WM_HIST_BYTES; ka->out_stride = c->in_stride;
     ka->taps = k.d_taps;
     if (k.resample) { ka->hist_in = k.d_hist + (size_t)k.cur * c->S * (k.T - 1u); ka->hist_out = k.d_hist + (size_t)(k.cur ^ 1u) * c->S * (k.T - 1u); }
@@ -1010,9 +1029,10 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     ka->L = k.L; ka->M = k.M; ka->T = k.T; ka->tile = k.tile;
     ka->gain_q8 = k.gain; ka->clipped = c->d_scalars + SC_CLIP;
     ka->step = k.step; ka->shift_tab = k.d_shift_tab;
+    if (k.chan) { ka->n_ch = c->CH; for (uint32_t ch = 0; ch < c->CH; ch++) ka->steps[ch] = k.steps[ch]; }
     if (k.dc) {                                          /* a push is whole 4096-byte blocks: whole level blocks */
         ka->dc_tab = k.d_dc_tab; ka->dc_stride = k.dc_stride;
-        k.dca = K0DcArgs{ka->raw, k.raw_stride, k.d_dc_sums, k.d_dc_tab, k.d_dc_state + (size_t)k.cur * c->S, k.d_dc_state + (size_t)(k.cur ^ 1u) * c->S,
+        k.dca = K0DcArgs{ka->raw, k.raw_stride, k.d_dc_sums, k.d_dc_tab, k.d_dc_state + (size_t)k.cur * c->NC, k.d_dc_state + (size_t)(k.cur ^ 1u) * c->NC,
                          k.dc_stride, n_in >> WM_K0_DC_LOG2, k.dc};
     }
     if (k.agc) {
@@ -1045,20 +1065,26 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
          {k0_convert_shift<WM_K0_CU8>, k0_convert_shift<WM_K0_CS8>, k0_convert_shift<WM_K0_CS16>, k0_convert_shift<WM_K0_CF32>}},
         {{k0_convert_dc<WM_K0_CU8, false>, k0_convert_dc<WM_K0_CS8, false>, k0_convert_dc<WM_K0_CS16, false>, k0_convert_dc<WM_K0_CF32, false>},
          {k0_convert_dc<WM_K0_CU8, true>, k0_convert_dc<WM_K0_CS8, true>, k0_convert_dc<WM_K0_CS16, true>, k0_convert_dc<WM_K0_CF32, true>}}};
+    /* cfg.input_channels: [WMBUS_FMT_*] -- the blocker and the AGC are runtime branches of these (K0Args.dc_tab / agc_tab); the grid's y is
+     * the pipeline stream, the level kernels' the capture */
+    void (*const resample_ch[4])(K0Args) = {k0_resample_ch<WM_K0_CU8>, k0_resample_ch<WM_K0_CS8>, k0_resample_ch<WM_K0_CS16>, k0_resample_ch<WM_K0_CF32>};
+    void (*const convert_ch[4])(K0Args) = {k0_convert_ch<WM_K0_CU8>, k0_convert_ch<WM_K0_CS8>, k0_convert_ch<WM_K0_CS16>, k0_convert_ch<WM_K0_CF32>};
     if (c->k0.dc) {                                      /* the level blocks' sums, then the recurrence over them: the table the K0 kernel subtracts */
         void (*const sums[4])(K0DcArgs) = {k0_dc_sums<WM_K0_CU8>, k0_dc_sums<WM_K0_CS8>, k0_dc_sums<WM_K0_CS16>, k0_dc_sums<WM_K0_CF32>};
         const K0DcArgs &da = c->k0.dca;
-        hipLaunchKernelGGL(sums[c->k0.fmt], dim3((da.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->S), dim3(WM_K0_THREADS), 0, c->stream, da);
-        hipLaunchKernelGGL(k0_dc_plan, dim3(c->S), dim3(128), 0, c->stream, da);
+        hipLaunchKernelGGL(sums[c->k0.fmt], dim3((da.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, da);
+        hipLaunchKernelGGL(k0_dc_plan, dim3(c->NC), dim3(128), 0, c->stream, da);
         c->k0.last_dc_blocks = da.n_blk;
     }
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
-        hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->S), dim3(WM_K0_THREADS), 0, c->stream, ga);
+        hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
         c->k0.last_dc_blocks = ga.n_blk;
     }
     const auto &stage = c->k0.agc ? (c->k0.resample ? resample_agc : convert_agc) : (c->k0.resample ? resample : convert);
-    hipLaunchKernelGGL(stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt], dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
+    void (*const kernel)(K0Args) = c->k0.chan ? (c->k0.resample ? resample_ch : convert_ch)[c->k0.fmt]
+                                              : stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt];
+    hipLaunchKernelGGL(kernel, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
                        c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;

@@ -272,7 +272,9 @@ static int decode_host(wmbus_ctx *c)
     }
     for (auto &r : all) {
         wmbus_line l{};
-        l.stream = r.stream; l.chain = r.chain; l.algo = r.algo; l.crc_ok = r.crc_ok; l.sample = r.sample;
+        /* r.stream is the pipeline stream v = capture * CH + channel (the sort above: captures ascending, channels within a capture) */
+        l.stream = r.stream / c->CH; l.channel = (uint8_t)(r.stream % c->CH);
+        l.chain = r.chain; l.algo = r.algo; l.crc_ok = r.crc_ok; l.sample = r.sample;
         l.text_off = (uint32_t)c->text.size(); l.text_len = r.len;
         c->text.append(parts[r.part].text, r.off, r.len);
         c->lines.push_back(l);

@@ -58,6 +58,17 @@
  * k0_convert_block once per lane group (its samples share a level block, as they share dc), the resampler per output, from the level
  * block of that output's newest input sample.  g differs from lane to lane, so the product is always the 64-bit one.  AG = false compiles
  * to exactly the code there was: every line of the AGC sits behind if constexpr (AG).
+ *
+ * Channels (cfg.input_channels = C; the contract is in include/wmbus_hip.h): the fifth template parameter CH of both block functions.  One
+ * raw capture feeds C pipeline streams, each with a phase step of its own.  The grid stays (tile, pipeline stream): blockIdx.y = v =
+ * capture * C + channel, and everything a stream carries -- history, remainder, output window -- is indexed by v as it always was.  The
+ * raw pointer and the rows of dc_tab / agc_tab come from capture v / C, the step from K0Args.steps[v % C]: ONE division per block, on the
+ * scalar unit (C is a launch argument), none per sample.  The rotation is always on in this form (a 0 Hz channel is step 0, table entry
+ * 0 = {16384, 0}: the bytes of the unshifted rule), so CH implies SH; every block stages its own span -- C blocks read a capture's span
+ * C times, from L2 after the first (DESIGN.md section 6 has the numbers and the form that stages once).  k0_dc_sums, k0_dc_plan and
+ * k0_agc_gain run in front of the rotation: they launch over captures.  In this form the blocker and the AGC are block-uniform runtime
+ * branches (dc_tab / agc_tab given or not) instead of instantiations of their own.  CH = false compiles to exactly the code there was:
+ * every line of the channels form sits behind if constexpr (CH), and DCX / AGX / dc_on / ag_on are then the constants DC and AG.
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -79,6 +90,7 @@
 #define WM_K0_DC_LOG2   9u         /* a level block of the DC blocker: 512 input samples */
 #define WM_K0_DC_MAX_R  12u
 #define WM_K0_AGC_TARGET 96u       /* a level block's peak |I| + |Q| lands on +-96 of the byte's +-127 */
+#define WM_K0_MAX_CH    8u         /* = WMBUS_MAX_CHANNELS of include/wmbus_hip.h */
 
 struct K0Args {
     const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
@@ -107,6 +119,10 @@ struct K0Args {
     uint32_t dc_stride;          /* level blocks per capture in dc_tab and agc_tab                            */
     /* per-block AGC (the AG instantiations only); NULL: none */
     const uint16_t *agc_tab;     /* [S][dc_stride] g of this push's level blocks (k0_agc_gain): takes gain_q8's place */
+    /* channels (the CH instantiations only); all zero: none.  With channels out, hist and rem are [S = captures x n_ch] rows, row v =
+     * capture * n_ch + channel; raw, dc_tab and agc_tab stay [captures] */
+    uint32_t n_ch;               /* channels per capture                                                      */
+    uint32_t steps[WM_K0_MAX_CH];/* the phase step of each channel: takes step's place                        */
 };
 
 /* the carried state of the DC blocker, per capture */
@@ -254,10 +270,18 @@ __device__ __forceinline__ uint32_t k0_sub_dc(uint32_t v, uint32_t dc)
 #endif
 }
 /* the staged sample v (as k0_load2 / k0_load1 left it) of stream index m, rotated */
-template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m)
+template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m, uint32_t step)
 {
     if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) v = k0_x64(v);
-    return k0_rotate(v, a.step * m, a.shift_tab);
+    return k0_rotate(v, step * m, a.shift_tab);
+}
+/* capture and phase step of pipeline stream v: the stream's own and K0Args.step, or with channels capture v / n_ch and the step of
+ * channel v % n_ch (v is blockIdx.y: block-uniform, one scalar division per block) */
+template <bool SH, bool CH> __device__ __forceinline__ void k0_capture_of(const K0Args &a, uint32_t v, uint32_t &cp, uint32_t &step)
+{
+    cp = v; step = 0u;
+    if constexpr (SH) step = a.step;
+    if constexpr (CH) { cp = v / a.n_ch; step = a.steps[v - cp * a.n_ch]; }
 }
 /* sample k of the four dwords a lane of k0_convert_block loaded, as the {I, Q} int16 pair of the unshifted rules */
 template <int FMT> __device__ __forceinline__ uint32_t k0_sample_of(const uint32_t (&in)[4], uint32_t k)
@@ -326,17 +350,26 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
     }
 }
 
-/* One block: blockIdx.x = tile, blockIdx.y = capture.  lds: k0_lds_bytes() bytes, dword aligned. */
-template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
+/* One block: blockIdx.x = tile, blockIdx.y = capture (with channels: pipeline stream, s; its capture is cp).  lds: k0_lds_bytes()
+ * bytes, dword aligned. */
+template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
+    static_assert(SH || !CH, "the channels form always rotates");
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
+    uint32_t cp, step;
+    k0_capture_of<SH, CH>(a, s, cp, step);
+    /* the channels form takes the blocker and the AGC as block-uniform runtime branches (K0Args.dc_tab / agc_tab given or not), not as
+     * instantiations of their own: DCX / AGX say whether the lines are compiled at all, dc_on / ag_on whether they run.  Without CH they
+     * are the constants DC and AG. */
+    constexpr bool DCX = DC || CH, AGX = AG || CH;
+    const bool dc_on = DC || (CH && a.dc_tab != nullptr), ag_on = AG || (CH && a.agc_tab != nullptr);
     const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
     constexpr uint32_t BPS = k0_bps(FMT);
     const uint32_t span = k0_span(L, M, T, a.tile);
     uint32_t *xs = lds;                                          /* [span] {I, Q} */
     const uint32_t *tp = lds + span;                             /* [L][k0_row(T)] tap pairs */
     uint16_t *ob = (uint16_t *)(lds + span + L * k0_row(T));     /* [tile] output {I, Q} bytes */
-    const uint8_t *raw = a.raw + (uint64_t)s * a.raw_stride;
+    const uint8_t *raw = a.raw + (uint64_t)cp * a.raw_stride;
     uint8_t *out = a.out + (uint64_t)s * a.out_stride;
     const uint32_t *hist_in = a.hist_in + (uint64_t)s * (T - 1u);
 
@@ -357,13 +390,13 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__
         if (r >= 0) {
             if (r < (int64_t)a.n_in) {                           /* n_in is even: r + 1 lies inside too */
                 k0_load2<FMT>(raw + BPS * (uint64_t)r, v0, v1);
-                if constexpr (DC) {                              /* r is even: both samples lie in one level block */
-                    const uint32_t dc = a.dc_tab[(uint64_t)s * a.dc_stride + ((uint32_t)r >> WM_K0_DC_LOG2)];
+                if constexpr (DCX) if (dc_on) {                  /* r is even: both samples lie in one level block */
+                    const uint32_t dc = a.dc_tab[(uint64_t)cp * a.dc_stride + ((uint32_t)r >> WM_K0_DC_LOG2)];
                     v0 = k0_sub_dc(v0, dc); v1 = k0_sub_dc(v1, dc);
                 }
                 if constexpr (SH) {                              /* only the low 32 bits of the stream index reach the phase */
                     const uint32_t m = (uint32_t)a.in_first + (uint32_t)r;
-                    v0 = k0_shifted<FMT>(a, v0, m); v1 = k0_shifted<FMT>(a, v1, m + 1u);
+                    v0 = k0_shifted<FMT>(a, v0, m, step); v1 = k0_shifted<FMT>(a, v1, m + 1u, step);
                 }
             }
         } else {                                                 /* r <= -2: both samples are history (the oldest slot, index -T, is never read) */
@@ -385,8 +418,8 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__
         for (uint32_t j = tid; j < T - 1u; j += nthr) {
             const uint32_t r = a.n_in - (T - 1u) + j;
             uint32_t v = k0_load1<FMT>(raw + BPS * (uint64_t)r);
-            if constexpr (DC) v = k0_sub_dc(v, a.dc_tab[(uint64_t)s * a.dc_stride + (r >> WM_K0_DC_LOG2)]);
-            if constexpr (SH) v = k0_shifted<FMT>(a, v, (uint32_t)a.in_first + r);
+            if constexpr (DCX) if (dc_on) v = k0_sub_dc(v, a.dc_tab[(uint64_t)cp * a.dc_stride + (r >> WM_K0_DC_LOG2)]);
+            if constexpr (SH) v = k0_shifted<FMT>(a, v, (uint32_t)a.in_first + r, step);
             hist_out[j] = v;
         }
         k0_carry_rem(a, s, out);
@@ -417,10 +450,13 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__
         for (uint32_t i = 0; i < WM_K0_OPL; i++) {
             const uint32_t t = t0 + i * L;
             if (t >= ntile) continue;
-            if constexpr (AG) {                                  /* LDS sample j is input base + j of the push; for an output of the push 0 <= that < n_in */
-                const uint32_t g = a.agc_tab[(uint64_t)s * a.dc_stride + ((uint32_t)(base + (int64_t)(b0 + i * M)) >> WM_K0_DC_LOG2)];
+            bool levelled = false;
+            if constexpr (AGX) if (ag_on) {                      /* LDS sample j is input base + j of the push; for an output of the push 0 <= that < n_in */
+                const uint32_t g = a.agc_tab[(uint64_t)cp * a.dc_stride + ((uint32_t)(base + (int64_t)(b0 + i * M)) >> WM_K0_DC_LOG2)];
                 ob[t] = (uint16_t)(k0_byte_ag<FMT, SH>(ai[i], g, nclip) | (k0_byte_ag<FMT, SH>(aq[i], g, nclip) << 8));
-            } else ob[t] = (uint16_t)(k0_byte_g<FMT, SH>(ai[i], gain, nclip) | (k0_byte_g<FMT, SH>(aq[i], gain, nclip) << 8));
+                levelled = true;
+            }
+            if (!levelled) ob[t] = (uint16_t)(k0_byte_g<FMT, SH>(ai[i], gain, nclip) | (k0_byte_g<FMT, SH>(aq[i], gain, nclip) << 8));
         }
     }
     __syncthreads();
@@ -442,11 +478,16 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
  * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
  * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
  * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
-template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
+    static_assert(SH || !CH, "the channels form always rotates");
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
-    const uint8_t *raw = a.raw + (uint64_t)s * a.raw_stride;
+    uint32_t cp, step;                                           /* s: pipeline stream (output, remainder); cp: its capture (raw, level tables) */
+    k0_capture_of<SH, CH>(a, s, cp, step);
+    constexpr bool DCX = DC || CH, AGX = AG || CH;               /* as in k0_resample_block_t: runtime branches in the channels form */
+    const bool dc_on = DC || (CH && a.dc_tab != nullptr), ag_on = AG || (CH && a.agc_tab != nullptr);
+    const uint8_t *raw = a.raw + (uint64_t)cp * a.raw_stride;
     uint8_t *out = a.out + (uint64_t)s * a.out_stride;
     uint8_t *rout = a.rem_out + (uint64_t)s * 4096u;
     const uint32_t t_first = blockIdx.x * a.tile;
@@ -472,18 +513,22 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false> __device__
                 const uint32_t m0 = (uint32_t)a.in_first + t_first + i;
                 uint32_t r[SPL / 2u];
                 uint32_t dc = 0u;                                /* t_first + i is a multiple of SPL: the lane's samples lie in one level block */
-                if constexpr (DC) dc = a.dc_tab[(uint64_t)s * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
+                if constexpr (DCX) if (dc_on) dc = a.dc_tab[(uint64_t)cp * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
                 uint32_t ag = 0u;
-                if constexpr (AG) ag = a.agc_tab[(uint64_t)s * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
+                if constexpr (AGX) if (ag_on) ag = a.agc_tab[(uint64_t)cp * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
 #pragma unroll
                 for (uint32_t k = 0; k < SPL; k++) {
                     uint32_t y = k0_sample_of<FMT>(in, k);
-                    if constexpr (DC) y = k0_sub_dc(y, dc);
-                    if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k);
+                    if constexpr (DCX) if (dc_on) y = k0_sub_dc(y, dc);
+                    if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k, step);
                     uint32_t pair;
-                    if constexpr (AG) pair = k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), ag, nclip) |
-                                             (k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), ag, nclip) << 8);
-                    else pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
+                    bool levelled = false;
+                    if constexpr (AGX) if (ag_on) {
+                        pair = k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), ag, nclip) |
+                               (k0_byte_ag<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), ag, nclip) << 8);
+                        levelled = true;
+                    }
+                    if (!levelled) pair = k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y & 0xFFFFu), gain, nclip) |
                                 (k0_byte_g<FMT, SH>(16384 * (int32_t)(int16_t)(y >> 16), gain, nclip) << 8);
                     r[k / 2u] = k & 1u ? r[k / 2u] | (pair << 16) : pair;
                 }
@@ -701,6 +746,19 @@ template <int FMT, bool SH, bool DC> __global__ void __launch_bounds__(WM_K0_THR
 {
     __shared__ uint32_t word;
     k0_convert_block<FMT, SH, DC, true>(a, &word);
+}
+/* cfg.input_channels: the two stages with a capture per n_ch pipeline streams and a phase step per channel; the rotation is always on,
+ * the blocker and the AGC are runtime branches on K0Args.dc_tab / agc_tab (one instantiation per format: DC x AG as template parameters
+ * were 32 more kernels and a third more compile time for the whole library) */
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_ch(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, true, false, false, true>(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_ch(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, true, false, false, true>(a, &word);
 }
 __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {

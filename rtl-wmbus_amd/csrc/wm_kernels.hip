@@ -12,6 +12,9 @@
  *                receiver, estimated per level block of 512 input samples and subtracted where a sample is staged (no counterpart).
  *   k0_agc_gain<fmt, dc> -> k0_resample_agc<fmt, shift, dc> / k0_convert_agc<fmt, shift, dc>  cfg.input_agc: the gain of every level block
  *                of 512 input samples from the block's own peak, in the place of cfg.input_gain_q8 in the output stage (no counterpart).
+ *   k0_resample_ch<fmt> / k0_convert_ch<fmt>  cfg.input_channels: the same two stages with one raw capture feeding C pipeline streams, each
+ *                rotated by its own phase step (several channels of one wideband capture; the blocker and the AGC, per capture, as runtime
+ *                branches; no counterpart).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.

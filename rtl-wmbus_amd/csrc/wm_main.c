@@ -60,6 +60,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-g dB input gain applied with that conversion, -48.2 ... 48.2 (a weak 16-bit capture wants 20 ... 40; -S prints the clipped share)\n");
     fprintf(stdout, "\t-g auto the gain found on the GPU, per block of 512 input samples from the block's own peak (weak and mixed-level captures; not together with -g dB; the rssi of a line is then relative)\n");
     fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
+    fprintf(stdout, "\t   a list (-O 325k,-325k; up to %d entries) decodes that many channels of one wideband capture at once and appends ;<channel Hz> to every line\n", WMBUS_MAX_CHANNELS);
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
@@ -220,14 +221,22 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
     return most;
 }
 
-/* -l: the line with ";offset_hz;dev_hz" in front of its newline, both fields empty for a level that could not be measured */
-static void write_line(const char *text, size_t len, const wmbus_level *lev)
+/* -l: the line with ";offset_hz;dev_hz" in front of its newline, both fields empty for a level that could not be measured.  -O with a
+ * list (chan_hz != NULL): ";<channel Hz>" of the line's channel behind that. */
+static void write_line(const char *text, size_t len, const wmbus_level *lev, const int *chan_hz)
 {
-    if (!lev) { fwrite(text, 1, len, stdout); return; }
+    if (!lev && !chan_hz) { fwrite(text, 1, len, stdout); return; }
     if (len && text[len - 1] == '\n') len--;
     fwrite(text, 1, len, stdout);
-    if (lev->n) fprintf(stdout, ";%d;%u\n", (int)lev->offset_hz, (unsigned)lev->dev_hz);
-    else fputs(";;\n", stdout);
+    if (lev && lev->n) fprintf(stdout, ";%d;%u", (int)lev->offset_hz, (unsigned)lev->dev_hz);
+    else if (lev) fputs(";;", stdout);
+    if (chan_hz) fprintf(stdout, ";%d", *chan_hz);
+    fputc('\n', stdout);
+}
+/* the channel field of a line: only a list of more than one -O entry prints it */
+static const int *line_channel_hz(const wmbus_cfg *cfg, const wmbus_line *ln)
+{
+    return cfg->input_channels > 1u ? &cfg->input_channel_hz[ln->channel] : NULL;
 }
 
 static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line *ln, size_t nl, const char *text, const wmbus_timing *t)
@@ -246,7 +255,7 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
-        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL);
+        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, line_channel_hz(&j->cfg, ln + i));
     }
     if (nl) fflush(stdout);
     pthread_mutex_unlock(&out_lock);
@@ -427,7 +436,7 @@ static int parse_devices(const char *arg, int *devs, int cap)
 }
 
 /* ---- live stream (stdin / TCP): wm_reader.c stages the bytes, this is where a push leaves -------- */
-struct live { wmbus_ctx *ctx; unsigned told; int levels; };
+struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; };
 
 static int live_push(void *user, const unsigned char *buf, size_t n)
 {
@@ -440,14 +449,14 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     if (!wmbus_get_timing(lv->ctx, &t)) report_warnings(t.warnings, &lv->told);
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
-    if (len && lv->levels) {
-        const wmbus_line *ln; const wmbus_level *lev;
+    if (len && (lv->levels || lv->cfg->input_channels > 1u)) {
+        const wmbus_line *ln; const wmbus_level *lev = NULL;
         const size_t nl = wmbus_lines(lv->ctx, &ln);
-        if (wmbus_line_levels(lv->ctx, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+        if (lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
             fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
             return -1;
         }
-        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lev + i);
+        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lev ? lev + i : NULL, line_channel_hz(lv->cfg, ln + i));
         fflush(stdout);
     } else if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
     return 0;
@@ -507,10 +516,24 @@ int main(int argc, char **argv)
             cfg.input_format = (unsigned)f;
             break;
         }
-        case 'O': {
-            int ok;
-            cfg.input_shift_hz = parse_shift(optarg, &ok);
-            if (!ok) { print_usage(argv[0]); return EXIT_FAILURE; }
+        case 'O': {                                          /* one offset, or a comma-separated list of channels, each spelled alike */
+            char item[64];
+            unsigned n = 0;
+            for (const char *p = optarg;; ) {
+                const char *comma = strchr(p, ',');
+                const size_t len = comma ? (size_t)(comma - p) : strlen(p);
+                int ok = 0;
+                if (len == 0 || len >= sizeof item || n == WMBUS_MAX_CHANNELS) { print_usage(argv[0]); return EXIT_FAILURE; }
+                memcpy(item, p, len); item[len] = 0;
+                cfg.input_channel_hz[n++] = parse_shift(item, &ok);
+                if (!ok) { print_usage(argv[0]); return EXIT_FAILURE; }
+                if (!comma) break;
+                p = comma + 1;
+            }
+            /* one entry is the shift it always was; more are the channels of a wideband capture */
+            cfg.input_shift_hz = n == 1u ? cfg.input_channel_hz[0] : 0;
+            cfg.input_channels = n == 1u ? 0u : n;
+            if (n == 1u) cfg.input_channel_hz[0] = 0;
             break;
         }
         case 'C': {
@@ -552,6 +575,12 @@ int main(int argc, char **argv)
                 (cfg.input_rate_hz ? cfg.input_rate_hz : cfg.decimation * 800000u) / 2u);
         return EXIT_FAILURE;
     }
+    for (unsigned ch = 0; ch < cfg.input_channels; ch++)
+        if (wmbus_shift_design(cfg.input_rate_hz ? cfg.input_rate_hz : cfg.decimation * 800000u, cfg.input_channel_hz[ch], NULL, NULL, 0)) {
+            fprintf(stderr, "rtl_wmbus_hip: -O %d: the offset must lie within +- half the input rate (%u Hz)\n", cfg.input_channel_hz[ch],
+                    (cfg.input_rate_hz ? cfg.input_rate_hz : cfg.decimation * 800000u) / 2u);
+            return EXIT_FAILURE;
+        }
 
     if (optind < argc) {
         /* batch mode: 2 MiB per file and push (-B overrides).  The staging is page-locked -- files x push bytes (twice that until round 5), pinned by
@@ -573,7 +602,7 @@ int main(int argc, char **argv)
     int fd = 0;
     if (tcp && (fd = open_tcp(tcp)) < 0) return EXIT_FAILURE;
 
-    struct live lv = {NULL, 0, (int)cfg.line_levels};
+    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg};
     int rc = wmbus_open(&cfg, &lv.ctx);
     if (rc) {
         fprintf(stderr, "rtl_wmbus_hip: cannot open GPU back end: %s\n", lv.ctx ? wmbus_last_error(lv.ctx) : "out of memory");
