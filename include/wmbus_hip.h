@@ -106,6 +106,15 @@ typedef struct wmbus_cfg {
                                    WMBUS_WARN_BURSTS_DROPPED paths */
     unsigned k1_small_tile;     /* 1: the first pass of the demodulation kernel on 976-sample tiles even where the 2000-sample tile of
                                    512 threads is available (decimation 2, no -s, RSSI on demand); A/B */
+    /* 0 (default): off.  1: CHANNEL SURVEY -- for every capture and every level block of 512 input samples the context computes a 512-point
+     * windowed DFT of the raw input on the GPU, in the exact integer arithmetic defined below under SPECTRUM, and accumulates per capture
+     * and bin the sum of the power and its maximum (max-hold) over all pushes; wmbus_read_spectrum() returns the arrays and
+     * wmbus_spectrum_channels() turns them into a list of channels: where the transmitters of a capture are, before anything has decoded
+     * -- the value input_shift_hz / input_channel_hz want.  The stage only reads the input: a context with the field prints the lines of
+     * the same context without it, and a cu8 context at the native rate stays on the plain path (no conversion kernel).  0 is in every
+     * respect the context without this field: the same kernels, buffers and bytes.  Anything above 1 is WMBUS_EINVAL.  (Directly in front
+     * of input_channels.) */
+    unsigned input_spectrum;
     /* 0 (default): one capture holds one channel.  C = 1 ... WMBUS_MAX_CHANNELS: every capture of the context is a wideband capture that is
      * decoded C times, channel c shifted by input_channel_hz[c] -- signed Hz with the meaning and the range of input_shift_hz below
      * (|f| <= Fin / 2); 0 Hz and duplicates are allowed.  The raw bytes are staged once per capture, the DC estimate and the AGC gain are
@@ -215,7 +224,7 @@ typedef struct wmbus_level {
 
 /* Per-push timings measured with HIP events on the library's own stream (ms). */
 typedef struct wmbus_timing {
-    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it */
+    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it, with cfg.input_spectrum the survey */
     float clock_ms;             /* IIR clock recovery + time2 framer (incl. re-runs)  */
     float rla_ms;               /* run-length framer (incl. re-runs)                  */
     float gather_ms;            /* burst extraction (and, without debug views, the RSSI of the tiles the bursts touch; with cfg.line_levels the level kernels) */
@@ -383,6 +392,55 @@ int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *t
  *   timing          wmbus_timing.input_bytes_out and input_clipped count all channels.
  *   batch           wmbus_batch_* count captures and wmbus_batch_plan splits captures, as ever; each context carries all channels of its
  *                   captures; the sink's wmbus_line.stream is the batch-wide capture, with `channel` beside it. */
+/* SPECTRUM (cfg.input_spectrum = 1; tests/spectrum_ref.py restates it in numpy and Python integers).  With x' the format's int16 sample per
+ * I and Q by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), behind the DC blocker where cfg.input_dc is
+ * set (x' = clamp(x - dc[k]), the table of I/Q DC BLOCKER below), m the sample's index within the stream and level block k = m >> 9:
+ *     v[n]  = 64 x'[512 k + n] for cu8 / cs8,  x'[512 k + n] for cs16 / cf32        n = 0 .. 511, per component (|v| <= 32768)
+ *     w[n]  = (16384 - c[2 n] + 1) >> 1      c[i] = the cosine of the shift's 1024-entry table (wmbus_shift_design); 0 .. 16384, a Hann window in Q14
+ *     y[n]  = (v[n] w[n] + 8192) >> 14                                              (>> floors; fits int16)
+ *     z     = y in bit-reversed order (9 bits); then radix-2 decimation in time, stages s = 1 .. 9, half = 2^(s-1):
+ *             for every group base g (multiple of 2^s) and j < half:  a = z[g + j], b = z[g + j + half], i = j (1024 >> s),
+ *               t_re = (b_re c[i] + b_im s[i] + 8192) >> 14,   t_im = (b_im c[i] - b_re s[i] + 8192) >> 14       (products in int64, >> floors)
+ *               z[g + j] = a + t,   z[g + j + half] = a - t                                                      (int32, nothing scaled, nothing clamped)
+ *     pw[j] = (z_re[j]^2 + z_im[j]^2) >> 16        (uint64 product; < 2^32: |z| <= sum|y| <= 2^23.5)
+ *     bin   b = (j + 256) mod 512  <->  f_b = (b - 256) Fin / 512,  Fin = cfg.input_rate_hz or decimation x 800000: ascending from -Fin / 2
+ *     sum[b] += pw (uint64),   peak[b] = max(peak[b], pw) (uint32),   blocks += 1          per capture, over all pushes since open or the last reset
+ * The twiddle multiply is the rotation rule of FREQUENCY SHIFT: t = b e^(-j 2 pi i / 1024) with the same table and the same rounding;
+ * entries 0 and 256 multiply exactly, so no stage is special.  The butterfly graph and its roundings are the definition, the schedule is
+ * not: any grouping of stages gives the same integers.  Sums and maxima of integers do not depend on the order of a reduction and a push
+ * always holds whole level blocks, so the three arrays do not depend on tile, block or push boundaries.  The stage reads the RAW bytes of
+ * the push at Fin: in front of the rotation, the resampler, the gain and the AGC, per capture (not per channel of cfg.input_channels).
+ * sum would overflow after about 2^33 full-scale level blocks (a full-scale tone on a bin centre reaches pw = 2^31, a little more; 2^42 samples); the reset
+ * is the remedy.
+ *
+ * wmbus_read_spectrum: the accumulators of one capture (`stream`), 512 entries each; any of sum / peak / blocks may be NULL.  To be called
+ * when no push is in flight (after wmbus_collect).  reset != 0 zeroes that capture's accumulators behind the read.  Returns 512, or a
+ * negative error: WMBUS_EINVAL on a context without cfg.input_spectrum.  It needs no cfg.keep_taps: it is feedback, like
+ * wmbus_read_input_dc. */
+long wmbus_read_spectrum(wmbus_ctx *ctx, unsigned stream, uint64_t *sum, uint32_t *peak, uint64_t *blocks, int reset);
+/* The channels of a survey; host only, no device needed, intermediate integers 128 bits wide.  Defaults for 0: width_hz 200000,
+ * min_ratio_q8 1024 (x 4), rel 8.  WMBUS_EINVAL for in_hz < 800000, blocks == 0 or 0 < min_ratio_q8 < 257.  Returns the hits written
+ * (at most cap), strongest first:
+ *     W   = clamp(floor(width_hz 512 / in_hz), 1, 256);   Fp = max(1, peak sorted ascending [255]);   Fm = max(1, (floor(sum[b] / blocks)) sorted ascending [255])
+ *     B[b] = sum of peak[b .. b + W)  for b = 0 .. 512 - W;   all b alive
+ *     repeat while hits < cap:  best = the alive b of the largest B (the lowest b on a tie);  stop if none, or B[best] 256 < min_ratio_q8 W Fp,
+ *                               or (not the first hit and B[best] rel < B of the first hit)
+ *        e[i] = max(0, peak[i] - Fp);  lo = best;  up to three times:  den = sum e[lo .. lo + W),  num = sum e[i] (i - 256) over the same i;
+ *            cb = floor((2 num + den) / (2 den));  nlo = clamp(cb + 256 - W / 2, 0, 512 - W);  done if nlo == lo or this was the third time, else lo = nlo
+ *        offset_hz = floor((2 num in_hz + 512 den) / (1024 den));   ratio_q8 = min(floor(B[best] 256 / (W Fp)), 2^32 - 1);   floor_peak = Fp, floor_mean = Fm
+ *        every b with |b - best| < W dies
+ * Every division floors, also for negative numerators.  den > 0 on the first trip follows from min_ratio_q8 > 256; a re-centred window
+ * without any bin above the floor (den = 0) keeps the window before it.  offset_hz has the sign and the meaning of cfg.input_shift_hz:
+ * it is the value to pass there.  The reference level is the median of the MAX-HOLD (telegrams are millisecond bursts: a mean over seconds
+ * dilutes them away), so the threshold does not move with the length of the capture.  What the defaults rest on, and what the rule cannot
+ * do: rel and the x 4 rest on four captures only -- the bundled 1.6 MS/s RTL-SDR capture (mixed by -43 ... +200 kHz: one hit each, within
+ * 1.2 bins), the synthetic three-channel 4.0 MS/s capture of the channels tests (three hits) and cu8 noise of sigma 1 ... 30 counts (none;
+ * strongest window x 1.1 of the floor).  A transmitter more than rel times weaker than the strongest hit is not reported: it cannot be
+ * told from the strongest hit's skirts (13 ... 17 dB below their carrier on those captures).  A zero-IF receiver's DC spike is a peak at
+ * 0 Hz unless cfg.input_dc removes it. */
+typedef struct wmbus_channel_hit { int32_t offset_hz; uint32_t ratio_q8; uint32_t floor_peak, floor_mean; } wmbus_channel_hit;
+int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t *peak, uint64_t blocks,
+                            unsigned width_hz, unsigned min_ratio_q8, unsigned rel, wmbus_channel_hit *out, unsigned cap);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):

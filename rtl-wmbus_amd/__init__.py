@@ -50,7 +50,7 @@ class Cfg(ctypes.Structure):
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint),
-                ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
+                ("input_spectrum", ctypes.c_uint), ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
                 ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
                 ("line_levels", ctypes.c_uint),
                 ("input_rate_hz", ctypes.c_uint), ("input_shift_hz", ctypes.c_int), ("input_dc", ctypes.c_uint), ("input_format", ctypes.c_uint), ("input_gain_q8", ctypes.c_uint)]
@@ -71,6 +71,17 @@ class Level(ctypes.Structure):
 
     def as_dict(self):
         return dict(sync_sample=int(self.sync_sample), offset_hz=int(self.offset_hz), dev_hz=int(self.dev_hz), n=int(self.n))
+
+
+class ChannelHit(ctypes.Structure):
+    """wmbus_channel_hit: one channel of a survey (wmbus_spectrum_channels)."""
+    _fields_ = [("offset_hz", ctypes.c_int32), ("ratio_q8", ctypes.c_uint32), ("floor_peak", ctypes.c_uint32), ("floor_mean", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return dict(offset_hz=int(self.offset_hz), ratio_q8=int(self.ratio_q8), floor_peak=int(self.floor_peak), floor_mean=int(self.floor_mean))
+
+
+SPECTRUM_BINS = 512
 
 
 class Timing(ctypes.Structure):
@@ -118,7 +129,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
            "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
-           "wmbus_line_levels", "wmbus_batch_line_levels"]
+           "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels"]
 
 _lib = None
 
@@ -153,6 +164,8 @@ def lib():
         L.wmbus_read_resampled.argtypes = [vp, u, vp, sz]; L.wmbus_read_resampled.restype = ctypes.c_long
         L.wmbus_read_input_dc.argtypes = [vp, u, vp, sz]; L.wmbus_read_input_dc.restype = ctypes.c_long
         L.wmbus_read_input_gain.argtypes = [vp, u, vp, sz]; L.wmbus_read_input_gain.restype = ctypes.c_long
+        L.wmbus_read_spectrum.argtypes = [vp, u, vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]; L.wmbus_read_spectrum.restype = ctypes.c_long
+        L.wmbus_spectrum_channels.argtypes = [u, vp, vp, ctypes.c_uint64, u, u, u, ctypes.POINTER(ChannelHit), u]
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -201,6 +214,19 @@ def shift_design(in_hz, shift_hz):
     return step.value, table
 
 
+def spectrum_channels(in_hz, total, peak, blocks, width_hz=0, min_ratio_q8=0, rel=0, cap=64):
+    """wmbus_spectrum_channels (host only): the channels of a survey -- (sum, peak, blocks) as Receiver.read_spectrum returns them -- as a
+    list of dicts offset_hz (the value input_shift_hz / input_channel_hz want), ratio_q8, floor_peak, floor_mean, strongest first.  0 takes
+    the library's default (width 200 kHz, ratio x 4, rel 8); raises WmbusError where the library refuses."""
+    total = np.ascontiguousarray(total, np.uint64); peak = np.ascontiguousarray(peak, np.uint32)
+    assert total.size == SPECTRUM_BINS and peak.size == SPECTRUM_BINS
+    out = (ChannelHit * max(1, int(cap)))()
+    n = lib().wmbus_spectrum_channels(int(in_hz), total.ctypes.data, peak.ctypes.data, int(blocks), int(width_hz), int(min_ratio_q8), int(rel), out, int(cap))
+    if n < 0:
+        raise WmbusError(f"wmbus_spectrum_channels failed: {n}")
+    return [out[i].as_dict() for i in range(n)]
+
+
 def pinned_array(nbytes):
     """uint8 numpy array over page-locked host memory (kept alive by the array's base object)."""
     p = lib().wmbus_alloc_pinned(nbytes)
@@ -243,7 +269,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
-              input_channel_hz=None):
+              input_channel_hz=None, input_spectrum=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -267,6 +293,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_shift_hz = int(input_shift_hz)   # signed Hz from the capture's centre to the channel (0: the capture is centred on it)
     c.input_dc = int(input_dc)               # 0: off; R = 1 ... 12: the I/Q DC blocker, time constant 2^R x 512 input samples
     c.input_agc = int(input_agc)             # 0: off; 1: the gain of every level block of 512 input samples from its own peak (not with input_gain_q8)
+    c.input_spectrum = int(input_spectrum)   # 1: the channel survey -- a max-hold spectrum of every capture: Receiver.read_spectrum(), spectrum_channels()
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
     # more entries than the library takes are passed on as a count, so that wmbus_open refuses them with its message
@@ -531,6 +558,16 @@ class Receiver:
         if r < 0:
             raise WmbusError(f"read_input_gain failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
         return out[:r]
+
+    def read_spectrum(self, stream, reset=False):
+        """(sum uint64 [512], peak uint32 [512], blocks): the survey of capture `stream` over every push since the context was opened or
+        the capture's accumulators were last reset (a context with input_spectrum); bin b lies at (b - 256) Fin / 512.  Call it when no
+        push is in flight; reset=True zeroes the capture's accumulators behind the read."""
+        total, peak, blocks = np.zeros(SPECTRUM_BINS, np.uint64), np.zeros(SPECTRUM_BINS, np.uint32), ctypes.c_uint64()
+        r = lib().wmbus_read_spectrum(self._h, stream, total.ctypes.data, peak.ctypes.data, ctypes.byref(blocks), int(bool(reset)))
+        if r < 0:
+            raise WmbusError(f"read_spectrum failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
+        return total, peak, int(blocks.value)
 
     def resampler_launches(self):
         return int(lib().wmbus_resampler_launches(self._h))

@@ -31,6 +31,7 @@
 #include "wm_dev.h"
 #include "wm_kernels.hip"
 #include "wm_resample_design.h"
+#include "wm_spectrum_channels.h"
 
 namespace {
 
@@ -129,6 +130,15 @@ struct wmbus_ctx {
         uint64_t last_out = 0;                         /* bytes the last push produced, all captures (wmbus_timing.input_bytes_out) */
         unsigned long long launches = 0;
     } k0;
+    /* cfg.input_spectrum: the channel survey (wm_k0_spectrum.h) -- k0_spectrum over the raw bytes of every push, in front of everything else
+     * (behind k0_dc_plan where there is a blocker), into accumulators that live as long as the context.  It only reads: a context on the
+     * plain cu8 path stays on it.  All nullptr without the option. */
+    struct {
+        bool on = false;
+        uint64_t *d_sum = nullptr;                     /* [NC][512] */
+        uint32_t *d_peak = nullptr;                    /* [NC][512] */
+        uint64_t *d_blocks = nullptr;                  /* [NC] */
+    } spec;
     /* device buffers */
     uint8_t *d_in = nullptr;                           /* [n_win][S][in_stride] */
     uint8_t *d_hist = nullptr;                         /* [S][4096] the input history of the next push (see k_copy_hist) */
@@ -442,6 +452,33 @@ long wmbus_read_input_gain(wmbus_ctx *c, unsigned stream, uint16_t *g, size_t ca
     return (long)n;
 }
 
+long wmbus_read_spectrum(wmbus_ctx *c, unsigned stream, uint64_t *sum, uint32_t *peak, uint64_t *blocks, int reset)
+{
+    if (!c || stream >= c->NC) return WMBUS_EINVAL;
+    if (!c->spec.on) return fail(c, WMBUS_EINVAL, "read_spectrum: the context was opened without cfg.input_spectrum");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_spectrum: collect the push first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    uint64_t *d_sum = c->spec.d_sum + (size_t)stream * WM_K0_SPEC_BINS, *d_blocks = c->spec.d_blocks + stream;
+    uint32_t *d_peak = c->spec.d_peak + (size_t)stream * WM_K0_SPEC_BINS;
+    /* on the context's own stream, which is idle behind a collect (a synchronous copy would bring the NULL stream's queue in: open_init) */
+    if (sum) HIPCHK(c, hipMemcpyAsync(sum, d_sum, WM_K0_SPEC_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (peak) HIPCHK(c, hipMemcpyAsync(peak, d_peak, WM_K0_SPEC_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (blocks) HIPCHK(c, hipMemcpyAsync(blocks, d_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (reset) {
+        HIPCHK(c, hipMemsetAsync(d_sum, 0, WM_K0_SPEC_BINS * sizeof(uint64_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(d_peak, 0, WM_K0_SPEC_BINS * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(d_blocks, 0, sizeof(uint64_t), c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return (long)WM_K0_SPEC_BINS;
+}
+
+int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t *peak, uint64_t blocks, unsigned width_hz, unsigned min_ratio_q8,
+                            unsigned rel, wmbus_channel_hit *out, unsigned cap)
+{
+    return k0_spectrum_channels(in_hz, sum, peak, blocks, width_hz, min_ratio_q8, rel, out, cap);
+}
+
 unsigned long long wmbus_resampler_launches(const wmbus_ctx *ctx) { return ctx ? ctx->k0.launches : 0ull; }
 
 const char *wmbus_last_error(const wmbus_ctx *ctx) { return ctx ? ctx->err : "null context"; }
@@ -488,6 +525,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         return fail(c, WMBUS_EINVAL, "input_agc takes the place of input_gain_q8: leave that 0 or 256 (got %u)", cfg->input_gain_q8);
     if (cfg->line_levels > 1u) return fail(c, WMBUS_EINVAL, "line_levels must be 0 or 1, got %u", cfg->line_levels);
     c->lev_on = cfg->line_levels != 0u;
+    if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
+    c->spec.on = cfg->input_spectrum != 0u;
     auto &k = c->k0;
     k.dc = cfg->input_dc; k.agc = cfg->input_agc != 0u;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
@@ -666,13 +705,18 @@ static int open_allocate(wmbus_ctx *c)
             A(m.dalloc(&c->k0.d_hist, (size_t)2 * c->S * (c->k0.T - 1u)));
         }
         A(m.dalloc(&c->k0.d_rem, (size_t)2 * c->S * WMBUS_BLOCK_BYTES));
-        if (c->k0.shift || c->k0.chan) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));
         if (c->k0.dc) {
             A(m.dalloc(&c->k0.d_dc_sums, (size_t)c->NC * c->k0.dc_stride));
             A(m.dalloc(&c->k0.d_dc_tab, (size_t)c->NC * c->k0.dc_stride));
             A(m.dalloc(&c->k0.d_dc_state, (size_t)2 * c->NC));
         }
         if (c->k0.agc) A(m.dalloc(&c->k0.d_agc_tab, (size_t)c->NC * c->k0.dc_stride));
+    }
+    if (c->k0.shift || c->k0.chan || c->spec.on) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));      /* the survey's window and twiddles are this table's */
+    if (c->spec.on) {
+        A(m.dalloc(&c->spec.d_sum, (size_t)c->NC * WM_K0_SPEC_BINS));
+        A(m.dalloc(&c->spec.d_peak, (size_t)c->NC * WM_K0_SPEC_BINS));
+        A(m.dalloc(&c->spec.d_blocks, (size_t)c->NC));
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -747,7 +791,12 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
     }
     if (c->k0.dc) A(hipMemsetAsync(c->k0.d_dc_state, 0, (size_t)2 * c->NC * sizeof(K0DcState), c->stream));      /* started = 0: A[0] = S[0] << R */
     std::vector<int16_t> shift_tab;
-    if (c->k0.shift || c->k0.chan) {                         /* {c, s} per entry: the dword the kernels read */
+    if (c->spec.on) {
+        A(hipMemsetAsync(c->spec.d_sum, 0, (size_t)c->NC * WM_K0_SPEC_BINS * sizeof(uint64_t), c->stream));
+        A(hipMemsetAsync(c->spec.d_peak, 0, (size_t)c->NC * WM_K0_SPEC_BINS * sizeof(uint32_t), c->stream));
+        A(hipMemsetAsync(c->spec.d_blocks, 0, (size_t)c->NC * sizeof(uint64_t), c->stream));
+    }
+    if (c->k0.shift || c->k0.chan || c->spec.on) {           /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
         k0_shift_design(800000u, 0, nullptr, shift_tab.data(), shift_tab.size());
         A(hipMemcpyAsync(c->k0.d_shift_tab, shift_tab.data(), shift_tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
@@ -1045,6 +1094,29 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     return whole;
 }
 
+/* cfg.input_spectrum: the survey over the `n_blk` level blocks every capture has in this push, raw bytes at raw + capture x raw_stride.  With
+ * a blocker it runs behind k0_dc_plan (it subtracts that table).  A wave takes a run of consecutive level blocks and ends with 512 64-bit
+ * atomic adds and 512 atomic maxima, which at runs of 4 cost as much as the transform (1.40 against 0.78 ms; 64 is no
+ * better than 16): runs of 16 where that still leaves a wave for every SIMD of the chip (16384 level blocks in the push), else of 4 (a live
+ * stream's single capture: 1024 level blocks per push are 256 waves then, not 64 -- there the launch is latency, not throughput). */
+#ifndef WM_K0_SPEC_RUN
+#define WM_K0_SPEC_RUN 16          /* build-time A/B (tools/build_variant.sh) */
+#endif
+static void spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, uint32_t n_blk)
+{
+    void (*const kernel[2][4])(K0SpecArgs) = {{k0_spectrum<WM_K0_CU8, false>, k0_spectrum<WM_K0_CS8, false>, k0_spectrum<WM_K0_CS16, false>, k0_spectrum<WM_K0_CF32, false>},
+                                              {k0_spectrum<WM_K0_CU8, true>, k0_spectrum<WM_K0_CS8, true>, k0_spectrum<WM_K0_CS16, true>, k0_spectrum<WM_K0_CF32, true>}};
+    K0SpecArgs a{};
+    a.raw = raw; a.raw_stride = raw_stride;
+    a.dc_tab = c->k0.dc ? c->k0.d_dc_tab : nullptr; a.dc_stride = c->k0.dc_stride;
+    a.shift_tab = c->k0.d_shift_tab;
+    a.sum = c->spec.d_sum; a.peak = c->spec.d_peak; a.blocks = c->spec.d_blocks;
+    a.n_blk = n_blk; a.run = (uint64_t)n_blk * c->NC >= 16384u ? (uint32_t)WM_K0_SPEC_RUN : 4u;
+    if (!n_blk) return;
+    const uint32_t runs = (n_blk + a.run - 1u) / a.run;
+    hipLaunchKernelGGL(kernel[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+}
+
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
 {
     /* [cfg.input_dc != 0][cfg.input_shift_hz != 0][WMBUS_FMT_*]; cfg.input_agc: the same three in the tables below */
@@ -1076,6 +1148,7 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
         hipLaunchKernelGGL(k0_dc_plan, dim3(c->NC), dim3(128), 0, c->stream, da);
         c->k0.last_dc_blocks = da.n_blk;
     }
+    if (c->spec.on) spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2);      /* per capture, in front of the rotation, behind the blocker's table */
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
         hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
@@ -1156,6 +1229,9 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             if (kc.last && kc.owner != c) HIPCHK(c, hipStreamWaitEvent(c->stream, kc.last, 0));
             HIPCHK(c, hipEventRecord(c->ev[EV_K1], c->stream));
             if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
+            /* the survey of a context on the plain cu8 path reads the device input window itself (a push of that path is whole 4096-byte
+             * blocks and always has decimated samples: this branch is taken); the context stays on the plain path */
+            else if (c->spec.on) spec_launch(c, win + WM_HIST_BYTES, c->in_stride, (uint32_t)(nbytes / 2u) >> WM_K0_DC_LOG2);
             /* The hand-over of the turn costs 0.15-0.2 ms (the next context's stream sits in an event wait on another
              * hardware queue; r03 trace: median 128 us between one K1 and the next, eight times per step = 5 % of it).
              * So the turn is handed over EARLY: a push's tiles leave in two launches, the event the next context waits for

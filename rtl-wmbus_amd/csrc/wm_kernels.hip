@@ -15,6 +15,8 @@
  *   k0_resample_ch<fmt> / k0_convert_ch<fmt>  cfg.input_channels: the same two stages with one raw capture feeding C pipeline streams, each
  *                rotated by its own phase step (several channels of one wideband capture; the blocker and the AGC, per capture, as runtime
  *                branches; no counterpart).
+ *   k0_spectrum<fmt, dc>  cfg.input_spectrum: the channel survey -- an exact integer 512-point windowed DFT of every level block of the raw
+ *                input, summed and max-held per capture and bin over the pushes of a context; reads only (no counterpart).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.
@@ -49,6 +51,7 @@
 #include "wm_exact.h"
 
 #include "wm_k0_resample.h"
+#include "wm_k0_spectrum.h"
 #include "wm_k1_demod.h"
 #include "wm_k2_common.h"
 #include "wm_k2_clock.h"

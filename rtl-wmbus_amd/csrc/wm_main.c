@@ -9,7 +9,8 @@
  * reached through the C ABI in include/wmbus_hip.h.
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
- * -I sample format of the input and -g input gain in dB or auto (converted on the GPU), -C I/Q DC blocker of the input, -l frequency offset and
+ * -I sample format of the input and -g input gain in dB or auto (converted on the GPU), -C I/Q DC blocker of the input, -w channel survey of the
+ * input (a max-hold spectrum taken on the GPU: where the transmitters are, printed to stderr as a ready-made -O), -l frequency offset and
  * deviation of every telegram appended to its line, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
@@ -63,6 +64,8 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t   a list (-O 325k,-325k; up to %d entries) decodes that many channels of one wideband capture at once and appends ;<channel Hz> to every line\n", WMBUS_MAX_CHANNELS);
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
+    fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
+    fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -261,6 +264,25 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     pthread_mutex_unlock(&out_lock);
 }
 
+/* -w: the survey of one capture of a context at the end of its input, to stderr: a line per hit and the -O that decodes them */
+static void print_spectrum(wmbus_ctx *ctx, unsigned stream, const wmbus_cfg *cfg, const char *name)
+{
+    uint64_t sum[512];
+    uint32_t peak[512];
+    uint64_t blocks = 0;
+    wmbus_channel_hit hit[WMBUS_MAX_CHANNELS];
+    const char *sep = name ? ": " : "";
+    if (!name) name = "";
+    if (wmbus_read_spectrum(ctx, stream, sum, peak, &blocks, 0) < 0) { fprintf(stderr, "rtl_wmbus_hip: %s%s%s\n", name, sep, wmbus_last_error(ctx)); return; }
+    const unsigned fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+    const int n = blocks ? wmbus_spectrum_channels(fin, sum, peak, blocks, 0, 0, 0, hit, WMBUS_MAX_CHANNELS) : 0;
+    if (n <= 0) { fprintf(stderr, "%s%sspectrum: nothing above the floor\n", name, sep); return; }
+    for (int k = 0; k < n; k++) fprintf(stderr, "%s%sspectrum: %d Hz x%.1f over the floor\n", name, sep, (int)hit[k].offset_hz, (double)hit[k].ratio_q8 / 256.0);
+    fprintf(stderr, "%s%sspectrum: -O ", name, sep);
+    for (int k = 0; k < n; k++) fprintf(stderr, "%s%d", k ? "," : "", (int)hit[k].offset_hz);
+    fputc('\n', stderr);
+}
+
 static int run_batch(struct batch_job *j)
 {
     int rc = EXIT_FAILURE;
@@ -294,6 +316,14 @@ static int run_batch(struct batch_job *j)
     if (j->stats && j->bytes_out)                            /* a converting path is active: what the gain did */
         fprintf(stderr, "rtl_wmbus_hip: device %d: input conversion: %llu of %llu bytes clipped (%.4f %%)\n", j->cfg.device, j->clipped, j->bytes_out,
                 100.0 * (double)j->clipped / (double)j->bytes_out);
+    if (j->stats && j->cfg.input_spectrum)                   /* -w: every file's survey, read from the context that served it */
+        for (unsigned i = 0; i < wmbus_batch_contexts(b); i++) {
+            unsigned first = 0, n = 0;
+            wmbus_ctx *ctx = wmbus_batch_context(b, i, &first, &n);
+            pthread_mutex_lock(&out_lock);                   /* a file's lines leave as a unit, whichever device they come from */
+            for (unsigned s = 0; ctx && s < n; s++) print_spectrum(ctx, s, &j->cfg, j->names[first + s]);
+            pthread_mutex_unlock(&out_lock);
+        }
     rc = j->lev_missing ? EXIT_FAILURE : EXIT_SUCCESS;
 out:
     if (!j->fast_exit || rc != EXIT_SUCCESS) wmbus_batch_close(b);      /* every exit path closes what it opened, unless the process is about to end anyway */
@@ -473,7 +503,7 @@ int main(int argc, char **argv)
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0, gain_given = 0;
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:l")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lw")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -505,6 +535,7 @@ int main(int argc, char **argv)
         case 'L': max_latency_ms = (unsigned)strtoul(optarg, NULL, 10); break;
         case 'S': stats = 1; break;
         case 'l': cfg.line_levels = 1; break;
+        case 'w': cfg.input_spectrum = 1; break;
         case 'F': cfg.tolerance_mode = 1; break;
         case 'R':
             cfg.input_rate_hz = parse_rate(optarg);
@@ -612,6 +643,7 @@ int main(int argc, char **argv)
     /* -f: the reference arms alarm(2) around every fread (rtl_wmbus.c:1300-1302) */
     const wm_reader_cfg rc_cfg = {fd, cfg.max_push_bytes, max_latency_ms, check_flow ? 2000u : 0u};
     const int how = wm_reader_run(&rc_cfg, live_push, &lv);
+    if (cfg.input_spectrum && how == WM_READER_EOF) print_spectrum(lv.ctx, 0, &cfg, NULL);
     wmbus_close(lv.ctx);
     if (how == WM_READER_FLOW_STOPPED) {
         fprintf(stderr, "rtl_wmbus: exiting since incoming data stopped flowing!\n");      /* rtl_wmbus.c:76 */
