@@ -104,7 +104,18 @@ typedef struct wmbus_cfg {
                                    on the GPU where it lies inside the push */
     unsigned burst_caps[4];     /* tests: burst storage {headers, chip words, packets, bytes} (0: sized from the batch), to reach the
                                    WMBUS_WARN_BURSTS_DROPPED paths */
-    unsigned k1_small_tile;     /* 1: the first pass of the demodulation kernel on 976-sample tiles even where the 2000-sample tile of
+    /* 0 (default): off.  1: AUTOMATIC FREQUENCY CORRECTION -- every capture of the context is shifted by an offset of its own, found on the
+     * GPU from that capture's own survey (the max-hold spectrum of input_spectrum, which this field switches on by itself:
+     * wmbus_read_spectrum works) and applied within the same push: the telegram that reveals the offset is decoded with it.  The
+     * nominal is input_shift_hz; input_afc_range_hz says how far from it a transmitter may lie (0: 64000 -- the +-43.4 kHz of a +-50 ppm
+     * dongle at 868 MHz, the bundled capture's own -10.3 kHz and a bin).  The arithmetic, the state carried from push to push and the
+     * limits are defined below under AFC; wmbus_read_input_afc() reads the lock.  input_afc alone switches the conversion kernel on, as
+     * a shift alone does.  WMBUS_EINVAL: input_afc above 1; together with input_channels (per-channel AFC is not offered);
+     * |input_shift_hz| + range > Fin / 2; input_afc_range_hz without input_afc.  0 is in every respect the context without these two
+     * fields: the same kernels, buffers and bytes.  (The newest fields: directly in front of k1_small_tile, nothing behind them moves.) */
+    unsigned input_afc;
+    unsigned input_afc_range_hz;
+    unsigned k1_small_tile;    /* 1: the first pass of the demodulation kernel on 976-sample tiles even where the 2000-sample tile of
                                    512 threads is available (decimation 2, no -s, RSSI on demand); A/B */
     /* 0 (default): off.  1: CHANNEL SURVEY -- for every capture and every level block of 512 input samples the context computes a 512-point
      * windowed DFT of the raw input on the GPU, in the exact integer arithmetic defined below under SPECTRUM, and accumulates per capture
@@ -441,6 +452,41 @@ long wmbus_read_spectrum(wmbus_ctx *ctx, unsigned stream, uint64_t *sum, uint32_
 typedef struct wmbus_channel_hit { int32_t offset_hz; uint32_t ratio_q8; uint32_t floor_peak, floor_mean; } wmbus_channel_hit;
 int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t *peak, uint64_t blocks,
                             unsigned width_hz, unsigned min_ratio_q8, unsigned rel, wmbus_channel_hit *out, unsigned cap);
+/* AFC (cfg.input_afc = 1, cfg.input_afc_range_hz = range, 0: 64000; the nominal is cfg.input_shift_hz; tests/afc_ref.py restates it in
+ * Python integers).  Per capture, carried from push to push: held_hz (int32, initially the nominal), locked (0), changes (0),
+ * ratio_q8 (0), base (uint32 phase, 0).  For every push of n_in input samples, after the survey has added this push's level blocks to
+ * the capture's accumulators (SPECTRUM above):
+ *     hits   = wmbus_spectrum_channels(Fin, sum, peak, blocks, 0, 0, 0, ..., cap = 8): the rule above with its defaults, strongest
+ *              first, on the accumulators as they stand now, this push included
+ *     cand   = the first hit with |offset_hz - nominal| <= range;  none: the state stays
+ *     fold cand in if locked == 0 or |cand.offset_hz - held_hz| > floor(Fin / 256):
+ *              held_hz = cand.offset_hz, ratio_q8 = cand.ratio_q8, locked = 1, changes += 1;  otherwise the state stays
+ *     step   = floor((held_hz 2^32 + Fin / 2) / Fin) mod 2^32                        (wmbus_shift_design's rule)
+ *     input sample j of this push (j = 0 .. n_in - 1) is rotated by the table entry of phase (base + step j) mod 2^32
+ *     base'  = (base + step n_in) mod 2^32
+ * Everything else of FREQUENCY SHIFT is unchanged: the index rounding, the table, the widening x 64 of cu8 / cs8 with F = 21, the clamp.
+ * floor(Fin / 256) is two survey bins: the rule's own scatter on the four mixes of the bundled capture is at most 1.2 bins (SPECTRUM),
+ * and a re-estimate inside that scatter must not move the shift.  Consequences:
+ *   - while held_hz has had one value since the stream's first sample, base = step m and the bytes are exactly those of a context with
+ *     input_shift_hz = held_hz;
+ *   - before a lock the rotation runs with the nominal's step; for nominal 0 that is step 0, table entry {16384, 0}: exactly the bytes
+ *     and the clip count of the unshifted rule, as the 0 Hz channel of CHANNELS;
+ *   - the phase is continuous across a change, the frequency is not;
+ *   - the resampler's carried history holds samples as they were rotated then;
+ *   - the DC blocker, the AGC, the gain, the formats and the resampler combine with AFC as they do with a shift.
+ * The limits:
+ *   - the result depends on how the input is cut into pushes -- the first feature of this library of which that is true (a host that
+ *     set input_shift_hz between pushes would have the same property);
+ *   - a telegram that straddles a change is rotated with two frequencies;
+ *   - telegrams in pushes before the first lock are decoded at the nominal;
+ *   - the max-hold never forgets: wmbus_read_spectrum(reset) is the remedy on a long live stream;
+ *   - one offset per capture: the strongest transmitter in range wins.
+ *
+ * wmbus_read_input_afc: the state the last push of capture `stream` was rotated with (before the first push: the initial state).  To
+ * be called when no push is in flight (after wmbus_collect).  It needs no cfg.keep_taps, like wmbus_read_input_dc.  Returns 0, or a
+ * negative error: WMBUS_EINVAL on a context without cfg.input_afc. */
+typedef struct wmbus_afc { int32_t shift_hz; uint32_t locked, changes, ratio_q8; } wmbus_afc;
+long wmbus_read_input_afc(wmbus_ctx *ctx, unsigned stream, wmbus_afc *out);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):

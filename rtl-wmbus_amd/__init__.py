@@ -49,7 +49,7 @@ class Cfg(ctypes.Structure):
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
-                ("burst_caps", ctypes.c_uint * 4), ("k1_small_tile", ctypes.c_uint),
+                ("burst_caps", ctypes.c_uint * 4), ("input_afc", ctypes.c_uint), ("input_afc_range_hz", ctypes.c_uint), ("k1_small_tile", ctypes.c_uint),
                 ("input_spectrum", ctypes.c_uint), ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
                 ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
                 ("line_levels", ctypes.c_uint),
@@ -82,6 +82,14 @@ class ChannelHit(ctypes.Structure):
 
 
 SPECTRUM_BINS = 512
+
+
+class Afc(ctypes.Structure):
+    """wmbus_afc: the lock a capture's last push was rotated with (cfg.input_afc, Receiver.read_input_afc)."""
+    _fields_ = [("shift_hz", ctypes.c_int32), ("locked", ctypes.c_uint32), ("changes", ctypes.c_uint32), ("ratio_q8", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return dict(shift_hz=int(self.shift_hz), locked=int(self.locked), changes=int(self.changes), ratio_q8=int(self.ratio_q8))
 
 
 class Timing(ctypes.Structure):
@@ -129,7 +137,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
            "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
-           "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels"]
+           "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc"]
 
 _lib = None
 
@@ -166,6 +174,7 @@ def lib():
         L.wmbus_read_input_gain.argtypes = [vp, u, vp, sz]; L.wmbus_read_input_gain.restype = ctypes.c_long
         L.wmbus_read_spectrum.argtypes = [vp, u, vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]; L.wmbus_read_spectrum.restype = ctypes.c_long
         L.wmbus_spectrum_channels.argtypes = [u, vp, vp, ctypes.c_uint64, u, u, u, ctypes.POINTER(ChannelHit), u]
+        L.wmbus_read_input_afc.argtypes = [vp, u, ctypes.POINTER(Afc)]; L.wmbus_read_input_afc.restype = ctypes.c_long
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -269,7 +278,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
-              input_channel_hz=None, input_spectrum=0):
+              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -294,6 +303,9 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.input_dc = int(input_dc)               # 0: off; R = 1 ... 12: the I/Q DC blocker, time constant 2^R x 512 input samples
     c.input_agc = int(input_agc)             # 0: off; 1: the gain of every level block of 512 input samples from its own peak (not with input_gain_q8)
     c.input_spectrum = int(input_spectrum)   # 1: the channel survey -- a max-hold spectrum of every capture: Receiver.read_spectrum(), spectrum_channels()
+    # 1: automatic frequency correction -- every capture locked to its own transmitter within input_shift_hz +- range (0: 64000 Hz),
+    # found from the capture's survey and applied within the same push: Receiver.read_input_afc()
+    c.input_afc, c.input_afc_range_hz = int(input_afc), int(input_afc_range_hz)
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
     # more entries than the library takes are passed on as a count, so that wmbus_open refuses them with its message
@@ -568,6 +580,15 @@ class Receiver:
         if r < 0:
             raise WmbusError(f"read_spectrum failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
         return total, peak, int(blocks.value)
+
+    def read_input_afc(self, stream):
+        """dict(shift_hz, locked, changes, ratio_q8): the lock the last push of capture `stream` was rotated with (a context with
+        input_afc).  Call it when no push is in flight."""
+        out = Afc()
+        r = lib().wmbus_read_input_afc(self._h, stream, ctypes.byref(out))
+        if r < 0:
+            raise WmbusError(f"read_input_afc failed: {r}: {lib().wmbus_last_error(self._h).decode()}")
+        return out.as_dict()
 
     def resampler_launches(self):
         return int(lib().wmbus_resampler_launches(self._h))

@@ -139,6 +139,15 @@ struct wmbus_ctx {
         uint32_t *d_peak = nullptr;                    /* [NC][512] */
         uint64_t *d_blocks = nullptr;                  /* [NC] */
     } spec;
+    /* cfg.input_afc: automatic frequency correction (wm_k0_afc.h) -- k0_afc_plan behind k0_spectrum and in front of the AFC form of either
+     * stage kernel.  The state is double-buffered with k0.cur like every carried state of K0.  All nullptr without the option. */
+    struct {
+        bool on = false;
+        int32_t nominal = 0; uint32_t range = 0, fin = 0;
+        K0AfcState *d_state = nullptr;                 /* [2][NC] */
+        K0AfcPush *d_push = nullptr;                   /* [NC] {step, base} of the last push */
+        K0AfcArgs args{};                              /* this push's arguments of k0_afc_plan (k0_plan) */
+    } afc;
     /* device buffers */
     uint8_t *d_in = nullptr;                           /* [n_win][S][in_stride] */
     uint8_t *d_hist = nullptr;                         /* [S][4096] the input history of the next push (see k_copy_hist) */
@@ -473,6 +482,19 @@ long wmbus_read_spectrum(wmbus_ctx *c, unsigned stream, uint64_t *sum, uint32_t 
     return (long)WM_K0_SPEC_BINS;
 }
 
+long wmbus_read_input_afc(wmbus_ctx *c, unsigned stream, wmbus_afc *out)
+{
+    if (!c || stream >= c->NC || !out) return WMBUS_EINVAL;
+    if (!c->afc.on) return fail(c, WMBUS_EINVAL, "read_input_afc: the context was opened without cfg.input_afc");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_afc: collect the push first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    K0AfcState st{};                                         /* half k0.cur: what the last push committed (before the first push: the initial state) */
+    HIPCHK(c, hipMemcpyAsync(&st, c->afc.d_state + (size_t)c->k0.cur * c->NC + stream, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out = wmbus_afc{st.held_hz, st.locked, st.changes, st.ratio_q8};
+    return 0;
+}
+
 int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t *peak, uint64_t blocks, unsigned width_hz, unsigned min_ratio_q8,
                             unsigned rel, wmbus_channel_hit *out, unsigned cap)
 {
@@ -546,12 +568,25 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         if (why) return fail(c, WMBUS_EINVAL, "%s (input_shift_hz = %d, limit +-%u at the input rate %u)", why, cfg->input_shift_hz, fin / 2u, fin);
         k.shift = true;
     }
+    if (cfg->input_afc > 1u) return fail(c, WMBUS_EINVAL, "input_afc must be 0 (off) or 1, got %u", cfg->input_afc);
+    if (cfg->input_afc_range_hz && !cfg->input_afc) return fail(c, WMBUS_EINVAL, "input_afc_range_hz = %u without input_afc", cfg->input_afc_range_hz);
+    if (cfg->input_afc) {
+        if (cfg->input_channels) return fail(c, WMBUS_EINVAL, "input_afc together with input_channels: AFC finds one offset per capture, not one per channel");
+        auto &f = c->afc;
+        f.fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+        f.nominal = cfg->input_shift_hz; f.range = cfg->input_afc_range_hz ? cfg->input_afc_range_hz : WM_K0_AFC_RANGE_HZ;
+        const int64_t reach = (int64_t)(f.nominal < 0 ? -(int64_t)f.nominal : (int64_t)f.nominal) + (int64_t)f.range;
+        if (f.fin < 800000u || 2 * reach > (int64_t)f.fin)
+            return fail(c, WMBUS_EINVAL, "input_afc: |input_shift_hz| + input_afc_range_hz = %lld lies beyond half the input rate %u", (long long)reach, f.fin);
+        f.on = true; c->spec.on = true;                          /* the survey is AFC's measurement */
+        k.shift = false;                                         /* the AFC form rotates, with a step of its own per capture and push */
+    }
     if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
         unsigned L = 0, M = 0, T = 0;
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
         const char *why = k0_design(cfg->input_rate_hz, cfg->decimation * 800000u, &L, &M, &T, k0_taps.data(), k0_taps.size());
         if (why) return fail(c, WMBUS_EINVAL, "%s (input_rate_hz = %u, output rate %u)", why, cfg->input_rate_hz, cfg->decimation * 800000u);
-        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32 || k.shift || k.chan)
+        if (k.fmt == WMBUS_FMT_CS16 || k.fmt == WMBUS_FMT_CF32 || k.shift || k.chan || c->afc.on)
             for (unsigned p = 0; p < L; p++) {                   /* 16-bit samples (a shifted cu8 / cs8 sample is one): |acc| <= 32768 sum|taps| must stay inside the kernel's int32 */
                 int64_t abs_total = 0;
                 for (unsigned t = 0; t < T; t++) abs_total += std::abs((int)k0_taps[(size_t)p * T + t]);
@@ -561,8 +596,8 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         k.tile = k0_pick_tile(L, M, T);
         if (!k.tile) return fail(c, WMBUS_EINVAL, "input_rate_hz: the resampler's tile does not fit the LDS (L = %u, M = %u, T = %u)", L, M, T);
         k.lds = k0_lds_bytes(L, M, T, k.tile);
-    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc || k.agc || k.chan) {
-        /* the native rate in another format, with a gain, with a shift, with the DC blocker, with the AGC or with channels: the conversion kernel alone */
+    } else if (cfg->input_format != WMBUS_FMT_CU8 || (cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u) || k.shift || k.dc || k.agc || k.chan || c->afc.on) {
+        /* the native rate in another format, with a gain, with a shift, with the DC blocker, with the AGC, with channels or with AFC: the conversion kernel alone */
         k.on = true; k.L = k.M = k.T = 1u;
         k.tile = WM_K0_THREADS * WM_K0_CONV_UNROLL * (16u / k.bps); k.lds = 0u;
     }
@@ -718,6 +753,10 @@ static int open_allocate(wmbus_ctx *c)
         A(m.dalloc(&c->spec.d_peak, (size_t)c->NC * WM_K0_SPEC_BINS));
         A(m.dalloc(&c->spec.d_blocks, (size_t)c->NC));
     }
+    if (c->afc.on) {
+        A(m.dalloc(&c->afc.d_state, (size_t)2 * c->NC));
+        A(m.dalloc(&c->afc.d_push, (size_t)c->NC));
+    }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_bits, (size_t)rows * (c->Mcap / 32)));
@@ -796,6 +835,12 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemsetAsync(c->spec.d_peak, 0, (size_t)c->NC * WM_K0_SPEC_BINS * sizeof(uint32_t), c->stream));
         A(hipMemsetAsync(c->spec.d_blocks, 0, (size_t)c->NC * sizeof(uint64_t), c->stream));
     }
+    std::vector<K0AfcState> afc_init;
+    if (c->afc.on) {                                         /* unlocked, at the nominal, phase 0: both halves */
+        afc_init.assign((size_t)2 * c->NC, K0AfcState{c->afc.nominal, 0u, 0u, 0u, 0u, {0u, 0u, 0u}});
+        A(hipMemcpyAsync(c->afc.d_state, afc_init.data(), afc_init.size() * sizeof(K0AfcState), hipMemcpyHostToDevice, c->stream));
+        A(hipMemsetAsync(c->afc.d_push, 0, (size_t)c->NC * sizeof(K0AfcPush), c->stream));
+    }
     if (c->k0.shift || c->k0.chan || c->spec.on) {           /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
         k0_shift_design(800000u, 0, nullptr, shift_tab.data(), shift_tab.size());
@@ -824,7 +869,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         lut[32 * WM_MAX_DECIM + n] = -sinf(phi);
     }
     A(hipMemcpyAsync(c->d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    A(hipStreamSynchronize(c->stream));                      /* k0_taps, shift_tab, init and lut leave with this function */
+    A(hipStreamSynchronize(c->stream));                      /* k0_taps, shift_tab, afc_init, init and lut leave with this function */
     if (e != hipSuccess) return fail(c, WMBUS_EDEVICE, "initialisation failed: %s", hipGetErrorString(e));
 
     c->decs.resize((size_t)c->S * 4);                        /* [stream][chain][algo] */
@@ -1088,6 +1133,11 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
         ka->agc_tab = k.d_agc_tab; ka->dc_stride = k.dc_stride;
         k.aga = K0AgcArgs{ka->raw, k.raw_stride, k.d_dc_tab, k.d_agc_tab, k.dc_stride, n_in >> WM_K0_DC_LOG2};
     }
+    if (c->afc.on) {                                     /* the dc / agc tables are runtime branches of the AFC form: dc_stride is set above where either is on */
+        ka->afc = c->afc.d_push;
+        c->afc.args = K0AfcArgs{c->spec.d_peak, c->spec.d_blocks, c->afc.d_state + (size_t)k.cur * c->NC, c->afc.d_state + (size_t)(k.cur ^ 1u) * c->NC,
+                                c->afc.d_push, c->afc.fin, c->afc.nominal, c->afc.range, n_in};
+    }
     k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
     k.last_bytes = whole; k.last_win = c->fill;
@@ -1141,6 +1191,9 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
      * the pipeline stream, the level kernels' the capture */
     void (*const resample_ch[4])(K0Args) = {k0_resample_ch<WM_K0_CU8>, k0_resample_ch<WM_K0_CS8>, k0_resample_ch<WM_K0_CS16>, k0_resample_ch<WM_K0_CF32>};
     void (*const convert_ch[4])(K0Args) = {k0_convert_ch<WM_K0_CU8>, k0_convert_ch<WM_K0_CS8>, k0_convert_ch<WM_K0_CS16>, k0_convert_ch<WM_K0_CF32>};
+    /* cfg.input_afc: [WMBUS_FMT_*] -- the blocker and the AGC are runtime branches of these too */
+    void (*const resample_afc[4])(K0Args) = {k0_resample_afc<WM_K0_CU8>, k0_resample_afc<WM_K0_CS8>, k0_resample_afc<WM_K0_CS16>, k0_resample_afc<WM_K0_CF32>};
+    void (*const convert_afc[4])(K0Args) = {k0_convert_afc<WM_K0_CU8>, k0_convert_afc<WM_K0_CS8>, k0_convert_afc<WM_K0_CS16>, k0_convert_afc<WM_K0_CF32>};
     if (c->k0.dc) {                                      /* the level blocks' sums, then the recurrence over them: the table the K0 kernel subtracts */
         void (*const sums[4])(K0DcArgs) = {k0_dc_sums<WM_K0_CU8>, k0_dc_sums<WM_K0_CS8>, k0_dc_sums<WM_K0_CS16>, k0_dc_sums<WM_K0_CF32>};
         const K0DcArgs &da = c->k0.dca;
@@ -1149,13 +1202,16 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
         c->k0.last_dc_blocks = da.n_blk;
     }
     if (c->spec.on) spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2);      /* per capture, in front of the rotation, behind the blocker's table */
+    /* cfg.input_afc: every capture's {step, base} for this push from its max-hold as it stands now, and the state commit, in ONE short launch */
+    if (c->afc.on) hipLaunchKernelGGL(k0_afc_plan, dim3(c->NC), dim3(WM_K0_AFC_THREADS), 0, c->stream, c->afc.args);
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
         hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
         c->k0.last_dc_blocks = ga.n_blk;
     }
     const auto &stage = c->k0.agc ? (c->k0.resample ? resample_agc : convert_agc) : (c->k0.resample ? resample : convert);
-    void (*const kernel)(K0Args) = c->k0.chan ? (c->k0.resample ? resample_ch : convert_ch)[c->k0.fmt]
+    void (*const kernel)(K0Args) = c->afc.on  ? (c->k0.resample ? resample_afc : convert_afc)[c->k0.fmt]
+                                   : c->k0.chan ? (c->k0.resample ? resample_ch : convert_ch)[c->k0.fmt]
                                               : stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt];
     hipLaunchKernelGGL(kernel, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
                        c->k0.resample ? c->k0.lds : 0u, c->stream, ka);

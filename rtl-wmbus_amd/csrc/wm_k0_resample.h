@@ -69,6 +69,13 @@
  * k0_agc_gain run in front of the rotation: they launch over captures.  In this form the blocker and the AGC are block-uniform runtime
  * branches (dc_tab / agc_tab given or not) instead of instantiations of their own.  CH = false compiles to exactly the code there was:
  * every line of the channels form sits behind if constexpr (CH), and DCX / AGX / dc_on / ag_on are then the constants DC and AG.
+ *
+ * AFC (cfg.input_afc; the contract is in include/wmbus_hip.h, the plan kernel in wm_k0_afc.h): the sixth template parameter AF of both block
+ * functions.  The phase step is no longer a constant of the context: k0_afc_plan, launched in front of the stage kernel of the same push,
+ * leaves {step, base} per capture in K0Args.afc, and sample j of the PUSH is rotated by the entry of phase base + step j -- the same
+ * k0_rotate, a push-local index in the place of the stream's, base in the place of 0.  k0_capture_of and k0_shifted are the two places
+ * that know.  AF implies SH; like the channels form it takes the blocker and the AGC as runtime branches (one instantiation per format
+ * and stage).  AF = false compiles to exactly the code there was: base is the constant 0 and m_first the stream's index.
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -92,8 +99,11 @@
 #define WM_K0_AGC_TARGET 96u       /* a level block's peak |I| + |Q| lands on +-96 of the byte's +-127 */
 #define WM_K0_MAX_CH    8u         /* = WMBUS_MAX_CHANNELS of include/wmbus_hip.h */
 
+/* AFC (wm_k0_afc.h): what k0_afc_plan leaves the stage kernel about one capture and one push */
+struct K0AfcPush { uint32_t step, base; };     /* the phase advance per input sample; the phase of the push's first sample */
+
 struct K0Args {
-    const uint8_t *raw;          /* [S][raw_stride] the raw cu8 of this push                                  */
+    const uint8_t *raw;         /* [S][raw_stride] the raw cu8 of this push                                  */
     uint64_t raw_stride;
     uint8_t *out;                /* [S][out_stride] first byte behind the window's history                    */
     uint64_t out_stride;
@@ -123,6 +133,8 @@ struct K0Args {
      * capture * n_ch + channel; raw, dc_tab and agc_tab stay [captures] */
     uint32_t n_ch;               /* channels per capture                                                      */
     uint32_t steps[WM_K0_MAX_CH];/* the phase step of each channel: takes step's place                        */
+    /* AFC (the AF instantiations only); NULL: none */
+    const K0AfcPush *afc;        /* [S] this push's {step, base} of every capture (k0_afc_plan): take step's place; the sample index is push-local */
 };
 
 /* the carried state of the DC blocker, per capture */
@@ -269,19 +281,24 @@ __device__ __forceinline__ uint32_t k0_sub_dc(uint32_t v, uint32_t dc)
                    k0_clamp16((int32_t)(int16_t)(v >> 16) - (int32_t)(int16_t)(dc >> 16)));
 #endif
 }
-/* the staged sample v (as k0_load2 / k0_load1 left it) of stream index m, rotated */
-template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m, uint32_t step)
+/* the staged sample v (as k0_load2 / k0_load1 left it) of stream index m, rotated; under AFC m is the index within the push and base
+ * the phase of the push's first sample (everywhere else the constant 0) */
+template <int FMT> __device__ __forceinline__ uint32_t k0_shifted(const K0Args &a, uint32_t v, uint32_t m, uint32_t step, uint32_t base = 0u)
 {
     if constexpr (FMT == WM_K0_CU8 || FMT == WM_K0_CS8) v = k0_x64(v);
-    return k0_rotate(v, step * m, a.shift_tab);
+    return k0_rotate(v, base + step * m, a.shift_tab);
 }
 /* capture and phase step of pipeline stream v: the stream's own and K0Args.step, or with channels capture v / n_ch and the step of
- * channel v % n_ch (v is blockIdx.y: block-uniform, one scalar division per block) */
-template <bool SH, bool CH> __device__ __forceinline__ void k0_capture_of(const K0Args &a, uint32_t v, uint32_t &cp, uint32_t &step)
+ * channel v % n_ch (v is blockIdx.y: block-uniform, one scalar division per block), or under AFC what k0_afc_plan left for capture v
+ * and this push: {step, base}, and m_first = 0 -- the phase is base + step x (index within the push) instead of step x (index
+ * within the stream) */
+template <bool SH, bool CH, bool AF = false> __device__ __forceinline__ void k0_capture_of(const K0Args &a, uint32_t v, uint32_t &cp, uint32_t &step, uint32_t &base,
+                                                                                          uint32_t &m_first)
 {
-    cp = v; step = 0u;
+    cp = v; step = 0u; base = 0u; m_first = (uint32_t)a.in_first;     /* only the low 32 bits of the stream index reach the phase */
     if constexpr (SH) step = a.step;
     if constexpr (CH) { cp = v / a.n_ch; step = a.steps[v - cp * a.n_ch]; }
+    if constexpr (AF) { const K0AfcPush p = a.afc[v]; step = p.step; base = p.base; m_first = 0u; }
 }
 /* sample k of the four dwords a lane of k0_convert_block loaded, as the {I, Q} int16 pair of the unshifted rules */
 template <int FMT> __device__ __forceinline__ uint32_t k0_sample_of(const uint32_t (&in)[4], uint32_t k)
@@ -352,17 +369,18 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
 
 /* One block: blockIdx.x = tile, blockIdx.y = capture (with channels: pipeline stream, s; its capture is cp).  lds: k0_lds_bytes()
  * bytes, dword aligned. */
-template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
+template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false, bool AF = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
-    static_assert(SH || !CH, "the channels form always rotates");
+    static_assert(SH || !(CH || AF), "the channels form and the AFC form always rotate");
+    static_assert(!(CH && AF), "AFC is per capture, not per channel");
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
-    uint32_t cp, step;
-    k0_capture_of<SH, CH>(a, s, cp, step);
+    uint32_t cp, step, ph0, m_first;
+    k0_capture_of<SH, CH, AF>(a, s, cp, step, ph0, m_first);
     /* the channels form takes the blocker and the AGC as block-uniform runtime branches (K0Args.dc_tab / agc_tab given or not), not as
      * instantiations of their own: DCX / AGX say whether the lines are compiled at all, dc_on / ag_on whether they run.  Without CH they
      * are the constants DC and AG. */
-    constexpr bool DCX = DC || CH, AGX = AG || CH;
-    const bool dc_on = DC || (CH && a.dc_tab != nullptr), ag_on = AG || (CH && a.agc_tab != nullptr);
+    constexpr bool DCX = DC || CH || AF, AGX = AG || CH || AF;   /* the AFC form takes both as the channels form does */
+    const bool dc_on = DC || ((CH || AF) && a.dc_tab != nullptr), ag_on = AG || ((CH || AF) && a.agc_tab != nullptr);
     const uint32_t L = a.L, M = a.M, T = a.T, gain = a.gain_q8 ? a.gain_q8 : 256u;
     constexpr uint32_t BPS = k0_bps(FMT);
     const uint32_t span = k0_span(L, M, T, a.tile);
@@ -394,9 +412,9 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = 
                     const uint32_t dc = a.dc_tab[(uint64_t)cp * a.dc_stride + ((uint32_t)r >> WM_K0_DC_LOG2)];
                     v0 = k0_sub_dc(v0, dc); v1 = k0_sub_dc(v1, dc);
                 }
-                if constexpr (SH) {                              /* only the low 32 bits of the stream index reach the phase */
-                    const uint32_t m = (uint32_t)a.in_first + (uint32_t)r;
-                    v0 = k0_shifted<FMT>(a, v0, m, step); v1 = k0_shifted<FMT>(a, v1, m + 1u, step);
+                if constexpr (SH) {
+                    const uint32_t m = m_first + (uint32_t)r;
+                    v0 = k0_shifted<FMT>(a, v0, m, step, ph0); v1 = k0_shifted<FMT>(a, v1, m + 1u, step, ph0);
                 }
             }
         } else {                                                 /* r <= -2: both samples are history (the oldest slot, index -T, is never read) */
@@ -419,7 +437,7 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = 
             const uint32_t r = a.n_in - (T - 1u) + j;
             uint32_t v = k0_load1<FMT>(raw + BPS * (uint64_t)r);
             if constexpr (DCX) if (dc_on) v = k0_sub_dc(v, a.dc_tab[(uint64_t)cp * a.dc_stride + (r >> WM_K0_DC_LOG2)]);
-            if constexpr (SH) v = k0_shifted<FMT>(a, v, (uint32_t)a.in_first + r, step);
+            if constexpr (SH) v = k0_shifted<FMT>(a, v, m_first + r, step, ph0);
             hist_out[j] = v;
         }
         k0_carry_rem(a, s, out);
@@ -478,15 +496,16 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
  * loads in flight before it converts the first; consecutive lanes load and store consecutive memory.  A push is a multiple of 4096
  * raw bytes, so n_out is a multiple of 512 and rem_prev one of 1024: every store (16, 16, 8, 4 bytes) is aligned to its size and
  * lies on one side of keep_from.  a.tile: a multiple of 8.  word: one dword of LDS for the clip count. */
-template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
+template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false, bool AF = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
-    static_assert(SH || !CH, "the channels form always rotates");
+    static_assert(SH || !(CH || AF), "the channels form and the AFC form always rotate");
+    static_assert(!(CH && AF), "AFC is per capture, not per channel");
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
-    uint32_t cp, step;                                           /* s: pipeline stream (output, remainder); cp: its capture (raw, level tables) */
-    k0_capture_of<SH, CH>(a, s, cp, step);
-    constexpr bool DCX = DC || CH, AGX = AG || CH;               /* as in k0_resample_block_t: runtime branches in the channels form */
-    const bool dc_on = DC || (CH && a.dc_tab != nullptr), ag_on = AG || (CH && a.agc_tab != nullptr);
+    uint32_t cp, step, ph0, m_first;                             /* s: pipeline stream (output, remainder); cp: its capture (raw, level tables) */
+    k0_capture_of<SH, CH, AF>(a, s, cp, step, ph0, m_first);
+    constexpr bool DCX = DC || CH || AF, AGX = AG || CH || AF;   /* as in k0_resample_block_t: runtime branches in the channels and the AFC form */
+    const bool dc_on = DC || ((CH || AF) && a.dc_tab != nullptr), ag_on = AG || ((CH || AF) && a.agc_tab != nullptr);
     const uint8_t *raw = a.raw + (uint64_t)cp * a.raw_stride;
     uint8_t *out = a.out + (uint64_t)s * a.out_stride;
     uint8_t *rout = a.rem_out + (uint64_t)s * 4096u;
@@ -510,7 +529,7 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = 
             uint8_t *dst = o >= a.keep_from ? rout + (o - a.keep_from) : nullptr;
             const uint32_t in[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
             if constexpr (SH || DC || AG) {                      /* every format alike: SPL samples -> SPL byte pairs, one store of 2 SPL bytes */
-                const uint32_t m0 = (uint32_t)a.in_first + t_first + i;
+                const uint32_t m0 = m_first + t_first + i;
                 uint32_t r[SPL / 2u];
                 uint32_t dc = 0u;                                /* t_first + i is a multiple of SPL: the lane's samples lie in one level block */
                 if constexpr (DCX) if (dc_on) dc = a.dc_tab[(uint64_t)cp * a.dc_stride + ((t_first + i) >> WM_K0_DC_LOG2)];
@@ -520,7 +539,7 @@ template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = 
                 for (uint32_t k = 0; k < SPL; k++) {
                     uint32_t y = k0_sample_of<FMT>(in, k);
                     if constexpr (DCX) if (dc_on) y = k0_sub_dc(y, dc);
-                    if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k, step);
+                    if constexpr (SH) y = k0_shifted<FMT>(a, y, m0 + k, step, ph0);
                     uint32_t pair;
                     bool levelled = false;
                     if constexpr (AGX) if (ag_on) {
@@ -759,6 +778,18 @@ template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_c
 {
     __shared__ uint32_t word;
     k0_convert_block<FMT, true, false, false, true>(a, &word);
+}
+/* cfg.input_afc: the two stages with a {step, base} per capture and push from k0_afc_plan (wm_k0_afc.h) and a push-local sample index;
+ * the rotation is always on, the blocker and the AGC are runtime branches, as in the channels form and for the same reason */
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_afc(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, true, false, false, false, true>(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_afc(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, true, false, false, false, true>(a, &word);
 }
 __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {

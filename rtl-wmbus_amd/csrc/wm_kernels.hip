@@ -17,6 +17,9 @@
  *                branches; no counterpart).
  *   k0_spectrum<fmt, dc>  cfg.input_spectrum: the channel survey -- an exact integer 512-point windowed DFT of every level block of the raw
  *                input, summed and max-held per capture and bin over the pushes of a context; reads only (no counterpart).
+ *   k0_afc_plan -> k0_resample_afc<fmt> / k0_convert_afc<fmt>  cfg.input_afc: behind k0_spectrum, one block per capture turns the
+ *                capture's max-hold into its phase step for this very push (the survey's channel rule, a range, a hysteresis); the two
+ *                stages rotate with that {step, base} and a push-local sample index (no counterpart).
  *   k1_demod2    time-parallel front end, one 976-sample tile per block: cu8 -> [+-325 kHz
  *                shift] -> integer boxcars -> decimate -> polar discriminator (exact fdlibm
  *                atan2f) -> FIR low-pass -> soft symbol; |s| -> EMA -> RSSI byte.
@@ -52,6 +55,7 @@
 
 #include "wm_k0_resample.h"
 #include "wm_k0_spectrum.h"
+#include "wm_k0_afc.h"
 #include "wm_k1_demod.h"
 #include "wm_k2_common.h"
 #include "wm_k2_clock.h"

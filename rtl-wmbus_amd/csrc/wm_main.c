@@ -10,7 +10,8 @@
  * Extensions (letters the reference does not use): -B bytes per GPU push, -L ms (a live stream's bytes never wait longer
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
  * -I sample format of the input and -g input gain in dB or auto (converted on the GPU), -C I/Q DC blocker of the input, -w channel survey of the
- * input (a max-hold spectrum taken on the GPU: where the transmitters are, printed to stderr as a ready-made -O), -l frequency offset and
+ * input (a max-hold spectrum taken on the GPU: where the transmitters are, printed to stderr as a ready-made -O), -O auto[:Hz] that offset
+ * found and applied on the GPU within the same run, per capture, -l frequency offset and
  * deviation of every telegram appended to its line, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
@@ -62,6 +63,9 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-g auto the gain found on the GPU, per block of 512 input samples from the block's own peak (weak and mixed-level captures; not together with -g dB; the rssi of a line is then relative)\n");
     fprintf(stdout, "\t-O Hz offset of the channel from the centre of the capture, signed (250k, -0.1M; rtl_sdr -f 868.70M wants -O 250k): shifted on the GPU, at most half the input rate\n");
     fprintf(stdout, "\t   a list (-O 325k,-325k; up to %d entries) decodes that many channels of one wideband capture at once and appends ;<channel Hz> to every line\n", WMBUS_MAX_CHANNELS);
+    fprintf(stdout, "\t   -O auto finds the offset on the GPU, per capture, from the capture's own spectrum, within +-64 kHz of the centre (a +-50 ppm dongle), and applies it from the push\n");
+    fprintf(stdout, "\t   that reveals it; -O auto:250k searches around 250 kHz instead.  With -v every change of the lock goes to stderr (afc: <Hz> Hz x<strength> over the floor;\n");
+    fprintf(stdout, "\t   batch mode: per file, at the end).  Not with a list.  The result depends on how the input is cut into pushes (-B)\n");
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
@@ -283,6 +287,8 @@ static void print_spectrum(wmbus_ctx *ctx, unsigned stream, const wmbus_cfg *cfg
     fputc('\n', stderr);
 }
 
+static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen);
+
 static int run_batch(struct batch_job *j)
 {
     int rc = EXIT_FAILURE;
@@ -322,6 +328,14 @@ static int run_batch(struct batch_job *j)
             wmbus_ctx *ctx = wmbus_batch_context(b, i, &first, &n);
             pthread_mutex_lock(&out_lock);                   /* a file's lines leave as a unit, whichever device they come from */
             for (unsigned s = 0; ctx && s < n; s++) print_spectrum(ctx, s, &j->cfg, j->names[first + s]);
+            pthread_mutex_unlock(&out_lock);
+        }
+    if (j->cfg.input_afc && j->cfg.show_algorithm)           /* -O auto -v: the lock every file ended with */
+        for (unsigned i = 0; i < wmbus_batch_contexts(b); i++) {
+            unsigned first = 0, n = 0;
+            wmbus_ctx *ctx = wmbus_batch_context(b, i, &first, &n);
+            pthread_mutex_lock(&out_lock);
+            for (unsigned s = 0; ctx && s < n; s++) print_afc(ctx, s, j->names[first + s], NULL);
             pthread_mutex_unlock(&out_lock);
         }
     rc = j->lev_missing ? EXIT_FAILURE : EXIT_SUCCESS;
@@ -466,7 +480,19 @@ static int parse_devices(const char *arg, int *devs, int cap)
 }
 
 /* ---- live stream (stdin / TCP): wm_reader.c stages the bytes, this is where a push leaves -------- */
-struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; };
+struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; unsigned afc_changes; };
+
+/* -O auto with -v: the lock of one capture to stderr where it has changed since `*seen` changes (NULL: print it if there is one) */
+static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen)
+{
+    wmbus_afc a;
+    const char *sep = name ? ": " : "";
+    if (!name) name = "";
+    if (wmbus_read_input_afc(ctx, stream, &a) < 0) { fprintf(stderr, "rtl_wmbus_hip: %s%s%s\n", name, sep, wmbus_last_error(ctx)); return; }
+    if (seen ? a.changes == *seen : !a.locked) return;
+    if (seen) *seen = a.changes;
+    fprintf(stderr, "%s%safc: %d Hz x%.1f over the floor\n", name, sep, (int)a.shift_hz, (double)a.ratio_q8 / 256.0);
+}
 
 static int live_push(void *user, const unsigned char *buf, size_t n)
 {
@@ -477,6 +503,7 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     if (rc) { fprintf(stderr, "rtl_wmbus_hip: %s\n", wmbus_last_error(lv->ctx)); return rc; }
     wmbus_timing t;
     if (!wmbus_get_timing(lv->ctx, &t)) report_warnings(t.warnings, &lv->told);
+    if (lv->cfg->input_afc && lv->cfg->show_algorithm) print_afc(lv->ctx, 0, NULL, &lv->afc_changes);
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
     if (len && (lv->levels || lv->cfg->input_channels > 1u)) {
@@ -550,6 +577,14 @@ int main(int argc, char **argv)
         case 'O': {                                          /* one offset, or a comma-separated list of channels, each spelled alike */
             char item[64];
             unsigned n = 0;
+            if (!strncmp(optarg, "auto", 4)) {               /* auto | auto:HZ -- AFC around the nominal; anything else behind it (a list) is a bad option */
+                int ok = 1;
+                const int nominal = optarg[4] == ':' ? parse_shift(optarg + 5, &ok) : 0;
+                if (!ok || (optarg[4] && optarg[4] != ':')) { print_usage(argv[0]); return EXIT_FAILURE; }
+                cfg.input_afc = 1; cfg.input_shift_hz = nominal; cfg.input_channels = 0;
+                break;
+            }
+            cfg.input_afc = 0;
             for (const char *p = optarg;; ) {
                 const char *comma = strchr(p, ',');
                 const size_t len = comma ? (size_t)(comma - p) : strlen(p);
@@ -633,7 +668,7 @@ int main(int argc, char **argv)
     int fd = 0;
     if (tcp && (fd = open_tcp(tcp)) < 0) return EXIT_FAILURE;
 
-    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg};
+    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg, 0};
     int rc = wmbus_open(&cfg, &lv.ctx);
     if (rc) {
         fprintf(stderr, "rtl_wmbus_hip: cannot open GPU back end: %s\n", lv.ctx ? wmbus_last_error(lv.ctx) : "out of memory");
