@@ -102,6 +102,23 @@ typedef struct wmbus_cfg {
                                    (0: 200; configs[2] lists 310 and is faster on the full pass) */
     unsigned bursts_to_host;    /* 1: every burst travels to the host packet decoders as chips (round 1's path) instead of being decoded
                                    on the GPU where it lies inside the push */
+    /* 0 (default): the survey of input_spectrum / input_afc accumulates for ever (SPECTRUM below).  A = 1 ... 31: THE SURVEY FORGETS -- the
+     * stream is cut into epochs of 2^A level blocks (2^A x 512 input samples) and the survey holds the current epoch and the one before
+     * it, between 2^A + 1 and 2^(A+1) level blocks once the stream is that long: wmbus_read_spectrum returns that view and AFC locks on
+     * it, so a transmitter that has gone silent, a receiver that drifts or one strong telegram heard once no longer hold the lock for
+     * ever.  The definition is below under SPECTRUM AGE.  WMBUS_EINVAL: above 31; without input_spectrum or input_afc.  0 is in every
+     * respect the context without this field: the same kernels, buffers and bytes.  (The newest fields, this one and the next: directly
+     * in front of burst_caps, nothing behind them moves.) */
+    unsigned input_spectrum_age;
+    /* All 0 (default): every channel of input_channels is fixed at input_channel_hz[c].  Entry c non-zero: A LOCK PER CHANNEL -- channel c
+     * of every capture carries an AFC state of its own and follows its transmitter within input_channel_hz[c] +- input_channel_afc_hz[c]
+     * Hz, by AFC's rule on the capture's survey; the meters of two channels are different devices with different errors.  Any non-zero
+     * entry switches the survey on by itself, as input_afc does; input_afc = 1 together with input_channels stays refused -- this array is
+     * the switch of a channel list.  The contract is below under CHANNEL AFC; wmbus_read_input_afc() reads the lock of pipeline stream
+     * capture x C + channel.  WMBUS_EINVAL: a non-zero entry at c >= input_channels (or without channels);
+     * |input_channel_hz[c]| + input_channel_afc_hz[c] > Fin / 2; the array together with input_afc.  All 0 is in every respect the context
+     * without this field: the same kernels, buffers and bytes. */
+    unsigned input_channel_afc_hz[WMBUS_MAX_CHANNELS];
     unsigned burst_caps[4];     /* tests: burst storage {headers, chip words, packets, bytes} (0: sized from the batch), to reach the
                                    WMBUS_WARN_BURSTS_DROPPED paths */
     /* 0 (default): off.  1: AUTOMATIC FREQUENCY CORRECTION -- every capture of the context is shifted by an offset of its own, found on the
@@ -110,7 +127,7 @@ typedef struct wmbus_cfg {
      * nominal is input_shift_hz; input_afc_range_hz says how far from it a transmitter may lie (0: 64000 -- the +-43.4 kHz of a +-50 ppm
      * dongle at 868 MHz, the bundled capture's own -10.3 kHz and a bin).  The arithmetic, the state carried from push to push and the
      * limits are defined below under AFC; wmbus_read_input_afc() reads the lock.  input_afc alone switches the conversion kernel on, as
-     * a shift alone does.  WMBUS_EINVAL: input_afc above 1; together with input_channels (per-channel AFC is not offered);
+     * a shift alone does.  WMBUS_EINVAL: input_afc above 1; together with input_channels (a channel list has input_channel_afc_hz instead);
      * |input_shift_hz| + range > Fin / 2; input_afc_range_hz without input_afc.  0 is in every respect the context without these two
      * fields: the same kernels, buffers and bytes.  (The newest fields: directly in front of k1_small_tile, nothing behind them moves.) */
     unsigned input_afc;
@@ -429,6 +446,21 @@ int  wmbus_shift_design(unsigned in_hz, int shift_hz, uint32_t *step, int16_t *t
  * negative error: WMBUS_EINVAL on a context without cfg.input_spectrum.  It needs no cfg.keep_taps: it is feedback, like
  * wmbus_read_input_dc. */
 long wmbus_read_spectrum(wmbus_ctx *ctx, unsigned stream, uint64_t *sum, uint32_t *peak, uint64_t *blocks, int reset);
+/* SPECTRUM AGE (cfg.input_spectrum_age = A, 1 ... 31; tests/afc_age_ref.py restates it).  What SPECTRUM says about "all pushes since open
+ * or the last reset", and the overflow of sum, describe the default A = 0.  With A set the survey forgets.  All captures of a context
+ * advance in lock step: K is the context's index of a level block, counted from the stream's first sample over all pushes, 64 bits wide;
+ * a reset does not restart it.  The epoch of level block K is e(K) = K >> A: E = 2^A level blocks per epoch.  After a push whose last
+ * level block is K_last, with e_now = e(K_last), the VIEW of a capture is
+ *     members  = the level blocks K <= K_last with e(K) in {e_now - 1, e_now} and K >= K_reset
+ *     sum[b]   = sum of pw[K][b] over the members (uint64),   peak[b] = max of pw[K][b] over the members (uint32),   blocks = their number
+ * with pw SPECTRUM's, unchanged, and K_reset = 0 or the level block behind the last wmbus_read_spectrum(reset) of that capture.  The view
+ * holds between E + 1 and 2 E level blocks once the stream is that long; it is a function of the stream and of K_last alone -- not of how
+ * the input was cut into pushes, nor of any grouping of level blocks on the GPU.  wmbus_read_spectrum returns the view (reset empties it),
+ * and AFC evaluates its rule on the view: where AFC says "the accumulators as they stand now", read "the view".  sum cannot overflow:
+ * it holds at most 2^32 level blocks of pw < 2^32.  wmbus_spectrum_channels takes arrays and is untouched.
+ * What is left of the limit "the max-hold never forgets" with A set: a transmitter holds the lock for at most two epochs after its last
+ * telegram, and a lock that has lost its transmitter stays where it is until another hit in range appears (the state stays, as AFC says).
+ * A push that is longer than two epochs is surveyed by its last E + 1 ... 2 E level blocks only. */
 /* The channels of a survey; host only, no device needed, intermediate integers 128 bits wide.  Defaults for 0: width_hz 200000,
  * min_ratio_q8 1024 (x 4), rel 8.  WMBUS_EINVAL for in_hz < 800000, blocks == 0 or 0 < min_ratio_q8 < 257.  Returns the hits written
  * (at most cap), strongest first:
@@ -480,11 +512,31 @@ int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t 
  *   - a telegram that straddles a change is rotated with two frequencies;
  *   - telegrams in pushes before the first lock are decoded at the nominal;
  *   - the max-hold never forgets: wmbus_read_spectrum(reset) is the remedy on a long live stream;
+ *     (that is the default, cfg.input_spectrum_age = 0; with the field set the survey holds the last two epochs: SPECTRUM AGE above)
  *   - one offset per capture: the strongest transmitter in range wins.
+ *     (a channel list has a lock per channel instead, cfg.input_channel_afc_hz: CHANNEL AFC below)
  *
  * wmbus_read_input_afc: the state the last push of capture `stream` was rotated with (before the first push: the initial state).  To
  * be called when no push is in flight (after wmbus_collect).  It needs no cfg.keep_taps, like wmbus_read_input_dc.  Returns 0, or a
  * negative error: WMBUS_EINVAL on a context without cfg.input_afc. */
+/* CHANNEL AFC (cfg.input_channel_afc_hz[c] = range of channel c, 0: the channel is fixed; tests/afc_age_ref.py restates it as a loop over
+ * AFC's rule).  There is no new arithmetic.  What AFC says about "one offset per capture: the strongest transmitter in range wins" and
+ * the refusal of input_afc with input_channels describe the per-capture switch; with the array set:
+ *   - pipeline stream v = k C + c (capture k, channel c) carries an AFC state of its own: held_hz starts at input_channel_hz[c]; locked,
+ *     changes, ratio_q8 and base at 0;
+ *   - after the survey of a push AFC's rule runs once per v, on capture k's survey (with cfg.input_spectrum_age: on its view), with
+ *     nominal = input_channel_hz[c] and range = input_channel_afc_hz[c];
+ *   - a channel with range 0 skips the search: its step is that of input_channel_hz[c] and its base runs on -- exactly the bytes of the
+ *     fixed channel of CHANNELS; wmbus_read_input_afc reads {input_channel_hz[c], 0, 0, 0} for it;
+ *   - channel c of capture k is byte for byte, line for line and state for state what a single-channel context produces on capture k
+ *     with input_shift_hz = input_channel_hz[c], input_afc = 1, input_afc_range_hz = input_channel_afc_hz[c], the same
+ *     input_spectrum_age, the same pushes and otherwise the same configuration;
+ *   - the DC estimate, the AGC gain and the survey stay per capture, taken once;
+ *   - on such a context the `stream` of wmbus_read_input_afc is v.
+ * Two channels may lock on the same transmitter (ranges may overlap; a hit is not used up).  SPECTRUM's limit carries over: a transmitter
+ * more than rel (8) times weaker than the capture's strongest hit is not reported, whichever channel it lies in, so its channel never
+ * locks and stays at its nominal.  AFC's other limits hold per channel: the cut into pushes, a telegram that straddles a change, the
+ * pushes before the first lock; there is no switch per channel other than the range, and nothing tracks within a push. */
 typedef struct wmbus_afc { int32_t shift_hz; uint32_t locked, changes, ratio_q8; } wmbus_afc;
 long wmbus_read_input_afc(wmbus_ctx *ctx, unsigned stream, wmbus_afc *out);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q

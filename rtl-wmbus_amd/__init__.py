@@ -49,6 +49,7 @@ class Cfg(ctypes.Structure):
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
+                ("input_spectrum_age", ctypes.c_uint), ("input_channel_afc_hz", ctypes.c_uint * MAX_CHANNELS),
                 ("burst_caps", ctypes.c_uint * 4), ("input_afc", ctypes.c_uint), ("input_afc_range_hz", ctypes.c_uint), ("k1_small_tile", ctypes.c_uint),
                 ("input_spectrum", ctypes.c_uint), ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
                 ("k1_tiles_per_block", ctypes.c_uint), ("input_agc", ctypes.c_uint), ("clock_waves", ctypes.c_uint),
@@ -278,7 +279,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
-              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0):
+              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -306,6 +307,12 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     # 1: automatic frequency correction -- every capture locked to its own transmitter within input_shift_hz +- range (0: 64000 Hz),
     # found from the capture's survey and applied within the same push: Receiver.read_input_afc()
     c.input_afc, c.input_afc_range_hz = int(input_afc), int(input_afc_range_hz)
+    # A = 1 ... 31: the survey forgets -- it holds the last two epochs of 2^A level blocks (2^A x 512 input samples); AFC locks on that view
+    c.input_spectrum_age = int(input_spectrum_age)
+    # a lock per channel of input_channel_hz: the AFC range of every channel in Hz, 0: that channel is fixed.  Entries beyond the
+    # library's limit are dropped here; one beyond the channel list is passed on, so that wmbus_open refuses it with its message
+    for i, r in enumerate(list(input_channel_afc_hz if input_channel_afc_hz is not None else ())[:MAX_CHANNELS]):
+        c.input_channel_afc_hz[i] = int(r)
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
     # more entries than the library takes are passed on as a count, so that wmbus_open refuses them with its message
@@ -574,7 +581,8 @@ class Receiver:
     def read_spectrum(self, stream, reset=False):
         """(sum uint64 [512], peak uint32 [512], blocks): the survey of capture `stream` over every push since the context was opened or
         the capture's accumulators were last reset (a context with input_spectrum); bin b lies at (b - 256) Fin / 512.  Call it when no
-        push is in flight; reset=True zeroes the capture's accumulators behind the read."""
+        push is in flight; reset=True zeroes the capture's accumulators behind the read.  With input_spectrum_age = A the three are the
+        VIEW: the level blocks of the stream's current epoch of 2^A level blocks and of the one before it (and behind the last reset)."""
         total, peak, blocks = np.zeros(SPECTRUM_BINS, np.uint64), np.zeros(SPECTRUM_BINS, np.uint32), ctypes.c_uint64()
         r = lib().wmbus_read_spectrum(self._h, stream, total.ctypes.data, peak.ctypes.data, ctypes.byref(blocks), int(bool(reset)))
         if r < 0:
@@ -583,7 +591,9 @@ class Receiver:
 
     def read_input_afc(self, stream):
         """dict(shift_hz, locked, changes, ratio_q8): the lock the last push of capture `stream` was rotated with (a context with
-        input_afc).  Call it when no push is in flight."""
+        input_afc).  Call it when no push is in flight.  With input_spectrum_age the lock follows the survey's last two epochs.  On a
+        context with input_channel_afc_hz `stream` is the pipeline stream capture x channels + channel; a fixed channel reads its own
+        input_channel_hz, unlocked."""
         out = Afc()
         r = lib().wmbus_read_input_afc(self._h, stream, ctypes.byref(out))
         if r < 0:

@@ -138,14 +138,25 @@ struct wmbus_ctx {
         uint64_t *d_sum = nullptr;                     /* [NC][512] */
         uint32_t *d_peak = nullptr;                    /* [NC][512] */
         uint64_t *d_blocks = nullptr;                  /* [NC] */
+        /* cfg.input_spectrum_age = A: two slots of the three arrays, {sum [NC][512] | blocks [NC] | peak [NC][512]} per slot in ONE
+         * allocation (a slot, or both, is cleared with one fill); the pointers above are slot 0's, slot 1's lie slot_stride uint64 behind.
+         * K counts the level blocks of the stream: all captures advance in lock step, a reset does not restart it. */
+        uint32_t age = 0;
+        uint64_t *d_slots = nullptr; uint64_t slot_stride = 0;
+        uint64_t K = 0;
     } spec;
     /* cfg.input_afc: automatic frequency correction (wm_k0_afc.h) -- k0_afc_plan behind k0_spectrum and in front of the AFC form of either
      * stage kernel.  The state is double-buffered with k0.cur like every carried state of K0.  All nullptr without the option. */
     struct {
         bool on = false;
         int32_t nominal = 0; uint32_t range = 0, fin = 0;
-        K0AfcState *d_state = nullptr;                 /* [2][NC] */
-        K0AfcPush *d_push = nullptr;                   /* [NC] {step, base} of the last push */
+        /* cfg.input_channel_afc_hz: a lock per channel -- a state and a push entry per pipeline stream v = capture x C + channel, the plan
+         * kernel once per v; `n` is the number of states: S with channels, NC without */
+        bool chan = false;
+        uint32_t ch_range[WMBUS_MAX_CHANNELS] = {};
+        uint32_t n = 0;
+        K0AfcState *d_state = nullptr;                 /* [2][n] */
+        K0AfcPush *d_push = nullptr;                   /* [n] {step, base} of the last push */
         K0AfcArgs args{};                              /* this push's arguments of k0_afc_plan (k0_plan) */
     } afc;
     /* device buffers */
@@ -469,6 +480,28 @@ long wmbus_read_spectrum(wmbus_ctx *c, unsigned stream, uint64_t *sum, uint32_t 
     HIPCHK(c, hipSetDevice(c->cfg.device));
     uint64_t *d_sum = c->spec.d_sum + (size_t)stream * WM_K0_SPEC_BINS, *d_blocks = c->spec.d_blocks + stream;
     uint32_t *d_peak = c->spec.d_peak + (size_t)stream * WM_K0_SPEC_BINS;
+    if (c->spec.age) {                                       /* the view: the two slots together (SPECTRUM AGE); a reset clears both */
+        const uint64_t st = c->spec.slot_stride;
+        uint64_t h_sum[2][WM_K0_SPEC_BINS], h_blocks[2];
+        uint32_t h_peak[2][WM_K0_SPEC_BINS];
+        for (unsigned sl = 0; sl < 2u; sl++) {
+            HIPCHK(c, hipMemcpyAsync(h_sum[sl], d_sum + sl * st, sizeof h_sum[sl], hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_peak[sl], d_peak + 2u * sl * st, sizeof h_peak[sl], hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&h_blocks[sl], d_blocks + sl * st, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+            if (reset) {
+                HIPCHK(c, hipMemsetAsync(d_sum + sl * st, 0, WM_K0_SPEC_BINS * sizeof(uint64_t), c->stream));
+                HIPCHK(c, hipMemsetAsync(d_peak + 2u * sl * st, 0, WM_K0_SPEC_BINS * sizeof(uint32_t), c->stream));
+                HIPCHK(c, hipMemsetAsync(d_blocks + sl * st, 0, sizeof(uint64_t), c->stream));
+            }
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (unsigned b = 0; b < WM_K0_SPEC_BINS; b++) {
+            if (sum) sum[b] = h_sum[0][b] + h_sum[1][b];
+            if (peak) peak[b] = std::max(h_peak[0][b], h_peak[1][b]);
+        }
+        if (blocks) *blocks = h_blocks[0] + h_blocks[1];
+        return (long)WM_K0_SPEC_BINS;
+    }
     /* on the context's own stream, which is idle behind a collect (a synchronous copy would bring the NULL stream's queue in: open_init) */
     if (sum) HIPCHK(c, hipMemcpyAsync(sum, d_sum, WM_K0_SPEC_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (peak) HIPCHK(c, hipMemcpyAsync(peak, d_peak, WM_K0_SPEC_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -484,12 +517,12 @@ long wmbus_read_spectrum(wmbus_ctx *c, unsigned stream, uint64_t *sum, uint32_t 
 
 long wmbus_read_input_afc(wmbus_ctx *c, unsigned stream, wmbus_afc *out)
 {
-    if (!c || stream >= c->NC || !out) return WMBUS_EINVAL;
+    if (!c || stream >= (c->afc.chan ? c->S : c->NC) || !out) return WMBUS_EINVAL;      /* with a lock per channel `stream` is the pipeline stream */
     if (!c->afc.on) return fail(c, WMBUS_EINVAL, "read_input_afc: the context was opened without cfg.input_afc");
     if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_input_afc: collect the push first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     K0AfcState st{};                                         /* half k0.cur: what the last push committed (before the first push: the initial state) */
-    HIPCHK(c, hipMemcpyAsync(&st, c->afc.d_state + (size_t)c->k0.cur * c->NC + stream, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&st, c->afc.d_state + (size_t)c->k0.cur * c->afc.n + stream, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *out = wmbus_afc{st.held_hz, st.locked, st.changes, st.ratio_q8};
     return 0;
@@ -581,6 +614,23 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         f.on = true; c->spec.on = true;                          /* the survey is AFC's measurement */
         k.shift = false;                                         /* the AFC form rotates, with a step of its own per capture and push */
     }
+    for (unsigned ch = 0; ch < WMBUS_MAX_CHANNELS; ch++) {       /* a lock per channel: any non-zero entry is the switch */
+        const unsigned range = cfg->input_channel_afc_hz[ch];
+        if (!range) continue;
+        if (ch >= cfg->input_channels)
+            return fail(c, WMBUS_EINVAL, "input_channel_afc_hz[%u] = %u without that channel (input_channels = %u)", ch, range, cfg->input_channels);
+        if (cfg->input_afc) return fail(c, WMBUS_EINVAL, "input_channel_afc_hz together with input_afc: the array is the switch of a channel list");
+        auto &f = c->afc;
+        f.fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+        const int64_t hz = cfg->input_channel_hz[ch], reach = (hz < 0 ? -hz : hz) + (int64_t)range;
+        if (f.fin < 800000u || 2 * reach > (int64_t)f.fin)
+            return fail(c, WMBUS_EINVAL, "input_channel_afc_hz: |input_channel_hz[%u]| + input_channel_afc_hz[%u] = %lld lies beyond half the input rate %u", ch, ch, (long long)reach, f.fin);
+        f.ch_range[ch] = range;
+        f.on = true; f.chan = true; c->spec.on = true;           /* the survey is AFC's measurement */
+    }
+    if (cfg->input_spectrum_age > 31u) return fail(c, WMBUS_EINVAL, "input_spectrum_age must be 0 (the survey never forgets) or 1 ... 31 (epochs of 2^A level blocks), got %u", cfg->input_spectrum_age);
+    if (cfg->input_spectrum_age && !c->spec.on) return fail(c, WMBUS_EINVAL, "input_spectrum_age = %u without a survey: set input_spectrum or input_afc", cfg->input_spectrum_age);
+    c->spec.age = cfg->input_spectrum_age;
     if (cfg->input_rate_hz && cfg->input_rate_hz != cfg->decimation * 800000u) {
         unsigned L = 0, M = 0, T = 0;
         k0_taps.resize((size_t)WM_K0_MAX_L * WM_K0_MAX_T);
@@ -748,14 +798,21 @@ static int open_allocate(wmbus_ctx *c)
         if (c->k0.agc) A(m.dalloc(&c->k0.d_agc_tab, (size_t)c->NC * c->k0.dc_stride));
     }
     if (c->k0.shift || c->k0.chan || c->spec.on) A(m.dalloc(&c->k0.d_shift_tab, (size_t)WM_K0_SHIFT_ENTRIES));      /* the survey's window and twiddles are this table's */
-    if (c->spec.on) {
+    if (c->spec.on && !c->spec.age) {
         A(m.dalloc(&c->spec.d_sum, (size_t)c->NC * WM_K0_SPEC_BINS));
         A(m.dalloc(&c->spec.d_peak, (size_t)c->NC * WM_K0_SPEC_BINS));
         A(m.dalloc(&c->spec.d_blocks, (size_t)c->NC));
     }
+    if (c->spec.age) {
+        c->spec.slot_stride = (uint64_t)c->NC * (WM_K0_SPEC_BINS + 1u + WM_K0_SPEC_BINS / 2u);
+        A(m.dalloc(&c->spec.d_slots, (size_t)2 * c->spec.slot_stride));
+        c->spec.d_sum = c->spec.d_slots; c->spec.d_blocks = c->spec.d_sum + (size_t)c->NC * WM_K0_SPEC_BINS;
+        c->spec.d_peak = (uint32_t *)(c->spec.d_blocks + c->NC);
+    }
     if (c->afc.on) {
-        A(m.dalloc(&c->afc.d_state, (size_t)2 * c->NC));
-        A(m.dalloc(&c->afc.d_push, (size_t)c->NC));
+        c->afc.n = c->afc.chan ? c->S : c->NC;
+        A(m.dalloc(&c->afc.d_state, (size_t)2 * c->afc.n));
+        A(m.dalloc(&c->afc.d_push, (size_t)c->afc.n));
     }
     A(m.dalloc(&c->d_dphi, (size_t)rows * c->Mcap));
     A(m.dalloc(&c->d_rssi, (size_t)rows * c->Mcap));
@@ -830,16 +887,18 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
     }
     if (c->k0.dc) A(hipMemsetAsync(c->k0.d_dc_state, 0, (size_t)2 * c->NC * sizeof(K0DcState), c->stream));      /* started = 0: A[0] = S[0] << R */
     std::vector<int16_t> shift_tab;
-    if (c->spec.on) {
+    if (c->spec.age) A(hipMemsetAsync(c->spec.d_slots, 0, (size_t)2 * c->spec.slot_stride * sizeof(uint64_t), c->stream));
+    else if (c->spec.on) {
         A(hipMemsetAsync(c->spec.d_sum, 0, (size_t)c->NC * WM_K0_SPEC_BINS * sizeof(uint64_t), c->stream));
         A(hipMemsetAsync(c->spec.d_peak, 0, (size_t)c->NC * WM_K0_SPEC_BINS * sizeof(uint32_t), c->stream));
         A(hipMemsetAsync(c->spec.d_blocks, 0, (size_t)c->NC * sizeof(uint64_t), c->stream));
     }
     std::vector<K0AfcState> afc_init;
     if (c->afc.on) {                                         /* unlocked, at the nominal, phase 0: both halves */
-        afc_init.assign((size_t)2 * c->NC, K0AfcState{c->afc.nominal, 0u, 0u, 0u, 0u, {0u, 0u, 0u}});
+        afc_init.assign((size_t)2 * c->afc.n, K0AfcState{c->afc.nominal, 0u, 0u, 0u, 0u, {0u, 0u, 0u}});
+        if (c->afc.chan) for (size_t v = 0; v < afc_init.size(); v++) afc_init[v].held_hz = c->cfg.input_channel_hz[v % c->CH];      /* every channel at its own nominal */
         A(hipMemcpyAsync(c->afc.d_state, afc_init.data(), afc_init.size() * sizeof(K0AfcState), hipMemcpyHostToDevice, c->stream));
-        A(hipMemsetAsync(c->afc.d_push, 0, (size_t)c->NC * sizeof(K0AfcPush), c->stream));
+        A(hipMemsetAsync(c->afc.d_push, 0, (size_t)c->afc.n * sizeof(K0AfcPush), c->stream));
     }
     if (c->k0.shift || c->k0.chan || c->spec.on) {           /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
@@ -1135,8 +1194,13 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
     }
     if (c->afc.on) {                                     /* the dc / agc tables are runtime branches of the AFC form: dc_stride is set above where either is on */
         ka->afc = c->afc.d_push;
-        c->afc.args = K0AfcArgs{c->spec.d_peak, c->spec.d_blocks, c->afc.d_state + (size_t)k.cur * c->NC, c->afc.d_state + (size_t)(k.cur ^ 1u) * c->NC,
-                                c->afc.d_push, c->afc.fin, c->afc.nominal, c->afc.range, n_in};
+        c->afc.args = K0AfcArgs{c->spec.d_peak, c->spec.d_blocks, c->afc.d_state + (size_t)k.cur * c->afc.n, c->afc.d_state + (size_t)(k.cur ^ 1u) * c->afc.n,
+                                c->afc.d_push, c->afc.fin, c->afc.nominal, c->afc.range, n_in, nullptr, nullptr, 0u, {}, {}};
+        if (c->afc.chan) {
+            c->afc.args.n_ch = c->CH;
+            for (uint32_t ch = 0; ch < c->CH; ch++) { c->afc.args.ch_nominal_hz[ch] = c->cfg.input_channel_hz[ch]; c->afc.args.ch_range_hz[ch] = c->afc.ch_range[ch]; }
+        }
+        if (c->spec.age) { c->afc.args.peak1 = c->spec.d_peak + 2u * c->spec.slot_stride; c->afc.args.blocks1 = c->spec.d_blocks + c->spec.slot_stride; }
     }
     k.last_out = 2ull * n_out * c->S;
     k.n_in += n_in; k.n_out = out_end; k.rem = (uint32_t)(total - whole); k.cur ^= 1u;
@@ -1152,8 +1216,11 @@ static size_t k0_plan(wmbus_ctx *c, size_t raw_bytes, K0Args *ka)
 #ifndef WM_K0_SPEC_RUN
 #define WM_K0_SPEC_RUN 16          /* build-time A/B (tools/build_variant.sh) */
 #endif
-static void spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, uint32_t n_blk)
+static int spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, uint32_t n_blk)
 {
+#define K0_SPEC_AGE(DC) {k0_spectrum<WM_K0_CU8, DC, true>, k0_spectrum<WM_K0_CS8, DC, true>, k0_spectrum<WM_K0_CS16, DC, true>, k0_spectrum<WM_K0_CF32, DC, true>}
+    void (*const aged[2][4])(K0SpecArgs) = {K0_SPEC_AGE(false), K0_SPEC_AGE(true)};       /* cfg.input_spectrum_age */
+#undef K0_SPEC_AGE
     void (*const kernel[2][4])(K0SpecArgs) = {{k0_spectrum<WM_K0_CU8, false>, k0_spectrum<WM_K0_CS8, false>, k0_spectrum<WM_K0_CS16, false>, k0_spectrum<WM_K0_CF32, false>},
                                               {k0_spectrum<WM_K0_CU8, true>, k0_spectrum<WM_K0_CS8, true>, k0_spectrum<WM_K0_CS16, true>, k0_spectrum<WM_K0_CF32, true>}};
     K0SpecArgs a{};
@@ -1162,9 +1229,19 @@ static void spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, u
     a.shift_tab = c->k0.d_shift_tab;
     a.sum = c->spec.d_sum; a.peak = c->spec.d_peak; a.blocks = c->spec.d_blocks;
     a.n_blk = n_blk; a.run = (uint64_t)n_blk * c->NC >= 16384u ? (uint32_t)WM_K0_SPEC_RUN : 4u;
-    if (!n_blk) return;
+    if (!n_blk) return WMBUS_OK;
+    if (c->spec.age) {
+        /* the one place where a push's level blocks enter the ageing survey, once per push: what the push clears and what it leaves out
+         * is k0_spec_age_plan's decision, and K moves on here and nowhere else */
+        const K0SpecAgePlan plan = k0_spec_age_plan(c->spec.K, n_blk, c->spec.age);
+        a.age = c->spec.age; a.k_first = c->spec.K; a.e_keep = plan.e_keep; a.slot_stride = c->spec.slot_stride;
+        c->spec.K += n_blk;
+        if (plan.clear == 3u) HIPCHK(c, hipMemsetAsync(c->spec.d_slots, 0, (size_t)2 * c->spec.slot_stride * sizeof(uint64_t), c->stream));
+        else if (plan.clear) HIPCHK(c, hipMemsetAsync(c->spec.d_slots + (plan.clear >> 1) * c->spec.slot_stride, 0, (size_t)c->spec.slot_stride * sizeof(uint64_t), c->stream));
+    }
     const uint32_t runs = (n_blk + a.run - 1u) / a.run;
-    hipLaunchKernelGGL(kernel[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+    hipLaunchKernelGGL((c->spec.age ? aged : kernel)[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+    return WMBUS_OK;
 }
 
 static int k0_launch(wmbus_ctx *c, const K0Args &ka)
@@ -1194,6 +1271,9 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
     /* cfg.input_afc: [WMBUS_FMT_*] -- the blocker and the AGC are runtime branches of these too */
     void (*const resample_afc[4])(K0Args) = {k0_resample_afc<WM_K0_CU8>, k0_resample_afc<WM_K0_CS8>, k0_resample_afc<WM_K0_CS16>, k0_resample_afc<WM_K0_CF32>};
     void (*const convert_afc[4])(K0Args) = {k0_convert_afc<WM_K0_CU8>, k0_convert_afc<WM_K0_CS8>, k0_convert_afc<WM_K0_CS16>, k0_convert_afc<WM_K0_CF32>};
+    /* cfg.input_channel_afc_hz: [WMBUS_FMT_*] -- the channels form with k0_afc_plan's {step, base} per pipeline stream */
+    void (*const resample_ch_afc[4])(K0Args) = {k0_resample_ch_afc<WM_K0_CU8>, k0_resample_ch_afc<WM_K0_CS8>, k0_resample_ch_afc<WM_K0_CS16>, k0_resample_ch_afc<WM_K0_CF32>};
+    void (*const convert_ch_afc[4])(K0Args) = {k0_convert_ch_afc<WM_K0_CU8>, k0_convert_ch_afc<WM_K0_CS8>, k0_convert_ch_afc<WM_K0_CS16>, k0_convert_ch_afc<WM_K0_CF32>};
     if (c->k0.dc) {                                      /* the level blocks' sums, then the recurrence over them: the table the K0 kernel subtracts */
         void (*const sums[4])(K0DcArgs) = {k0_dc_sums<WM_K0_CU8>, k0_dc_sums<WM_K0_CS8>, k0_dc_sums<WM_K0_CS16>, k0_dc_sums<WM_K0_CF32>};
         const K0DcArgs &da = c->k0.dca;
@@ -1201,16 +1281,17 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
         hipLaunchKernelGGL(k0_dc_plan, dim3(c->NC), dim3(128), 0, c->stream, da);
         c->k0.last_dc_blocks = da.n_blk;
     }
-    if (c->spec.on) spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2);      /* per capture, in front of the rotation, behind the blocker's table */
+    if (c->spec.on) { const int rc = spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2); if (rc) return rc; }      /* per capture, in front of the rotation, behind the blocker's table */
     /* cfg.input_afc: every capture's {step, base} for this push from its max-hold as it stands now, and the state commit, in ONE short launch */
-    if (c->afc.on) hipLaunchKernelGGL(k0_afc_plan, dim3(c->NC), dim3(WM_K0_AFC_THREADS), 0, c->stream, c->afc.args);
+    if (c->afc.on) hipLaunchKernelGGL(k0_afc_plan, dim3(c->NC, c->afc.chan ? c->CH : 1u), dim3(WM_K0_AFC_THREADS), 0, c->stream, c->afc.args);
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
         hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
         c->k0.last_dc_blocks = ga.n_blk;
     }
     const auto &stage = c->k0.agc ? (c->k0.resample ? resample_agc : convert_agc) : (c->k0.resample ? resample : convert);
-    void (*const kernel)(K0Args) = c->afc.on  ? (c->k0.resample ? resample_afc : convert_afc)[c->k0.fmt]
+    void (*const kernel)(K0Args) = c->afc.chan ? (c->k0.resample ? resample_ch_afc : convert_ch_afc)[c->k0.fmt]
+                                   : c->afc.on  ? (c->k0.resample ? resample_afc : convert_afc)[c->k0.fmt]
                                    : c->k0.chan ? (c->k0.resample ? resample_ch : convert_ch)[c->k0.fmt]
                                               : stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt];
     hipLaunchKernelGGL(kernel, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
@@ -1287,7 +1368,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
             /* the survey of a context on the plain cu8 path reads the device input window itself (a push of that path is whole 4096-byte
              * blocks and always has decimated samples: this branch is taken); the context stays on the plain path */
-            else if (c->spec.on) spec_launch(c, win + WM_HIST_BYTES, c->in_stride, (uint32_t)(nbytes / 2u) >> WM_K0_DC_LOG2);
+            else if (c->spec.on) { rc = spec_launch(c, win + WM_HIST_BYTES, c->in_stride, (uint32_t)(nbytes / 2u) >> WM_K0_DC_LOG2); if (rc) return rc; }
             /* The hand-over of the turn costs 0.15-0.2 ms (the next context's stream sits in an event wait on another
              * hardware queue; r03 trace: median 128 us between one K1 and the next, eight times per step = 5 % of it).
              * So the turn is handed over EARLY: a push's tiles leave in two launches, the event the next context waits for

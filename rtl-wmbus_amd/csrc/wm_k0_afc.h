@@ -5,10 +5,12 @@
  * survey (include/wmbus_hip.h, SPECTRUM: wmbus_spectrum_channels with its defaults, cap 8) on the capture's max-hold as it stands now,
  * this push's level blocks included, takes the first hit within the allowed range of the nominal, applies the hysteresis, and leaves the
  * stage kernel {step, base} of this push (K0Args.afc) and the next push the state.  The arithmetic is the definition (include/wmbus_hip.h,
- * AFC; tests/afc_ref.py restates it in Python integers); the host rule in wm_spectrum_channels.h is the oracle of the hit list.
+ * AFC; tests/afc_ref.py restates it in Python integers); the host rule in wm_spectrum_channels.h is the oracle of the hit list.  With
+ * cfg.input_spectrum_age the max-hold is the view's: the maximum of the survey's two slots, the block count their sum (SPECTRUM AGE).
  *
- * Shape: one block of 512 threads per capture, thread b <-> bin b.  It is latency on a context's launch chain, not throughput: one launch,
- * the state commit inside it.
+ * Shape: one block of 512 threads per capture (with cfg.input_channel_afc_hz: per capture and channel, the channel in blockIdx.y, each
+ * with its own nominal, range and state: the early exit at the first hit in range is the block's own), thread b <-> bin b.  It is
+ * latency on a context's launch chain, not throughput: one launch, the state commit inside it.
  *   Fp        rank counting: thread i counts the entries below its own (ties by index); rank 255 is the median the rule asks for
  *   windows   three inclusive prefix sums in LDS (Hillis-Steele, nine steps, ping-pong): peak, e = max(0, peak - Fp), e (b - 256); every
  *             window sum of the rule -- B[b], den, num -- is then two LDS reads, so the three re-centring trips cost thread 0 nothing
@@ -47,6 +49,14 @@ struct K0AfcArgs {
     int32_t nominal_hz;          /* cfg.input_shift_hz                                                         */
     uint32_t range_hz;           /* a hit counts within nominal +- range                                       */
     uint32_t n_in;               /* input samples of this push                                                 */
+    /* cfg.input_spectrum_age: the survey's second slot (both NULL without ageing; behind everything else: the arguments keep their places) */
+    const uint32_t *peak1;       /* [NC][512] the view's max-hold is max(peak, peak1)                          */
+    const uint64_t *blocks1;     /* [NC] its level blocks are blocks + blocks1                                 */
+    /* cfg.input_channel_afc_hz: a lock per channel.  n_ch = 0: none, the grid is (captures), the state of block x is [x].  n_ch = C: the
+     * grid is (captures, C), block (x, y) evaluates the rule on capture x's survey for channel y and owns state and push [x C + y] */
+    uint32_t n_ch;
+    int32_t ch_nominal_hz[WM_K0_MAX_CH];     /* cfg.input_channel_hz: take nominal_hz's place                  */
+    uint32_t ch_range_hz[WM_K0_MAX_CH];      /* take range_hz's place; 0: the channel is fixed -- no search, its state never changes but for the phase */
 };
 
 /* what a block needs of LDS */
@@ -116,8 +126,18 @@ __device__ __forceinline__ void k0_afc_plan_block(const K0AfcArgs &a, K0AfcLds &
 {
     constexpr uint32_t N = WM_K0_SPEC_BINS;
     const uint32_t t = threadIdx.x, cp = blockIdx.x;
+    const uint32_t v = a.n_ch ? cp * a.n_ch + blockIdx.y : cp;                       /* the state's and the push's index */
+    const int32_t nominal_hz = a.n_ch ? a.ch_nominal_hz[blockIdx.y] : a.nominal_hz;
+    const uint32_t range_hz = a.n_ch ? a.ch_range_hz[blockIdx.y] : a.range_hz;
+    const bool fixed = a.n_ch != 0u && range_hz == 0u;                               /* block-uniform */
     const uint32_t *peak = a.peak + (uint64_t)cp * N;
-    const uint32_t mine = peak[t];
+    uint32_t mine = peak[t];
+    uint64_t blocks = a.blocks[cp];
+    if (a.peak1) {                                               /* the ageing survey's view: the two slots together (SPECTRUM AGE) */
+        const uint32_t other = a.peak1[(uint64_t)cp * N + t];
+        mine = other > mine ? other : mine;
+        blocks += a.blocks1[cp];
+    }
     s.pk[t] = mine;
     if (t == 0u) { s.found = 0u; s.stop = 0u; }
     __syncthreads();
@@ -141,7 +161,7 @@ __device__ __forceinline__ void k0_afc_plan_block(const K0AfcArgs &a, K0AfcLds &
     const uint64_t w_raw = (uint64_t)WM_K0_AFC_WIDTH_HZ * N / a.in_hz;
     const uint32_t W = (uint32_t)(w_raw < 1u ? 1u : w_raw > 256u ? 256u : w_raw), nB = N - W + 1u;
     const uint64_t B = t < nB ? k0_afc_window(inP, t, W) : 0u;
-    bool alive = t < nB && a.blocks[cp] != 0u;                   /* no level block yet: the rule refuses, no hit */
+    bool alive = t < nB && blocks != 0u && !fixed;               /* no level block yet: the rule refuses, no hit; a fixed channel does not search */
     uint64_t first = 0u;                                         /* thread 0's */
     uint32_t hits = 0u;
     for (uint32_t trip = 0; trip < WM_K0_AFC_CAP; trip++) {
@@ -172,8 +192,8 @@ __device__ __forceinline__ void k0_afc_plan_block(const K0AfcArgs &a, K0AfcLds &
                 hits++;
                 if (den != 0u) {
                     const int32_t hz = k0_afc_offset(num, den, a.in_hz);
-                    const int64_t off = (int64_t)hz - (int64_t)a.nominal_hz;
-                    if ((off < 0 ? -off : off) <= (int64_t)a.range_hz) {
+                    const int64_t off = (int64_t)hz - (int64_t)nominal_hz;
+                    if ((off < 0 ? -off : off) <= (int64_t)range_hz) {
                         const uint64_t ratio = Bb * 256u / ((uint64_t)W * Fp);
                         s.cand_hz = hz; s.cand_ratio = ratio > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ratio; s.found = 1u;
                         stop = true;                             /* the first hit within range is the candidate */
@@ -188,7 +208,7 @@ __device__ __forceinline__ void k0_afc_plan_block(const K0AfcArgs &a, K0AfcLds &
         if ((t > best ? t - best : best - t) < W) alive = false;
     }
     if (t == 0u) {
-        K0AfcState st = a.st_in[cp];
+        K0AfcState st = a.st_in[v];
         if (s.found) {
             const int64_t move = (int64_t)s.cand_hz - (int64_t)st.held_hz;
             if (!st.locked || (move < 0 ? -move : move) > (int64_t)(a.in_hz / 256u)) {
@@ -196,9 +216,9 @@ __device__ __forceinline__ void k0_afc_plan_block(const K0AfcArgs &a, K0AfcLds &
             }
         }
         const uint32_t step = k0_afc_step(st.held_hz, a.in_hz);
-        a.push[cp] = K0AfcPush{step, st.base};
+        a.push[v] = K0AfcPush{step, st.base};
         st.base += step * a.n_in;
-        a.st_out[cp] = st;
+        a.st_out[v] = st;
     }
 }
 

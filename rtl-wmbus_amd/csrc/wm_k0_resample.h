@@ -76,6 +76,9 @@
  * k0_rotate, a push-local index in the place of the stream's, base in the place of 0.  k0_capture_of and k0_shifted are the two places
  * that know.  AF implies SH; like the channels form it takes the blocker and the AGC as runtime branches (one instantiation per format
  * and stage).  AF = false compiles to exactly the code there was: base is the constant 0 and m_first the stream's index.
+ * CH and AF together (cfg.input_channel_afc_hz: a lock per channel): the capture is v / n_ch as in the channels form, {step, base} are
+ * K0Args.afc[v] -- k0_afc_plan has run once per pipeline stream v, a fixed channel's entry is its own step and the phase that runs on --
+ * and K0Args.steps is not looked at.
  */
 #ifndef WM_K0_RESAMPLE_H
 #define WM_K0_RESAMPLE_H
@@ -134,7 +137,8 @@ struct K0Args {
     uint32_t n_ch;               /* channels per capture                                                      */
     uint32_t steps[WM_K0_MAX_CH];/* the phase step of each channel: takes step's place                        */
     /* AFC (the AF instantiations only); NULL: none */
-    const K0AfcPush *afc;        /* [S] this push's {step, base} of every capture (k0_afc_plan): take step's place; the sample index is push-local */
+    const K0AfcPush *afc;        /* [S] this push's {step, base} of every capture (k0_afc_plan): take step's place; the sample index is push-local.
+                                    With channels (CH && AF): of every pipeline stream v = capture * n_ch + channel */
 };
 
 /* the carried state of the DC blocker, per capture */
@@ -297,7 +301,7 @@ template <bool SH, bool CH, bool AF = false> __device__ __forceinline__ void k0_
 {
     cp = v; step = 0u; base = 0u; m_first = (uint32_t)a.in_first;     /* only the low 32 bits of the stream index reach the phase */
     if constexpr (SH) step = a.step;
-    if constexpr (CH) { cp = v / a.n_ch; step = a.steps[v - cp * a.n_ch]; }
+    if constexpr (CH) { cp = v / a.n_ch; if constexpr (!AF) step = a.steps[v - cp * a.n_ch]; }
     if constexpr (AF) { const K0AfcPush p = a.afc[v]; step = p.step; base = p.base; m_first = 0u; }
 }
 /* sample k of the four dwords a lane of k0_convert_block loaded, as the {I, Q} int16 pair of the unshifted rules */
@@ -372,7 +376,6 @@ __device__ __forceinline__ void k0_carry_rem(const K0Args &a, uint32_t s, uint8_
 template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false, bool AF = false> __device__ __forceinline__ void k0_resample_block_t(const K0Args &a, uint32_t *lds)
 {
     static_assert(SH || !(CH || AF), "the channels form and the AFC form always rotate");
-    static_assert(!(CH && AF), "AFC is per capture, not per channel");
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y;
     uint32_t cp, step, ph0, m_first;
     k0_capture_of<SH, CH, AF>(a, s, cp, step, ph0, m_first);
@@ -499,7 +502,6 @@ __device__ __forceinline__ void k0_resample_block(const K0Args &a, uint32_t *lds
 template <int FMT, bool SH = false, bool DC = false, bool AG = false, bool CH = false, bool AF = false> __device__ __forceinline__ void k0_convert_block(const K0Args &a, uint32_t *word)
 {
     static_assert(SH || !(CH || AF), "the channels form and the AFC form always rotate");
-    static_assert(!(CH && AF), "AFC is per capture, not per channel");
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS;       /* samples per lane and load */
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, s = blockIdx.y, gain = a.gain_q8 ? a.gain_q8 : 256u;
     uint32_t cp, step, ph0, m_first;                             /* s: pipeline stream (output, remainder); cp: its capture (raw, level tables) */
@@ -790,6 +792,17 @@ template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_a
 {
     __shared__ uint32_t word;
     k0_convert_block<FMT, true, false, false, false, true>(a, &word);
+}
+/* cfg.input_channel_afc_hz: the channels form with a {step, base} per pipeline stream and push from k0_afc_plan */
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample_ch_afc(K0Args a)
+{
+    extern __shared__ uint32_t k0_lds[];
+    k0_resample_block_t<FMT, true, false, false, true, true>(a, k0_lds);
+}
+template <int FMT> __global__ void __launch_bounds__(WM_K0_THREADS) k0_convert_ch_afc(K0Args a)
+{
+    __shared__ uint32_t word;
+    k0_convert_block<FMT, true, false, false, true, true>(a, &word);
 }
 __global__ void __launch_bounds__(WM_K0_THREADS) k0_resample(K0Args a)          /* cu8 */
 {

@@ -28,6 +28,13 @@
  * 0.78 against 0.61 ms per push of 64 x 2^22 samples); it is gone.
  * sum (uint64) and peak of the lane's 8 bins stay in registers over the run; at its end one 64-bit
  * atomic add and one 32-bit atomic max per bin (consecutive lanes, consecutive bins) and one add to the capture's block count.
+ *
+ * The survey that forgets (cfg.input_spectrum_age = A, include/wmbus_hip.h, SPECTRUM AGE; tests/afc_age_ref.py): level block K of the
+ * stream (64 bits, counted over all pushes) belongs to epoch K >> A and accumulates into slot (K >> A) & 1 of two sets of accumulators;
+ * the view is the two slots together, the last two epochs.  The HOST decides what a push clears and what it skips (k0_spec_age_plan
+ * below: the one owner of that decision, shared with the emulator harness of the tests); the AGE form of the kernel leaves out the level
+ * blocks of epochs below e_keep -- a prefix of the push, not transformed at all -- and flushes its registers whenever the epoch changes
+ * inside a wave's run, and at its end, with the same atomics.  AGE = false is the code above.
  */
 #ifndef WM_K0_SPECTRUM_H
 #define WM_K0_SPECTRUM_H
@@ -52,7 +59,25 @@ struct K0SpecArgs {
     uint32_t *peak;              /* [NC][512] max-hold                                                          */
     uint64_t *blocks;            /* [NC] += level blocks                                                        */
     uint32_t n_blk, run;         /* level blocks of this push per capture; consecutive level blocks per wave    */
+    /* the AGE form only (behind everything else: the plain form's arguments keep their places) */
+    uint32_t age;                /* A: 2^A level blocks per epoch                                               */
+    uint64_t k_first;            /* the stream's index of this push's first level block                        */
+    uint64_t e_keep;             /* level blocks of epochs below this one are left out                         */
+    uint64_t slot_stride;        /* slot 1 of sum / blocks lies this many uint64 behind slot 0, of peak twice as many uint32 */
 };
+
+/* What a push of n_blk > 0 level blocks, the first of them the stream's k_first, does to the two slots of an ageing survey.  The push
+ * ends in epoch e_now = (k_first + n_blk - 1) >> age; the level block in front of it lay in e_prev (none for k_first = 0, where every
+ * slot is still clear).  Every epoch in (e_prev, e_now] is newly entered: one of them -- its slot still holds epoch e_now - 2: clear it;
+ * two or more -- neither slot holds anything of e_now - 1 or e_now: clear both.  Level blocks of epochs below e_keep = e_now - 1 have
+ * no place in the view: the kernel leaves them out. */
+struct K0SpecAgePlan { uint64_t e_keep; uint32_t clear; };       /* clear: bit s set <-> slot s is zeroed in front of the kernel */
+__host__ __device__ __forceinline__ K0SpecAgePlan k0_spec_age_plan(uint64_t k_first, uint32_t n_blk, uint32_t age)
+{
+    const uint64_t e_now = (k_first + n_blk - 1u) >> age;
+    const uint64_t entered = k_first ? e_now - ((k_first - 1u) >> age) : 0u;
+    return K0SpecAgePlan{e_now ? e_now - 1u : 0u, entered == 0u ? 0u : entered == 1u ? 1u << (e_now & 1u) : 3u};
+}
 
 __device__ __forceinline__ void k0_add64(uint64_t *p, uint64_t v)
 {
@@ -105,16 +130,40 @@ template <bool FIRST> __device__ __forceinline__ void k0_spec_pass(int32_t (&zr)
     }
 }
 
+/* A wave's registers into the accumulators of capture s, slot `slot` (0 without ageing): one 64-bit atomic add and one atomic max per bin
+ * that has something, and the count of the n level blocks they hold. */
+__device__ __forceinline__ void k0_spec_flush(const K0SpecArgs &a, uint32_t s, uint32_t lane, uint64_t slot, const uint64_t (&acc)[8], const uint32_t (&top)[8],
+                                              uint32_t n)
+{
+    uint64_t *sum = a.sum + slot * a.slot_stride + (uint64_t)s * WM_K0_SPEC_BINS;
+    uint32_t *peak = a.peak + 2u * slot * a.slot_stride + (uint64_t)s * WM_K0_SPEC_BINS;
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; q++) {                          /* the lane holds j = 64 q + lane: bin (j + 256) mod 512 */
+        const uint32_t b = 64u * (q ^ 4u) + lane;
+        if (acc[q]) k0_add64(sum + b, acc[q]);
+        if (top[q]) k0_max32(peak + b, top[q]);
+    }
+    if (lane == 0u) k0_add64(a.blocks + slot * a.slot_stride + s, (uint64_t)n);
+}
+
 /* One block of WM_K0_SPEC_WAVES waves: blockIdx.x = four runs, blockIdx.y = capture.  lds: WM_K0_SPEC_WAVES x 2 x WM_K0_SPEC_PLANE dwords.
  * Lanes of a wave leave together or not at all. */
-template <int FMT, bool DC> __device__ __forceinline__ void k0_spectrum_block(const K0SpecArgs &a, int32_t *lds)
+template <int FMT, bool DC, bool AGE = false> __device__ __forceinline__ void k0_spectrum_block(const K0SpecArgs &a, int32_t *lds)
 {
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS, LOADS = (BPS << WM_K0_DC_LOG2) / (64u * 16u);
     static_assert(SPL * LOADS == 8u, "a lane loads 8 of a level block's 512 samples");
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, s = blockIdx.y;
-    const uint32_t first = (blockIdx.x * (blockDim.x >> 6) + wave) * a.run;
+    uint32_t first = (blockIdx.x * (blockDim.x >> 6) + wave) * a.run;
     if (first >= a.n_blk) return;
     const uint32_t last = a.n_blk - first < a.run ? a.n_blk : first + a.run;
+    if constexpr (AGE) {                                         /* the level blocks of epochs below e_keep are a prefix of the push */
+        const uint64_t k_keep = a.e_keep << a.age;
+        if (k_keep > a.k_first) {
+            const uint64_t skip = k_keep - a.k_first;
+            if (skip >= last) return;                            /* the same in every lane of the wave */
+            first = skip > first ? (uint32_t)skip : first;
+        }
+    }
     int32_t *re = lds + wave * 2u * WM_K0_SPEC_PLANE, *im = re + WM_K0_SPEC_PLANE;
     const uint32_t *tab = a.shift_tab;
 
@@ -148,8 +197,18 @@ template <int FMT, bool DC> __device__ __forceinline__ void k0_spectrum_block(co
     uint32_t top[8];
 #pragma unroll
     for (uint32_t q = 0; q < 8u; q++) { acc[q] = 0u; top[q] = 0u; }
+    uint32_t since = first;                                      /* AGE: the first level block the registers hold */
 
     for (uint32_t blk = first; blk < last; blk++) {
+        if constexpr (AGE) {                                     /* an epoch edge inside the run: what the registers hold goes to its slot */
+            const uint64_t e = (a.k_first + blk) >> a.age;
+            if (blk != since && e != (a.k_first + since) >> a.age) {
+                k0_spec_flush(a, s, lane, ((a.k_first + since) >> a.age) & 1u, acc, top, blk - since);
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) { acc[q] = 0u; top[q] = 0u; }
+                since = blk;
+            }
+        }
         const uint8_t *p = a.raw + (uint64_t)s * a.raw_stride + ((uint64_t)blk << WM_K0_DC_LOG2) * BPS;
         K0U4 w[LOADS];
 #pragma unroll
@@ -194,22 +253,15 @@ template <int FMT, bool DC> __device__ __forceinline__ void k0_spectrum_block(co
             top[q] = (uint32_t)pw > top[q] ? (uint32_t)pw : top[q];
         }
     }
-    uint64_t *sum = a.sum + (uint64_t)s * WM_K0_SPEC_BINS;
-    uint32_t *peak = a.peak + (uint64_t)s * WM_K0_SPEC_BINS;
-#pragma unroll
-    for (uint32_t q = 0; q < 8u; q++) {                          /* the lane holds j = 64 q + lane: bin (j + 256) mod 512 */
-        const uint32_t b = 64u * (q ^ 4u) + lane;
-        if (acc[q]) k0_add64(sum + b, acc[q]);
-        if (top[q]) k0_max32(peak + b, top[q]);
-    }
-    if (lane == 0u) k0_add64(a.blocks + s, (uint64_t)(last - first));
+    if constexpr (AGE) k0_spec_flush(a, s, lane, ((a.k_first + since) >> a.age) & 1u, acc, top, last - since);
+    else k0_spec_flush(a, s, lane, 0u, acc, top, last - first);
 }
 
 #if defined(__HIPCC__)
-template <int FMT, bool DC> __global__ void __launch_bounds__(64 * WM_K0_SPEC_WAVES) k0_spectrum(K0SpecArgs a)
+template <int FMT, bool DC, bool AGE = false> __global__ void __launch_bounds__(64 * WM_K0_SPEC_WAVES) k0_spectrum(K0SpecArgs a)
 {
     __shared__ int32_t k0_spec_lds[WM_K0_SPEC_WAVES * 2u * WM_K0_SPEC_PLANE];
-    k0_spectrum_block<FMT, DC>(a, k0_spec_lds);
+    k0_spectrum_block<FMT, DC, AGE>(a, k0_spec_lds);
 }
 #endif
 

@@ -11,7 +11,8 @@
  * than this for their push to fill; wm_reader.c), -G HIP device(s), -P polyphase pre-filter, -A 1|2 fast arctangents,
  * -I sample format of the input and -g input gain in dB or auto (converted on the GPU), -C I/Q DC blocker of the input, -w channel survey of the
  * input (a max-hold spectrum taken on the GPU: where the transmitters are, printed to stderr as a ready-made -O), -O auto[:Hz] that offset
- * found and applied on the GPU within the same run, per capture, -l frequency offset and
+ * found and applied on the GPU within the same run, per capture (auto:Hz entries inside an -O list: per channel), -E seconds a survey
+ * that forgets, so that the lock follows the last seconds of a live stream, -l frequency offset and
  * deviation of every telegram appended to its line, -U / -W de-duplication, -T host:port (cu8 over TCP; the role of the reference's unused net_support.h:15-44 /
  * rtl_wmbus.c:1281), -S statistics, and
  *   rtl_wmbus_hip [switches] a.cu8 b.cu8 ...      batch mode: one capture per file, lines prefixed "a.cu8: ".
@@ -65,11 +66,15 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t   a list (-O 325k,-325k; up to %d entries) decodes that many channels of one wideband capture at once and appends ;<channel Hz> to every line\n", WMBUS_MAX_CHANNELS);
     fprintf(stdout, "\t   -O auto finds the offset on the GPU, per capture, from the capture's own spectrum, within +-64 kHz of the centre (a +-50 ppm dongle), and applies it from the push\n");
     fprintf(stdout, "\t   that reveals it; -O auto:250k searches around 250 kHz instead.  With -v every change of the lock goes to stderr (afc: <Hz> Hz x<strength> over the floor;\n");
-    fprintf(stdout, "\t   batch mode: per file, at the end).  Not with a list.  The result depends on how the input is cut into pushes (-B)\n");
+    fprintf(stdout, "\t   batch mode: per file, at the end).  The result depends on how the input is cut into pushes (-B)\n");
+    fprintf(stdout, "\t   in a list an entry spelled auto:Hz follows its transmitter within +-64 kHz of Hz, each channel with a lock of its own (-O auto:325k,auto:-325k; -O auto:325k,-325k\n");
+    fprintf(stdout, "\t   keeps the second fixed); -v prints afc[<channel Hz>]: <Hz> Hz x<strength> over the floor.  A bare auto inside a list is not taken\n");
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
     fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
+    fprintf(stdout, "\t-E seconds the survey of -w and -O auto forgets: it holds the last seconds ... 2 x seconds of the input (epochs of 2^A x 512 samples, the smallest A that\n");
+    fprintf(stdout, "\t   lasts that long), so that on a live stream -O auto follows a receiver that drifts and lets go of a transmitter that has gone silent; default: it never forgets\n");
     fprintf(stdout, "\t-B bytes per GPU push (multiple of 4096; default 1048576 for a live stream; per file in batch mode 2097152, 1048576 from 384 files per GPU on)\n");
     fprintf(stdout, "\t-L ms a live stream's bytes wait at most this long for their push to fill (default 50; 0: only full pushes)\n");
     fprintf(stdout, "\t-S batch mode: print samples, seconds and Msamples/s to stderr\n");
@@ -287,7 +292,8 @@ static void print_spectrum(wmbus_ctx *ctx, unsigned stream, const wmbus_cfg *cfg
     fputc('\n', stderr);
 }
 
-static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen);
+static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen, const int *chan_hz);
+static int any_channel_afc(const wmbus_cfg *cfg);
 
 static int run_batch(struct batch_job *j)
 {
@@ -335,7 +341,17 @@ static int run_batch(struct batch_job *j)
             unsigned first = 0, n = 0;
             wmbus_ctx *ctx = wmbus_batch_context(b, i, &first, &n);
             pthread_mutex_lock(&out_lock);
-            for (unsigned s = 0; ctx && s < n; s++) print_afc(ctx, s, j->names[first + s], NULL);
+            for (unsigned s = 0; ctx && s < n; s++) print_afc(ctx, s, j->names[first + s], NULL, NULL);
+            pthread_mutex_unlock(&out_lock);
+        }
+    if (any_channel_afc(&j->cfg) && j->cfg.show_algorithm)   /* a list with auto: entries and -v: every file's final lock per following channel */
+        for (unsigned i = 0; i < wmbus_batch_contexts(b); i++) {
+            unsigned first = 0, n = 0;
+            wmbus_ctx *ctx = wmbus_batch_context(b, i, &first, &n);
+            pthread_mutex_lock(&out_lock);
+            for (unsigned s = 0; ctx && s < n; s++)
+                for (unsigned ch = 0; ch < j->cfg.input_channels; ch++)
+                    if (j->cfg.input_channel_afc_hz[ch]) print_afc(ctx, s * j->cfg.input_channels + ch, j->names[first + s], NULL, &j->cfg.input_channel_hz[ch]);
             pthread_mutex_unlock(&out_lock);
         }
     rc = j->lev_missing ? EXIT_FAILURE : EXIT_SUCCESS;
@@ -480,10 +496,18 @@ static int parse_devices(const char *arg, int *devs, int cap)
 }
 
 /* ---- live stream (stdin / TCP): wm_reader.c stages the bytes, this is where a push leaves -------- */
-struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; unsigned afc_changes; };
+struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; unsigned afc_changes; unsigned afc_ch_changes[WMBUS_MAX_CHANNELS]; };
 
-/* -O auto with -v: the lock of one capture to stderr where it has changed since `*seen` changes (NULL: print it if there is one) */
-static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen)
+/* a list with auto: entries (cfg.input_channel_afc_hz): is any channel following its transmitter? */
+static int any_channel_afc(const wmbus_cfg *cfg)
+{
+    for (unsigned ch = 0; ch < cfg->input_channels && ch < WMBUS_MAX_CHANNELS; ch++) if (cfg->input_channel_afc_hz[ch]) return 1;
+    return 0;
+}
+
+/* -O auto with -v: the lock of one capture to stderr where it has changed since `*seen` changes (NULL: print it if there is one).
+ * chan_hz: NULL, or the channel of a list whose lock `stream` (capture x channels + channel) is: the line says afc[<channel Hz>]: */
+static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigned *seen, const int *chan_hz)
 {
     wmbus_afc a;
     const char *sep = name ? ": " : "";
@@ -491,7 +515,8 @@ static void print_afc(wmbus_ctx *ctx, unsigned stream, const char *name, unsigne
     if (wmbus_read_input_afc(ctx, stream, &a) < 0) { fprintf(stderr, "rtl_wmbus_hip: %s%s%s\n", name, sep, wmbus_last_error(ctx)); return; }
     if (seen ? a.changes == *seen : !a.locked) return;
     if (seen) *seen = a.changes;
-    fprintf(stderr, "%s%safc: %d Hz x%.1f over the floor\n", name, sep, (int)a.shift_hz, (double)a.ratio_q8 / 256.0);
+    if (chan_hz) fprintf(stderr, "%s%safc[%d]: %d Hz x%.1f over the floor\n", name, sep, *chan_hz, (int)a.shift_hz, (double)a.ratio_q8 / 256.0);
+    else fprintf(stderr, "%s%safc: %d Hz x%.1f over the floor\n", name, sep, (int)a.shift_hz, (double)a.ratio_q8 / 256.0);
 }
 
 static int live_push(void *user, const unsigned char *buf, size_t n)
@@ -503,7 +528,10 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     if (rc) { fprintf(stderr, "rtl_wmbus_hip: %s\n", wmbus_last_error(lv->ctx)); return rc; }
     wmbus_timing t;
     if (!wmbus_get_timing(lv->ctx, &t)) report_warnings(t.warnings, &lv->told);
-    if (lv->cfg->input_afc && lv->cfg->show_algorithm) print_afc(lv->ctx, 0, NULL, &lv->afc_changes);
+    if (lv->cfg->input_afc && lv->cfg->show_algorithm) print_afc(lv->ctx, 0, NULL, &lv->afc_changes, NULL);
+    if (lv->cfg->show_algorithm)                             /* a list with auto: entries: every following channel's lock */
+        for (unsigned ch = 0; ch < lv->cfg->input_channels; ch++)
+            if (lv->cfg->input_channel_afc_hz[ch]) print_afc(lv->ctx, ch, NULL, &lv->afc_ch_changes[ch], &lv->cfg->input_channel_hz[ch]);
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
     if (len && (lv->levels || lv->cfg->input_channels > 1u)) {
@@ -528,9 +556,10 @@ int main(int argc, char **argv)
     wmbus_default_cfg(&cfg);
     cfg.max_push_bytes = 0;                                  /* 0: the mode's default, see below */
     int check_flow = 0, opt, map_only = 0, devs[64], n_devs = 0, stats = 0, gain_given = 0;
+    double age_seconds = 0.0;                                /* -E */
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lw")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -563,6 +592,12 @@ int main(int argc, char **argv)
         case 'S': stats = 1; break;
         case 'l': cfg.line_levels = 1; break;
         case 'w': cfg.input_spectrum = 1; break;
+        case 'E': {
+            char *end;
+            age_seconds = strtod(optarg, &end);
+            if (end == optarg || *end || !(age_seconds > 0.0) || age_seconds > 1e9) { print_usage(argv[0]); return EXIT_FAILURE; }
+            break;
+        }
         case 'F': cfg.tolerance_mode = 1; break;
         case 'R':
             cfg.input_rate_hz = parse_rate(optarg);
@@ -577,7 +612,8 @@ int main(int argc, char **argv)
         case 'O': {                                          /* one offset, or a comma-separated list of channels, each spelled alike */
             char item[64];
             unsigned n = 0;
-            if (!strncmp(optarg, "auto", 4)) {               /* auto | auto:HZ -- AFC around the nominal; anything else behind it (a list) is a bad option */
+            memset(cfg.input_channel_afc_hz, 0, sizeof cfg.input_channel_afc_hz);
+            if (!strncmp(optarg, "auto", 4) && !strchr(optarg, ',')) {       /* auto | auto:HZ -- AFC around the nominal, per capture */
                 int ok = 1;
                 const int nominal = optarg[4] == ':' ? parse_shift(optarg + 5, &ok) : 0;
                 if (!ok || (optarg[4] && optarg[4] != ':')) { print_usage(argv[0]); return EXIT_FAILURE; }
@@ -591,7 +627,12 @@ int main(int argc, char **argv)
                 int ok = 0;
                 if (len == 0 || len >= sizeof item || n == WMBUS_MAX_CHANNELS) { print_usage(argv[0]); return EXIT_FAILURE; }
                 memcpy(item, p, len); item[len] = 0;
-                cfg.input_channel_hz[n++] = parse_shift(item, &ok);
+                /* an entry of a list: HZ (fixed) or auto:HZ (that channel follows its transmitter within the default range); a bare auto
+                 * inside a list, auto: and auto:x are bad options */
+                const int follows = !strncmp(item, "auto", 4);
+                if (follows && item[4] != ':') { print_usage(argv[0]); return EXIT_FAILURE; }
+                cfg.input_channel_afc_hz[n] = follows ? 64000u : 0u;
+                cfg.input_channel_hz[n++] = parse_shift(follows ? item + 5 : item, &ok);
                 if (!ok) { print_usage(argv[0]); return EXIT_FAILURE; }
                 if (!comma) break;
                 p = comma + 1;
@@ -599,7 +640,7 @@ int main(int argc, char **argv)
             /* one entry is the shift it always was; more are the channels of a wideband capture */
             cfg.input_shift_hz = n == 1u ? cfg.input_channel_hz[0] : 0;
             cfg.input_channels = n == 1u ? 0u : n;
-            if (n == 1u) cfg.input_channel_hz[0] = 0;
+            if (n == 1u) { cfg.input_channel_hz[0] = 0; cfg.input_channel_afc_hz[0] = 0; }
             break;
         }
         case 'C': {
@@ -619,6 +660,13 @@ int main(int argc, char **argv)
         }
     }
     if (cfg.input_agc && gain_given) { print_usage(argv[0]); return EXIT_FAILURE; }      /* -g auto takes the place of a gain in dB */
+    if (age_seconds > 0.0) {                                 /* -E: the smallest A whose epoch of 2^A x 512 input samples lasts that long */
+        if (!cfg.input_spectrum && !cfg.input_afc && !any_channel_afc(&cfg)) { print_usage(argv[0]); return EXIT_FAILURE; }      /* nothing would be surveyed */
+        const double want = age_seconds * (double)(cfg.input_rate_hz ? cfg.input_rate_hz : (cfg.decimation ? cfg.decimation : 1u) * 800000u);
+        unsigned a = 1u;
+        while (a < 31u && (double)(1ull << a) * 512.0 < want) a++;
+        cfg.input_spectrum_age = a;
+    }
     if (getenv("WMBUS_FIXED_TS")) cfg.fixed_timestamp = 1;
     /* -d is taken unchecked like the reference takes it (rtl_wmbus.c:950).  There `-d 0` keeps every sample, exactly like
      * `-d 1` (the counter test at :1350-1352 is `++index < rate`), so that is what it means here; with -s it indexes a
@@ -668,7 +716,7 @@ int main(int argc, char **argv)
     int fd = 0;
     if (tcp && (fd = open_tcp(tcp)) < 0) return EXIT_FAILURE;
 
-    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg, 0};
+    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg, 0, {0}};
     int rc = wmbus_open(&cfg, &lv.ctx);
     if (rc) {
         fprintf(stderr, "rtl_wmbus_hip: cannot open GPU back end: %s\n", lv.ctx ? wmbus_last_error(lv.ctx) : "out of memory");

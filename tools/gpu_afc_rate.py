@@ -11,7 +11,15 @@ capture, --streams 1 --log2-samples 19 --steps 20.
 
 Prints one JSON line per repetition -- the wall clock per push (process + collect), the median wmbus_timing.demod_ms of its pushes (every
 K0 kernel lies inside it) and gpu_total_ms -- and one summary line per leg and one for the difference.  The fixed leg's shift is the lock
-the AFC leg reports for capture 0 after its warm-up (1 Hz if that is 0: the rotating kernel, not the plain one).  Kernel times proper:
+the AFC leg reports for capture 0 after its warm-up (1 Hz if that is 0: the rotating kernel, not the plain one).
+
+Three more legs at the same shape, in the same interleaved order, each held against its counterpart of the same visit:
+    afc_aged     AFC on a survey that forgets (cfg.input_spectrum_age = `--age`, default 16) against `afc`: the same transform, one more
+                 flush per epoch edge inside a wave's run, a fill per newly entered epoch, and a plan kernel that reads two slots
+    ch2_fixed    a list of two fixed channels (cfg.input_channel_hz = [lock, lock + 100000]) with the survey on
+    ch2_afc      the same list with a lock per channel (cfg.input_channel_afc_hz = [64000, 64000]) against `ch2_fixed`: the plan kernel on
+                 a grid of (captures, 2), the stage kernel's step from its table
+--legs picks a subset (fixed and afc are always there).  Kernel times proper:
     rocprofv3 --kernel-trace --stats -d DIR -o afc --output-format csv -- python tools/gpu_afc_rate.py --reps 1 --steps 3
 and read the k0_afc_plan row."""
 import argparse
@@ -33,6 +41,8 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--streams", type=int, default=64)
 ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic captures (the others repeat them)")
 ap.add_argument("--log2-samples", type=int, default=22)
+ap.add_argument("--age", type=int, default=16, help="cfg.input_spectrum_age of the afc_aged leg")
+ap.add_argument("--legs", default="afc_aged,ch2_fixed,ch2_afc", help="the legs beside fixed and afc, comma separated (empty: none)")
 a = ap.parse_args()
 if wm.device_count() < 1:
     sys.exit("gpu_afc_rate.py: no HIP device")
@@ -54,6 +64,14 @@ def opened(**kw):
 legs = {"afc": opened(input_afc=1)}
 lock = legs["afc"].read_input_afc(0)
 legs = {"fixed": opened(input_spectrum=1, input_shift_hz=lock["shift_hz"] or 1), "afc": legs["afc"]}
+more = [x for x in a.legs.split(",") if x]
+pair = [lock["shift_hz"] or 1, (lock["shift_hz"] or 1) + 100000]
+if "afc_aged" in more:
+    legs["afc_aged"] = opened(input_afc=1, input_spectrum_age=a.age)
+if "ch2_fixed" in more:
+    legs["ch2_fixed"] = opened(input_spectrum=1, input_channel_hz=pair)
+if "ch2_afc" in more:
+    legs["ch2_afc"] = opened(input_channel_hz=pair, input_channel_afc_hz=[64000, 64000])
 
 push_ms, demods = {k: [] for k in legs}, {k: [] for k in legs}
 for r in range(a.reps):
@@ -75,5 +93,11 @@ for name in legs:
 print(json.dumps(dict(summary="afc - fixed", push_ms=round(statistics.median(push_ms["afc"]) - statistics.median(push_ms["fixed"]), 4),
                       demod_ms=round(statistics.median(demods["afc"]) - statistics.median(demods["fixed"]), 4), lock=lock,
                       lock_at_the_end=legs["afc"].read_input_afc(0))), flush=True)
+for name, against in (("afc_aged", "afc"), ("ch2_afc", "ch2_fixed")):
+    if name in legs and against in legs:
+        print(json.dumps(dict(summary=f"{name} - {against}", push_ms=round(statistics.median(push_ms[name]) - statistics.median(push_ms[against]), 4),
+                              demod_ms=round(statistics.median(demods[name]) - statistics.median(demods[against]), 4),
+                              ratio=round(statistics.median(push_ms[name]) / statistics.median(push_ms[against]), 4),
+                              lock_at_the_end=legs[name].read_input_afc(0))), flush=True)
 for rx in legs.values():
     rx.close()
