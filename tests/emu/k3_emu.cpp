@@ -39,7 +39,7 @@ void wm_emu_k3_set_spill(uint32_t *arena, uint32_t arena_words, uint32_t *chain,
     emu_spill.arena = arena; emu_spill.arena_words = arena_words; emu_spill.chain = chain; emu_spill.nchain = nchain; emu_spill.used = used;
 }
 
-/* geo: M, Mcap, flags, m0, seg_len[2], nseg[2], cap[2] (S = 1).  Returns the number of bursts, or -1 on overflow. */
+/* geo: M, Mcap, flags, m0, seg_len[2], nseg[2], cap[2].  Returns the number of bursts, or -1 on overflow. */
 /* optional: where the bursts decoded by the kernel go (WmPkt array, byte arena); unset = every burst as chips */
 static WmPkt *emu_pkts = nullptr; static uint32_t emu_pkts_cap = 0, *emu_n_pkts = nullptr; static uint8_t *emu_bytes = nullptr; static uint32_t emu_bytes_cap = 0;
 void wm_emu_k3_set_decode(void *pkts, uint32_t pkts_cap, uint32_t *n_pkts, uint8_t *bytes, uint32_t bytes_cap)
@@ -55,12 +55,12 @@ static uint32_t *emu_span_flags = nullptr; static uint32_t emu_span_tiles = 0, e
 void wm_emu_k3_set_spans(uint32_t *flags, uint32_t ntiles) { emu_span_flags = flags; emu_span_tiles = ntiles; }
 unsigned wm_emu_k3_spans_listed(void) { return emu_span_listed; }
 
-long wm_emu_k3(const uint64_t *geo, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0, const uint32_t *counts1,
+static long emu_k3(uint32_t S, uint32_t *err_out, const uint64_t *geo, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0, const uint32_t *counts1,
                const uint32_t *seen0, const uint32_t *seen1, const uint8_t *rssi, const uint32_t *pending, void *hdr_out, uint32_t hdr_cap,
                uint32_t *words_out, uint32_t words_cap, uint32_t *n_words_out, uint32_t max_blocks)
 {
     WmPush g{};
-    g.S = 1; g.d = 2; g.M = (uint32_t)geo[0]; g.Mcap = (uint32_t)geo[1]; g.flags = (uint32_t)geo[2]; g.m0 = geo[3];
+    g.S = S; g.d = 2; g.M = (uint32_t)geo[0]; g.Mcap = (uint32_t)geo[1]; g.flags = (uint32_t)geo[2]; g.m0 = geo[3];
     for (int a = 0; a < 2; a++) {
         g.seg_len[a] = (uint32_t)geo[4 + a]; g.nseg[a] = (uint32_t)geo[6 + a]; g.nseg_cap[a] = g.nseg[a]; g.cap[a] = (uint32_t)geo[8 + a];
     }
@@ -89,26 +89,28 @@ long wm_emu_k3(const uint64_t *geo, const uint32_t *chips0, const uint32_t *chip
     std::vector<uint8_t> masked;
     if (emu_span_flags) {
         const uint32_t T = WM_K1_TILE2, nt = emu_span_tiles;
-        std::vector<uint32_t> list(nt);
+        std::vector<uint32_t> list((size_t)nt * g.S);
         uint32_t n_list = 0;
         static std::vector<WmItemRec> plans;                 /* k3_spans leaves its findings for k3_bursts, as in the product */
         plans.assign((size_t)4 * g.S + hdr_cap, WmItemRec{0xDEADu, 0xDEADu, 0xDEADu, WmPlan{}});
         k3.plans = plans.data();
-        std::fill(emu_span_flags, emu_span_flags + nt, 0u);
+        std::fill(emu_span_flags, emu_span_flags + (size_t)nt * g.S, 0u);
         for (uint32_t b = 0; b < gridDim.x; b++) {
             blockIdx = {b, 0, 0};
             block_emu::run_block(256, [&] { k3_spans(k3, T, nt, emu_span_flags, list.data(), &n_list); });
         }
         emu_span_listed = n_list;
-        for (uint32_t i = 0; i < n_list; i++) if (list[i] >= nt || !emu_span_flags[list[i]]) return -2;       /* listed = flagged, once each */
+        /* listed = flagged, once each: flags [ntiles][S], list entries capture * ntiles + tile (k3_mark) */
+        for (uint32_t i = 0; i < n_list; i++) if (list[i] >= nt * g.S || !emu_span_flags[(size_t)(list[i] % nt) * g.S + list[i] / nt]) return -2;
         uint32_t flagged = 0;
-        for (uint32_t tl = 0; tl < nt; tl++) flagged += emu_span_flags[tl] != 0;
+        for (size_t i = 0; i < (size_t)nt * g.S; i++) flagged += emu_span_flags[i] != 0;
         if (flagged != n_list) return -3;
-        masked.assign(rssi, rssi + 2 * (size_t)g.Mcap);
+        masked.assign(rssi, rssi + 2 * (size_t)g.S * g.Mcap);
         for (uint32_t ch = 0; ch < 2; ch++)
-            for (uint32_t tl = 0; tl < nt; tl++)
-                if (!((emu_span_flags[tl] >> ch) & 1u))
-                    for (uint32_t m = tl * T; m < std::min((tl + 1) * T, g.Mcap); m++) masked[(size_t)ch * g.Mcap + m] = 0;
+            for (uint32_t s = 0; s < g.S; s++)
+                for (uint32_t tl = 0; tl < nt; tl++)
+                    if (!((emu_span_flags[(size_t)tl * g.S + s] >> ch) & 1u))
+                        for (uint32_t m = tl * T; m < std::min((tl + 1) * T, g.Mcap); m++) masked[((size_t)ch * g.S + s) * g.Mcap + m] = 0;
         k3.rssi = masked.data();
     }
     for (uint32_t b = 0; b < gridDim.x; b++) {
@@ -116,7 +118,25 @@ long wm_emu_k3(const uint64_t *geo, const uint32_t *chips0, const uint32_t *chip
         block_emu::run_block(256, [&] { k3_bursts(k3, n_items); });
     }
     if (n_words_out) *n_words_out = n_words;
+    if (err_out) { *err_out = err; return (long)std::min(n_hdr, hdr_cap); }
     return err ? -1 : (long)n_hdr;
+}
+
+long wm_emu_k3(const uint64_t *geo, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0, const uint32_t *counts1,
+               const uint32_t *seen0, const uint32_t *seen1, const uint8_t *rssi, const uint32_t *pending, void *hdr_out, uint32_t hdr_cap,
+               uint32_t *words_out, uint32_t words_cap, uint32_t *n_words_out, uint32_t max_blocks)
+{
+    return emu_k3(1u, nullptr, geo, chips0, chips1, counts0, counts1, seen0, seen1, rssi, pending, hdr_out, hdr_cap, words_out, words_cap, n_words_out, max_blocks);
+}
+
+/* The same for S captures in lock step: chips [2][S][nseg][cap], counts / seen [2][S][nseg], rssi [2][S][Mcap], pending [2][2][S],
+ * span flags [ntiles][S].  The kernels' error word goes to *err_out instead of turning the result into -1 (the arenas may be made too
+ * small on purpose: what is written then is the test's subject); returns the number of burst headers written. */
+long wm_emu_k3_captures(uint32_t S, uint32_t *err_out, const uint64_t *geo, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0,
+                        const uint32_t *counts1, const uint32_t *seen0, const uint32_t *seen1, const uint8_t *rssi, const uint32_t *pending,
+                        void *hdr_out, uint32_t hdr_cap, uint32_t *words_out, uint32_t words_cap, uint32_t *n_words_out, uint32_t max_blocks)
+{
+    return emu_k3(S, err_out, geo, chips0, chips1, counts0, counts1, seen0, seen1, rssi, pending, hdr_out, hdr_cap, words_out, words_cap, n_words_out, max_blocks);
 }
 
 }

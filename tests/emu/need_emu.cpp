@@ -54,4 +54,21 @@ unsigned wm_emu_decoder_consumes(int mode, const uint8_t *chips, unsigned n)
     return n + 1;
 }
 
+/* The host decoder from the access-code chip vals[0] on, driven as decode_stream_range (wm_host_decode.h) drives it: a chip that
+ * carries the framer's reset marker (value bit 2) while the decoder receives aborts it BEFORE that chip.  Returns the chips consumed
+ * (0: the stream ended first), *done = 1 if they completed a telegram; `d` is left as the decoder stood, for wm_decoder_format. */
+unsigned wm_emu_decode_burst(int mode, const uint8_t *vals, const uint8_t *rssi, unsigned n, wm_decoder *d, int *done)
+{
+    wm_decoder_init(d, mode);
+    *done = 0;
+    int st = WM_DEC_IDLE;
+    for (unsigned k = 0; k < n; k++) {
+        if ((vals[k] & 4u) && st == WM_DEC_RECEIVING) { wm_decoder_abort(d); return k; }
+        st = wm_decoder_chip(d, vals[k] & 3u, rssi[k]);
+        if (st == WM_DEC_DONE) { *done = 1; return k + 1; }
+        if (st == WM_DEC_IDLE) return k + 1;
+    }
+    return 0;
+}
+
 }

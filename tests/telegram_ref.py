@@ -1,0 +1,289 @@
+"""A plain restatement of Wireless M-Bus telegrams (EN 13757-4 modes T1, C1 frame A / B, S1) for the telegram-space tests:
+how a telegram is framed and put on air, and what a chip-driven packet decoder does with the chips behind an access code.
+Pure Python and numpy, written from the standard's framing and from the five stop rules listed above `burst_item` in
+rtl-wmbus_amd/csrc/wm_k3_bursts.h; it shares no code with the kernel, with wm_decoder.c or with the oracle.
+
+Words used here.  The AIR bytes of a telegram are its bytes with the block CRCs in place, L-field first.  A CHIP is one
+recovered symbol of the 2-FSK signal; the framers mark the chip that completes the sync word with value 2 (the access-code
+chip), and a decoder starts on the chip behind it.  `chain` 0 receives T1 and C1 (100 kchip/s), chain 1 receives S1 (32.768 kchip/s).
+"""
+import numpy as np
+
+MODES = ("T1", "C1A", "C1B", "S1")
+CHAIN = {"T1": 0, "C1A": 0, "C1B": 0, "S1": 1}
+RSSI_GATE = 5                     # a decoder drops a telegram whose RSSI falls below this
+MAX_AIR = 290                     # frame A at L-field 255
+
+# EN 13757-4, table "3 out of 6": nibble -> six chips
+SYMBOL_OF_NIBBLE = (0b010110, 0b001101, 0b001110, 0b001011, 0b011100, 0b011001, 0b011010, 0b010011,
+                    0b101100, 0b100101, 0b100110, 0b100011, 0b110100, 0b110001, 0b110010, 0b101001)
+NIBBLE_OF_SYMBOL = {s: n for n, s in enumerate(SYMBOL_OF_NIBBLE)}
+INVALID_SYMBOLS = tuple(s for s in range(64) if s not in NIBBLE_OF_SYMBOL)
+
+
+def crc16(data):
+    """CRC-16 of EN 13757: polynomial 0x3D65, most significant bit first, start 0, result complemented."""
+    crc = 0
+    for byte in bytes(data):
+        crc ^= byte << 8
+        for _ in range(8):
+            crc = ((crc << 1) ^ 0x3D65) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
+    return crc ^ 0xFFFF
+
+
+assert crc16(b"123456789") == 0xC2B7
+
+
+def _with_crc(data):
+    c = crc16(data)
+    return bytes(data) + bytes([c >> 8, c & 255])
+
+
+def frame_a_length(lfield):
+    """Air bytes of a frame A whose L-field is `lfield`: L, `lfield` bytes, two CRC bytes per block of 10 / 16 / 16 ... data bytes."""
+    return 1 + lfield + 2 * (1 + (max(0, lfield - 9) + 15) // 16)
+
+
+def frame_a(telegram):
+    """Air bytes of the CRC-free telegram (telegram[0] = its L-field = len - 1): blocks of 10, then 16 data bytes, a CRC behind each."""
+    t = bytes(telegram)
+    assert len(t) >= 1 and t[0] == len(t) - 1
+    out, pos, blk = b"", 0, 10
+    while pos < len(t):
+        out += _with_crc(t[pos:pos + blk])
+        pos += blk
+        blk = 16
+    assert len(out) == frame_a_length(t[0])
+    return out
+
+
+def frame_b(total, fill):
+    """A VALID frame B of `total` air bytes (1 .. 256): L = total - 1 counts every byte behind itself, CRC bytes included; blocks of
+    128 air bytes, each ending in the CRC of the bytes before it in the block; the last block may be short, and a last block of two
+    bytes is the CRC of nothing (0xFFFF).  A last block of ONE byte (total 129) has no room for a CRC: it is a data byte, and no
+    receiver can find that telegram clean.  `fill`: the data bytes, taken in order (at least `total` of them)."""
+    assert 1 <= total <= 256
+    fill = iter(bytes(fill))
+    out = bytearray()
+    for start in range(0, total, 128):
+        blk = min(128, total - start)
+        room = blk >= (3 if start == 0 else 2)               # the first block holds the L-field before its CRC
+        data = bytearray(next(fill) for _ in range(blk - 2 if room else blk))
+        if start == 0:
+            data[0] = total - 1
+        out += _with_crc(data) if room else data
+    assert len(out) == total
+    return bytes(out)
+
+
+def blocks(frame_b_, n):
+    """[(start, length)] of the CRC blocks of `n` air bytes: frame A 12 then 18s, frame B 128s, the last one as long as what is left."""
+    out, start, blk = [], 0, 128 if frame_b_ else 12
+    while start < n:
+        out.append((start, min(blk, n - start)))
+        start += blk
+        blk = 128 if frame_b_ else 18
+    return out
+
+
+def crc_clean(frame_b_, air, n):
+    """The verdict a receiver prints: `n` air bytes (n = the length the L-field announced) are clean if there are at least 12 of them,
+    every block has room for its CRC and every CRC is the one of the block's bytes before it."""
+    if n < 12:
+        return False
+    for start, blk in blocks(frame_b_, n):
+        if blk < 2 or crc16(air[start:start + blk - 2]) != (air[start + blk - 2] << 8 | air[start + blk - 1]):
+            return False
+    return True
+
+
+def printed_hex(frame_b_, air, n):
+    """The hex field of a telegram's line: the air bytes without the CRC bytes, for frame B with the L-field lowered by two per block
+    (it counted them).  A telegram below 12 air bytes, a frame A with L-field 0 and a frame B with L-field below 2 print nothing."""
+    air = bytes(air)
+    if n < 12 or (air[0] < 2 if frame_b_ else air[0] == 0):
+        return ""
+    out = bytearray()
+    lfield = air[0]
+    for start, blk in blocks(frame_b_, n):
+        if blk < 2:
+            break
+        out += air[start:start + blk - 2]
+        if frame_b_:
+            lfield = (lfield - 2) & 255
+    if frame_b_:
+        out[0] = lfield
+    return out.hex()
+
+
+def _bits(value, n):
+    return [(value >> (n - 1 - i)) & 1 for i in range(n)]
+
+
+def body(mode, air):
+    """The chips of the air bytes behind the sync word: two 3-out-of-6 symbols per byte (T1); 0x54CD (frame A) or 0x543D (frame B) and
+    the bytes as they are (C1, NRZ); a pair per bit, 01 for a one and 10 for a zero (S1, Manchester)."""
+    out = []
+    if mode == "T1":
+        for b in bytes(air):
+            out += _bits(SYMBOL_OF_NIBBLE[b >> 4], 6) + _bits(SYMBOL_OF_NIBBLE[b & 15], 6)
+    elif mode in ("C1A", "C1B"):
+        out += _bits(0x54CD if mode == "C1A" else 0x543D, 16)
+        for b in bytes(air):
+            out += _bits(b, 8)
+    else:
+        assert mode == "S1"
+        for b in bytes(air):
+            for bit in _bits(b, 8):
+                out += [0, 1] if bit else [1, 0]
+    return out
+
+
+IDLE_TAIL = [0, 1] * 16
+
+
+def chips(mode, air, tail=IDLE_TAIL):
+    """A chip stream as a framer leaves it: the access-code chip (value 2), the telegram's chips, an idle tail."""
+    return [2] + body(mode, air) + list(tail)
+
+
+def expect(mode, chips_, rssi, resets=()):
+    """What a decoder of `mode`'s chain does from the access-code chip chips_[0] on.  chips_: chip values (bit 0 = the data chip),
+    rssi: one byte per chip, resets: the indices of chips that carry the framer's reset marker.
+
+    A decoder consumes chip after chip until the telegram is complete or one of five things stops it:
+      1. the access-code chip itself arrives with RSSI below the gate: the decoder is not armed, one chip consumed;
+      2. chip j >= 1 carries a framer reset: the decoder is reset BEFORE that chip, j chips consumed;
+      3. chip j arrives with RSSI below the gate and does not complete the telegram: dropped, j + 1 consumed;
+      4. chip j completes a Manchester pair 00 or 11 (S1; the L-field's pairs and the telegram's last pair included): j + 1 consumed;
+      5. the header is no header: an L-field symbol that is no 3-out-of-6 symbol where the twelve chips do not spell a C1 mode word
+         (12 chips behind the access code), or a C1 mode word whose trailer nibble is not 0xD (16 chips).
+    Returns None if the stream ends before the chips the header asks for are all there (such a burst travels on as chips), else
+    {consumed, done, bytes, L, c1, frame_b, err3of6, crc_ok, pkt_rssi, rssi_now}: L is the air length the L-field announces, bytes
+    what the decoder has stored (a C1 frame B that announces fewer than two bytes still stores two), pkt_rssi the RSSI at chip 1 and
+    rssi_now the one at the last chip consumed."""
+    v = np.asarray(chips_, np.int64) & 1
+    rssi = np.asarray(rssi, np.int64)
+    avail = len(v)
+    chain = CHAIN[mode]
+    c1 = fb = False
+    header_ok, lfield = True, 0
+
+    def field(first, n):
+        return int("".join(map(str, v[first:first + n])), 2)
+
+    if chain == 0:
+        if avail < 1 + 12:
+            return None
+        hi, lo = NIBBLE_OF_SYMBOL.get(field(1, 6)), NIBBLE_OF_SYMBOL.get(field(7, 6))
+        if hi is not None and lo is not None:
+            lfield, L = hi << 4 | lo, frame_a_length(hi << 4 | lo)
+            nbytes, per_byte, first_byte, need = L, 12, 1, 12 * L
+        elif field(1, 12) in (0x54C, 0x543):
+            c1, fb = True, field(1, 12) == 0x543
+            if avail < 1 + 24:
+                return None
+            if field(13, 4) != 0xD:
+                header_ok, need = False, 16
+            else:
+                lfield = field(17, 8)
+                L = 1 + lfield if fb else frame_a_length(lfield)
+                nbytes, per_byte, first_byte = max(L, 2), 8, 17
+                need = 16 + 8 * nbytes
+        else:
+            header_ok, need = False, 12
+    else:
+        if avail < 1 + 16:
+            return None
+        pairs = [field(1 + 2 * k, 2) for k in range(8)]
+        bad = [k for k, p in enumerate(pairs) if p in (0, 3)]
+        if bad:
+            header_ok, need = False, 2 * bad[0] + 2
+        else:
+            lfield = int("".join("1" if p == 1 else "0" for p in pairs), 2)
+            L = frame_a_length(lfield)
+            nbytes, per_byte, first_byte, need = L, 16, 1, 16 * L
+    if avail < need + 1:
+        return None
+    n = need + 1                                             # chips a decoder takes if nothing stops it, the access-code chip included
+
+    stops = []                                               # (chips consumed, kind)
+    if rssi[0] < RSSI_GATE:
+        stops.append(1)
+    for j in sorted(resets):
+        if 1 <= j < n:
+            stops.append(j)
+            break
+    low = np.nonzero(rssi[1:n] < RSSI_GATE)[0] + 1
+    for j in low:
+        if j + 1 < n or not header_ok:
+            stops.append(int(j) + 1)
+            break
+    if chain == 1 and header_ok:
+        pair = v[1:n:2] * 2 + v[2:n:2]
+        badp = np.nonzero((pair == 0) | (pair == 3))[0]
+        if badp.size:
+            stops.append(2 * int(badp[0]) + 3)               # the pair's second chip is chip 2 k + 2: 2 k + 3 consumed
+    if not header_ok:
+        stops.append(n)
+    if stops:
+        consumed = min(stops)
+        return dict(consumed=consumed, done=False, bytes=b"", L=0, c1=c1, frame_b=fb, err3of6=False, crc_ok=False,
+                    pkt_rssi=int(rssi[1]) if consumed > 1 else 0, rssi_now=int(rssi[consumed - 1]))
+
+    data, err36 = bytearray(), False
+    for b in range(nbytes):
+        at = first_byte + per_byte * b
+        if chain == 1:
+            val = int("".join("1" if field(at + 2 * k, 2) == 1 else "0" for k in range(8)), 2)
+        elif c1:
+            val = field(at, 8)
+        else:
+            hi, lo = NIBBLE_OF_SYMBOL.get(field(at, 6)), NIBBLE_OF_SYMBOL.get(field(at + 6, 6))
+            if hi is None or lo is None:
+                err36, val = True, 0xFF                      # an invalid symbol reads as all ones and they stick in the byte
+            else:
+                val = hi << 4 | lo
+        data.append(val)
+    return dict(consumed=n, done=True, bytes=bytes(data), L=L, c1=c1, frame_b=fb, err3of6=err36, crc_ok=crc_clean(fb, data, L),
+                pkt_rssi=int(rssi[1]), rssi_now=int(rssi[n - 1]))
+
+
+# ---- on air --------------------------------------------------------------------------------------------------------------------
+CHIP_RATE = {"T1": 100e3, "C1A": 100e3, "C1B": 100e3, "S1": 32768.0}
+DEVIATION = {"T1": 50e3, "C1A": 45e3, "C1B": 45e3, "S1": 50e3}
+POSTAMBLE = _bits(0x55, 8)
+
+
+def preamble(mode):
+    """Preamble and sync word: T1 19 x 01 and 0000111101; C1 16 x 01 and 0x543D; S1 30 x 01 and 000111011010010110."""
+    if mode == "T1":
+        return [0, 1] * 19 + _bits(0x03D, 10)
+    if mode in ("C1A", "C1B"):
+        return [0, 1] * 16 + _bits(0x543D, 16)
+    return [0, 1] * 30 + _bits(0x07696, 18)
+
+
+def modulate(telegrams, seed, fs=1.6e6, amplitude=60.0, sigma=2.0, gap=4000, block=4096):
+    """Continuous-phase 2-FSK of the telegrams, one after the other, as interleaved unsigned 8-bit I/Q at `fs`: `gap` samples of
+    receiver noise, then preamble, sync word, the telegram's chips and the postamble; a one is +deviation, a zero -deviation.
+    telegrams: (mode, air bytes) or (mode, chips behind the sync word) or either with a third entry `keep`, the fraction of the
+    burst after which the carrier stops.  The phase is summed in float64.  The capture ends with a gap and is padded with noise to
+    a whole number of `block` bytes."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for t in telegrams:
+        mode, what, keep = (tuple(t) + (1.0,))[:3]
+        seq = preamble(mode) + (body(mode, what) if isinstance(what, (bytes, bytearray)) else list(what)) + POSTAMBLE
+        n = int(len(seq) * fs / CHIP_RATE[mode])
+        which = np.minimum((np.arange(n) * (CHIP_RATE[mode] / fs)).astype(np.int64), len(seq) - 1)
+        step = (2.0 * np.asarray(seq, np.float64)[which] - 1.0) * (2.0 * np.pi * DEVIATION[mode] / fs)
+        phase = rng.uniform(0.0, 2.0 * np.pi) + np.cumsum(step)
+        iq = amplitude * np.stack([np.cos(phase), np.sin(phase)], axis=1)[: int(n * keep)]
+        parts += [np.zeros((gap, 2)), iq]
+    parts.append(np.zeros((gap, 2)))
+    x = np.concatenate(parts)
+    pad = -(2 * len(x)) % block // 2
+    x = np.concatenate([x, np.zeros((pad, 2))])
+    x = x + rng.normal(0.0, sigma, x.shape) + 127.5
+    return np.clip(np.rint(x), 0, 255).astype(np.uint8).reshape(-1)

@@ -209,7 +209,9 @@ def host_decoder_on_every_access_code(dec, ref, ch, al):
         err36, c1, fb = int(d[3]), int(d[4]), int(d[5])
         l_, L = int(d[6]) | int(d[7]) << 8, int(d[8]) | int(d[9]) << 8
         pkt_rssi = int(np.frombuffer(buf.raw[20:24], "<u4")[0])
-        out[int(i)] = dict(consumed=res[0], done=res[1], L=L, nbytes=l_, bytes=bytes(d[24:24 + l_]), c1=c1, fb=fb, err36=err36, pkt_rssi=pkt_rssi,
+        dec.wm_packet_crc_ok.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_int]
+        crc_ok = bool(res[1] and dec.wm_packet_crc_ok(ctypes.addressof(buf) + 24, L, fb))      # the host decoder's CRC verdict
+        out[int(i)] = dict(consumed=res[0], done=res[1], L=L, nbytes=l_, bytes=bytes(d[24:24 + l_]), c1=c1, fb=fb, err36=err36, crc_ok=crc_ok, pkt_rssi=pkt_rssi,
                            rssi_now=int(rssi[i + res[0] - 1]), sample=int(pos[i + res[0] - 1]))
     return out
 
@@ -246,6 +248,7 @@ def test_bursts_inside_the_push_are_decoded_like_the_host_decoder_would(emu_k3, 
                 if w["done"]:
                     fl = int(p["flags"])
                     assert (int(p["L"]), bool(fl & 1), bool(fl & 2), bool(fl & 4)) == (w["L"], bool(w["c1"]), bool(w["fb"]), bool(w["err36"])), (ch, al, i)
+                    assert bool(fl & 8) == w["crc_ok"], (ch, al, i)           # WM_PKTF_CRC_OK: nothing behind the kernel corrects it
                     assert bytes(pbytes[int(p["off"]):int(p["off"]) + w["nbytes"]]) == w["bytes"], (ch, al, i)
                     assert (int(p["pkt_rssi"]), int(p["rssi_now"]), int(p["sample"])) == (w["pkt_rssi"] & 0xFF, w["rssi_now"], w["sample"]), (ch, al, i)
                     n_done += 1
