@@ -100,6 +100,14 @@ typedef struct wmbus_cfg {
     unsigned rssi_full;         /* 1: the RSSI of every sample in the demodulation kernel even without debug views (A/B of RSSI on demand) */
     unsigned rssi_dense_pm;     /* RSSI on demand pauses for 16 pushes when more than this many per mille of a push's tiles were listed
                                    (0: 200; configs[2] lists 310 and is faster on the full pass) */
+    /* 0 (default): off.  1: CHANNEL POWER -- every datagram line comes with a power record (wmbus_power, wmbus_line_power() below): the
+     * signal in the telegram's 200 kHz channel, the noise floor in front of it and their ratio, measured on the GPU from the RAW input, in
+     * front of every gain and independent of input_agc, in the integer arithmetic defined below under CHANNEL POWER.  The field switches
+     * the survey on by itself, as input_afc does (wmbus_read_spectrum works), and the level records of line_levels, which carry every
+     * line's access-code sample (wmbus_line_levels works).  The lines themselves do not change.  0 is in every respect the context
+     * without this field: the same kernels, buffers and bytes.  Anything above 1 is WMBUS_EINVAL.  (The newest field: directly in front
+     * of bursts_to_host, nothing behind it moves.) */
+    unsigned line_power;
     unsigned bursts_to_host;    /* 1: every burst travels to the host packet decoders as chips (round 1's path) instead of being decoded
                                    on the GPU where it lies inside the push */
     /* 0 (default): the survey of input_spectrum / input_afc accumulates for ever (SPECTRUM below).  A = 1 ... 31: THE SURVEY FORGETS -- the
@@ -539,6 +547,63 @@ int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t 
  * pushes before the first lock; there is no switch per channel other than the range, and nothing tracks within a push. */
 typedef struct wmbus_afc { int32_t shift_hz; uint32_t locked, changes, ratio_q8; } wmbus_afc;
 long wmbus_read_input_afc(wmbus_ctx *ctx, unsigned stream, wmbus_afc *out);
+/* CHANNEL POWER (cfg.line_power = 1; tests/power_ref.py restates it in numpy and Python integers on top of tests/spectrum_ref.py).  Integers
+ * only; every division floors.  With pw[K][b] SPECTRUM's power of level block K (the stream's index of the block, counted from the
+ * stream's first sample over all pushes, 64 bits) and bin b (ascending from -Fin / 2):
+ *   band rows (the waterfall)   bp[K][j] = min(sum of pw[K][b] over b in [16 j, 16 j + 16), 2^32 - 1),  j = 0 .. 31: one row of 32 uint32
+ *                               per capture and level block, each band Fin / 32 wide
+ *   channel window              W  = clamp(floor(200000 x 512 / Fin), 1, 256), the survey's default window
+ *                               nb = min(32, ceil(W / 16) + 1): one band more than the window needs, so that a window of W bins fits at
+ *                               any alignment and nb is a constant of the context
+ *   centre of pipeline row r = chain x S + v (chain WMBUS_CHAIN_*, v the pipeline stream of CHANNELS, S their number):
+ *                               f_r = the frequency the stage kernel of THIS push rotates stream v by -- cfg.input_shift_hz,
+ *                               cfg.input_channel_hz[c], or under AFC / CHANNEL AFC the held_hz the push was rotated with -- and with
+ *                               cfg.simultaneous + 325000 for the T1/C1 chain, - 325000 for the S1 chain (the demodulation kernel's own
+ *                               shift: it takes T1/C1 from above the centre)
+ *                               cb = 256 + floor((1024 f_r + Fin) / (2 Fin)),   lo = clamp(cb - W / 2, 0, 512 - W)   (W / 2 floors),
+ *                               j0 = min(lo >> 4, 32 - nb)
+ *   channel power               P[r][K] = min(sum of bp[K][j0 .. j0 + nb), 2^32 - 1)
+ *   line record                 for a line with access-code sample a (wmbus_level.sync_sample) and completing sample e
+ *                               (wmbus_line.sample), both decimated samples:  m(n) = floor(n D M / L) with D the decimation and L / M
+ *                               the resampler's ratio (1 / 1 without one);  ka = m(a) >> 9,  ke = m(e) >> 9
+ *       signal blocks           ka < K < ke, whole level blocks strictly inside the telegram (the pipeline's filter delay, a few tens of
+ *                               samples, is ignored).  number = their count;  n_signal = min(number, 65535);
+ *                               signal = floor(sum of P / number)  (the count itself, not the capped field)
+ *       noise blocks            K in [ka - G - Nn, ka - G) with K >= 0;  G = ceil(Fin / 51200), 10 ms, the longest preamble;
+ *                               Nn = ceil(Fin / 25600), 20 ms.  number = their count;  n_noise = min(number, 65535);
+ *                               noise = the element at index floor(number / 4) of their P sorted ascending: the lower quartile -- other
+ *                               telegrams inside the window do not lift it
+ *       ratio_q8                = min(floor(signal x 256 / noise), 2^32 - 1);  0 when n_signal or n_noise is 0;  for noise = 0:
+ *                               2^32 - 1 when signal > 0, else 0
+ *       first_block             = ka
+ * The two clamps are guards no input reaches: the pw of all 512 bins of a level block add up to 512 x sum |y|^2 >> 16, at most 0.75 x 2^32.
+ * P is a ratio's raw material, not a physical unit: signal and noise are in the survey's units of pw (SPECTRUM), summed over nb bands
+ * (nb / 32 of the capture's bandwidth).  Sums of integers do not depend on the order of a reduction and a push always holds whole level
+ * blocks, so rows, P and the records do not depend on how the input is cut into pushes: the context keeps, per row, P of the last
+ * Nn + G + ceil(0.15 Fin / 512) level blocks in front of the current push (an S1 telegram of L = 255 lasts about 142 ms), so a level
+ * block K < 0 is the only missing one.  The survey reads the raw bytes of a push, the pipeline may hold back a partial 4096-byte block
+ * of converted bytes: P is always at or ahead of the lines.  The one exception is AFC, as in AFC's own contract: the window follows the
+ * lock push by push, so P (and a record whose blocks straddle a change) depends on the cut there.  With cfg.input_spectrum_age every level
+ * block of a push still gets its row; only the survey's accumulators skip old epochs.
+ *
+ * wmbus_line_power: the power records of the last push's lines, the same count and the same order as wmbus_lines() (cfg.dedup_twins /
+ * only_crc_ok drop a record with its line).  A context opened without cfg.line_power: 0, and *power = NULL.
+ * wmbus_read_waterfall: the band rows of the last push of one capture, 32 uint32 per level block into rows[0 .. 32 x cap_rows);
+ * *first_block (may be NULL) receives the stream's index of the first row.  Returns the rows written.
+ * wmbus_read_channel_power: P of the last push of pipeline row chain x S + stream_v into p[0 .. cap); *first_block as above.  Returns the
+ * values written.  Both reads are to be called when no push is in flight (after wmbus_collect), need no cfg.keep_taps and return
+ * WMBUS_EINVAL on a context without cfg.line_power.
+ * wmbus_line_power_rule: the line record above from a timeline; host only, no device needed.  p[0 .. n) holds P of level blocks
+ * first_block .. first_block + n - 1; a level block outside the array counts as missing, like K < 0.  WMBUS_EINVAL for in_hz < 800000 or
+ * NULL pointers (p may be NULL for n = 0).
+ * wmbus_line_power_block: m(sample) >> 9 for a context of that decimation and input rate (0: decimation x 800000); host only.
+ * WMBUS_EINVAL where wmbus_resampler_design refuses the rate. */
+typedef struct wmbus_power { uint64_t first_block; uint32_t signal, noise, ratio_q8; uint16_t n_signal, n_noise; } wmbus_power;
+size_t wmbus_line_power(const wmbus_ctx *ctx, const wmbus_power **power);
+long wmbus_read_waterfall(wmbus_ctx *ctx, unsigned capture, uint32_t *rows, uint64_t *first_block, size_t cap_rows);
+long wmbus_read_channel_power(wmbus_ctx *ctx, int chain, unsigned stream_v, uint32_t *p, uint64_t *first_block, size_t cap);
+int  wmbus_line_power_rule(const uint32_t *p, uint64_t first_block, size_t n, uint64_t ka, uint64_t ke, unsigned in_hz, wmbus_power *out);
+int  wmbus_line_power_block(unsigned decimation, unsigned input_rate_hz, uint64_t sample, uint64_t *block);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):
@@ -654,6 +719,8 @@ int  wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats
  * meanwhile and the calls are serialised: no race).  Returns the count; 0 with *levels = NULL for any other first_stream or without
  * cfg.line_levels. */
 size_t wmbus_batch_line_levels(const wmbus_batch *b, unsigned first_stream, const wmbus_level **levels);
+/* The same for a batch opened with cfg.line_power: the power records of the lines the `lines` callback has just been handed. */
+size_t wmbus_batch_line_power(const wmbus_batch *b, unsigned first_stream, const wmbus_power **power);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ class Cfg(ctypes.Structure):
                 ("keep_taps", ctypes.c_int), ("prefilter", ctypes.c_int), ("atan_mode", ctypes.c_int), ("spill_words", ctypes.c_uint), ("dedup_twins", ctypes.c_int), ("only_crc_ok", ctypes.c_int),
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
-                ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
+                ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("line_power", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("input_spectrum_age", ctypes.c_uint), ("input_channel_afc_hz", ctypes.c_uint * MAX_CHANNELS),
                 ("burst_caps", ctypes.c_uint * 4), ("input_afc", ctypes.c_uint), ("input_afc_range_hz", ctypes.c_uint), ("k1_small_tile", ctypes.c_uint),
                 ("input_spectrum", ctypes.c_uint), ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
@@ -72,6 +72,17 @@ class Level(ctypes.Structure):
 
     def as_dict(self):
         return dict(sync_sample=int(self.sync_sample), offset_hz=int(self.offset_hz), dev_hz=int(self.dev_hz), n=int(self.n))
+
+
+class Power(ctypes.Structure):
+    """wmbus_power: the signal in a line's channel, the noise floor in front of its telegram and their ratio (cfg.line_power), from the raw
+    input; n_signal / n_noise = 0: not measured."""
+    _fields_ = [("first_block", ctypes.c_uint64), ("signal", ctypes.c_uint32), ("noise", ctypes.c_uint32), ("ratio_q8", ctypes.c_uint32),
+                ("n_signal", ctypes.c_uint16), ("n_noise", ctypes.c_uint16)]
+
+    def as_dict(self):
+        return dict(first_block=int(self.first_block), signal=int(self.signal), noise=int(self.noise), ratio_q8=int(self.ratio_q8),
+                    n_signal=int(self.n_signal), n_noise=int(self.n_noise))
 
 
 class ChannelHit(ctypes.Structure):
@@ -138,7 +149,8 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
            "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
-           "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc"]
+           "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc",
+           "wmbus_line_power", "wmbus_batch_line_power", "wmbus_read_waterfall", "wmbus_read_channel_power", "wmbus_line_power_rule", "wmbus_line_power_block"]
 
 _lib = None
 
@@ -176,6 +188,12 @@ def lib():
         L.wmbus_read_spectrum.argtypes = [vp, u, vp, vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]; L.wmbus_read_spectrum.restype = ctypes.c_long
         L.wmbus_spectrum_channels.argtypes = [u, vp, vp, ctypes.c_uint64, u, u, u, ctypes.POINTER(ChannelHit), u]
         L.wmbus_read_input_afc.argtypes = [vp, u, ctypes.POINTER(Afc)]; L.wmbus_read_input_afc.restype = ctypes.c_long
+        L.wmbus_line_power.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Power))]; L.wmbus_line_power.restype = sz
+        L.wmbus_batch_line_power.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Power))]; L.wmbus_batch_line_power.restype = sz
+        L.wmbus_read_waterfall.argtypes = [vp, u, vp, ctypes.POINTER(ctypes.c_uint64), sz]; L.wmbus_read_waterfall.restype = ctypes.c_long
+        L.wmbus_read_channel_power.argtypes = [vp, ctypes.c_int, u, vp, ctypes.POINTER(ctypes.c_uint64), sz]; L.wmbus_read_channel_power.restype = ctypes.c_long
+        L.wmbus_line_power_rule.argtypes = [vp, ctypes.c_uint64, sz, ctypes.c_uint64, ctypes.c_uint64, u, ctypes.POINTER(Power)]
+        L.wmbus_line_power_block.argtypes = [u, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -237,6 +255,26 @@ def spectrum_channels(in_hz, total, peak, blocks, width_hz=0, min_ratio_q8=0, re
     return [out[i].as_dict() for i in range(n)]
 
 
+def line_power_rule(p, first_block, ka, ke, in_hz):
+    """wmbus_line_power_rule (host only): the power record of a line whose access code lies in level block ka and whose last chip in ke,
+    from p = P of level blocks first_block ... as Receiver.read_channel_power returns it; a dict of the record's fields."""
+    p = np.ascontiguousarray(p, np.uint32)
+    out = Power()
+    rc = lib().wmbus_line_power_rule(p.ctypes.data if p.size else None, int(first_block), p.size, int(ka), int(ke), int(in_hz), ctypes.byref(out))
+    if rc:
+        raise WmbusError(f"wmbus_line_power_rule failed: {rc}")
+    return out.as_dict()
+
+
+def line_power_block(sample, decimation=2, input_rate_hz=0):
+    """wmbus_line_power_block (host only): the level block of the raw input that decimated sample `sample` stands for."""
+    out = ctypes.c_uint64()
+    rc = lib().wmbus_line_power_block(int(decimation), int(input_rate_hz), int(sample), ctypes.byref(out))
+    if rc:
+        raise WmbusError(f"wmbus_line_power_block failed: {rc}")
+    return int(out.value)
+
+
 def pinned_array(nbytes):
     """uint8 numpy array over page-locked host memory (kept alive by the array's base object)."""
     p = lib().wmbus_alloc_pinned(nbytes)
@@ -279,7 +317,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
-              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None):
+              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None, line_power=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -313,6 +351,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     # library's limit are dropped here; one beyond the channel list is passed on, so that wmbus_open refuses it with its message
     for i, r in enumerate(list(input_channel_afc_hz if input_channel_afc_hz is not None else ())[:MAX_CHANNELS]):
         c.input_channel_afc_hz[i] = int(r)
+    c.line_power = int(line_power)           # 1: a power record (signal, noise floor, ratio) per line from the raw input: Receiver.line_power(), read_waterfall(), read_channel_power()
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
     # more entries than the library takes are passed on as a count, so that wmbus_open refuses them with its message
@@ -409,6 +448,11 @@ class Batch:
                     assert lib().wmbus_batch_line_levels(self._h, first, ctypes.byref(p)) == n_lines
                     for k, r in enumerate(recs):
                         r["level"] = p[k].as_dict()
+                if self.cfg.line_power:                # the same for the power records
+                    p = ctypes.POINTER(Power)()
+                    assert lib().wmbus_batch_line_power(self._h, first, ctypes.byref(p)) == n_lines
+                    for k, r in enumerate(recs):
+                        r["power"] = p[k].as_dict()
             on_push(first, n, recs, timing.contents.as_dict())
         return LINES_FN(c_lines)
 
@@ -504,6 +548,31 @@ class Receiver:
         p = ctypes.POINTER(Level)()
         n = lib().wmbus_line_levels(self._h, ctypes.byref(p))
         return [p[i].as_dict() for i in range(n)]
+
+    def line_power(self):
+        """The power records of the last push's lines, in the order of lines() (a context opened with line_power=1; else [])."""
+        p = ctypes.POINTER(Power)()
+        n = lib().wmbus_line_power(self._h, ctypes.byref(p))
+        return [p[i].as_dict() for i in range(n)]
+
+    def read_waterfall(self, capture, max_rows=1 << 20):
+        """(rows uint32 [n, 32], first_block): the band rows of the last push of one capture (a context with line_power): band j of a row
+        holds bins [16 j, 16 j + 16) of that level block's spectrum, Fin / 32 wide, ascending from -Fin / 2."""
+        rows = np.zeros((max_rows, 32), np.uint32)
+        first = ctypes.c_uint64()
+        n = lib().wmbus_read_waterfall(self._h, capture, rows.ctypes.data, ctypes.byref(first), max_rows)
+        if n < 0:
+            raise WmbusError(f"read_waterfall failed: {n}: {lib().wmbus_last_error(self._h).decode()}")
+        return rows[:n].copy(), int(first.value)
+
+    def read_channel_power(self, chain, stream, max_blocks=1 << 20):
+        """(P uint32 [n], first_block): the channel power of pipeline row (chain, stream) over the level blocks of the last push."""
+        p = np.zeros(max_blocks, np.uint32)
+        first = ctypes.c_uint64()
+        n = lib().wmbus_read_channel_power(self._h, chain, stream, p.ctypes.data, ctypes.byref(first), max_blocks)
+        if n < 0:
+            raise WmbusError(f"read_channel_power failed: {n}: {lib().wmbus_last_error(self._h).decode()}")
+        return p[:n].copy(), int(first.value)
 
     def lines_count(self):
         return int(lib().wmbus_lines(self._h, None))

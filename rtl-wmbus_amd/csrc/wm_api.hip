@@ -159,6 +159,23 @@ struct wmbus_ctx {
         K0AfcPush *d_push = nullptr;                   /* [n] {step, base} of the last push */
         K0AfcArgs args{};                              /* this push's arguments of k0_afc_plan (k0_plan) */
     } afc;
+    /* cfg.line_power: channel power (wm_k0_power.h) -- the band form of k0_spectrum writes a row of 32 bands per capture and level block,
+     * k0_channel_power (behind k0_afc_plan where there is one) sums every pipeline row's window into P, P travels to pinned host memory
+     * with the push, and wait_gpu appends it to the row's history: what decode_host turns into a record per line.  All nullptr / empty
+     * without the option. */
+    struct {
+        bool on = false;
+        uint32_t fin = 0, blk_cap = 0, hist = 0;       /* Fin; level blocks of a full push; level blocks kept in front of the current push */
+        uint32_t *d_bands = nullptr;                   /* [NC][32 blk_cap] */
+        uint32_t *d_P = nullptr, *h_P = nullptr;       /* [2 S][blk_cap] */
+        uint64_t K = 0;                                /* the stream's index of the next push's first level block */
+        uint64_t last_first = 0; uint32_t last_blk = 0;    /* the push in flight (or the last one): its first level block, their number */
+        K0PowArgs args{};                              /* this push's arguments of k0_channel_power */
+        std::vector<std::vector<uint32_t>> ring;       /* [2 S] P of level blocks ring_first ...: the history and the last collected push */
+        uint64_t ring_first = 0;
+        uint64_t got_first = 0; uint32_t got_blk = 0;  /* the last collected push */
+    } pw;
+    std::vector<wmbus_power> powers;                   /* parallel to `lines` */
     /* device buffers */
     uint8_t *d_in = nullptr;                           /* [n_win][S][in_stride] */
     uint8_t *d_hist = nullptr;                         /* [S][4096] the input history of the next push (see k_copy_hist) */
@@ -414,6 +431,11 @@ double now_ms()
 
 }  // namespace
 
+static void power_record(wmbus_power *out, const K0PowRecord &r)
+{
+    out->first_block = r.first_block; out->signal = r.signal; out->noise = r.noise; out->ratio_q8 = r.ratio_q8; out->n_signal = r.n_signal; out->n_noise = r.n_noise;
+}
+
 #include "wm_host_decode.h"
 
 extern "C" {
@@ -579,9 +601,11 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     if (cfg->input_agc && cfg->input_gain_q8 != 0u && cfg->input_gain_q8 != 256u)
         return fail(c, WMBUS_EINVAL, "input_agc takes the place of input_gain_q8: leave that 0 or 256 (got %u)", cfg->input_gain_q8);
     if (cfg->line_levels > 1u) return fail(c, WMBUS_EINVAL, "line_levels must be 0 or 1, got %u", cfg->line_levels);
-    c->lev_on = cfg->line_levels != 0u;
+    if (cfg->line_power > 1u) return fail(c, WMBUS_EINVAL, "line_power must be 0 or 1, got %u", cfg->line_power);
+    c->lev_on = cfg->line_levels != 0u || cfg->line_power != 0u;      /* a power record needs its line's access-code sample: the level record carries it */
+    c->pw.on = cfg->line_power != 0u;
     if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
-    c->spec.on = cfg->input_spectrum != 0u;
+    c->spec.on = cfg->input_spectrum != 0u || c->pw.on;          /* the band rows are the survey's */
     auto &k = c->k0;
     k.dc = cfg->input_dc; k.agc = cfg->input_agc != 0u;
     k.fmt = cfg->input_format; k.bps = k0_bps((int)cfg->input_format); k.gain = cfg->input_gain_q8;
@@ -675,6 +699,13 @@ static int open_geometry(wmbus_ctx *c)
         c->push_cap = (size_t)((most + WMBUS_BLOCK_BYTES - 1u) / WMBUS_BLOCK_BYTES * WMBUS_BLOCK_BYTES + WMBUS_BLOCK_BYTES);
         c->k0.raw_stride = (cfg->max_push_bytes + 255u) / 256u * 256u;
         c->k0.dc_stride = (uint32_t)(cfg->max_push_bytes / c->k0.bps) >> WM_K0_DC_LOG2;
+    }
+    if (c->pw.on) {
+        auto &w = c->pw;
+        w.fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+        w.blk_cap = (uint32_t)(cfg->max_push_bytes / c->k0.bps) >> WM_K0_DC_LOG2;
+        /* Nn + G + ceil(0.15 Fin / 512) level blocks in front of the current push: the noise window of the longest telegram that ends in it */
+        w.hist = (w.fin + 25599u) / 25600u + (w.fin + 51199u) / 51200u + (uint32_t)((3ull * w.fin + 10239u) / 10240u);
     }
     /* Time segments: 32768 / 8192 decimated samples for batches of whole waves (r02 / r03 A/Bs: clock 65536 -8 %, 16384 -25 %;
      * run-length 16384 -9 %, 4096 -20 %).  A batch with fewer captures than a wave has lanes is bound by how long ONE lane
@@ -808,6 +839,12 @@ static int open_allocate(wmbus_ctx *c)
         A(m.dalloc(&c->spec.d_slots, (size_t)2 * c->spec.slot_stride));
         c->spec.d_sum = c->spec.d_slots; c->spec.d_blocks = c->spec.d_sum + (size_t)c->NC * WM_K0_SPEC_BINS;
         c->spec.d_peak = (uint32_t *)(c->spec.d_blocks + c->NC);
+    }
+    if (c->pw.on) {
+        A(m.dalloc(&c->pw.d_bands, (size_t)c->NC * WM_K0_POW_BANDS * c->pw.blk_cap));
+        A(m.dalloc(&c->pw.d_P, (size_t)rows * c->pw.blk_cap));
+        A(m.halloc(&c->pw.h_P, (size_t)rows * c->pw.blk_cap));
+        c->pw.ring.assign((size_t)rows, std::vector<uint32_t>());
     }
     if (c->afc.on) {
         c->afc.n = c->afc.chan ? c->S : c->NC;
@@ -1223,6 +1260,10 @@ static int spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, ui
 #undef K0_SPEC_AGE
     void (*const kernel[2][4])(K0SpecArgs) = {{k0_spectrum<WM_K0_CU8, false>, k0_spectrum<WM_K0_CS8, false>, k0_spectrum<WM_K0_CS16, false>, k0_spectrum<WM_K0_CF32, false>},
                                               {k0_spectrum<WM_K0_CU8, true>, k0_spectrum<WM_K0_CS8, true>, k0_spectrum<WM_K0_CS16, true>, k0_spectrum<WM_K0_CF32, true>}};
+    /* cfg.line_power: the band form of either */
+#define K0_SPEC_BANDS(DC, AGE) {k0_spectrum<WM_K0_CU8, DC, AGE, true>, k0_spectrum<WM_K0_CS8, DC, AGE, true>, k0_spectrum<WM_K0_CS16, DC, AGE, true>, k0_spectrum<WM_K0_CF32, DC, AGE, true>}
+    void (*const banded[2][2][4])(K0SpecArgs) = {{K0_SPEC_BANDS(false, false), K0_SPEC_BANDS(true, false)}, {K0_SPEC_BANDS(false, true), K0_SPEC_BANDS(true, true)}};      /* [age][dc][fmt] */
+#undef K0_SPEC_BANDS
     K0SpecArgs a{};
     a.raw = raw; a.raw_stride = raw_stride;
     a.dc_tab = c->k0.dc ? c->k0.d_dc_tab : nullptr; a.dc_stride = c->k0.dc_stride;
@@ -1239,8 +1280,37 @@ static int spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, ui
         if (plan.clear == 3u) HIPCHK(c, hipMemsetAsync(c->spec.d_slots, 0, (size_t)2 * c->spec.slot_stride * sizeof(uint64_t), c->stream));
         else if (plan.clear) HIPCHK(c, hipMemsetAsync(c->spec.d_slots + (plan.clear >> 1) * c->spec.slot_stride, 0, (size_t)c->spec.slot_stride * sizeof(uint64_t), c->stream));
     }
+    if (c->pw.on) {
+        /* the one place where a push's level blocks enter the waterfall: K moves on here and nowhere else */
+        if (n_blk > c->pw.blk_cap) return fail(c, WMBUS_EINVAL, "internal error: a push of %u level blocks, the band rows hold %u", n_blk, c->pw.blk_cap);
+        a.bands = c->pw.d_bands; a.band_stride = (uint64_t)WM_K0_POW_BANDS * c->pw.blk_cap;
+        c->pw.last_first = c->pw.K; c->pw.last_blk = n_blk; c->pw.K += n_blk;
+    }
     const uint32_t runs = (n_blk + a.run - 1u) / a.run;
-    hipLaunchKernelGGL((c->spec.age ? aged : kernel)[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+    hipLaunchKernelGGL(c->pw.on ? banded[c->spec.age != 0u][c->k0.dc != 0u][c->k0.fmt] : (c->spec.age ? aged : kernel)[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+    return WMBUS_OK;
+}
+
+/* cfg.line_power: P of this push's level blocks for every pipeline row, behind the survey's band rows and -- where there is one -- behind
+ * k0_afc_plan, whose committed state names the centre this push is rotated to; then P to pinned host memory, on the context's stream. */
+static int power_launch(wmbus_ctx *c)
+{
+    auto &w = c->pw;
+    const uint32_t n_blk = w.last_blk;
+    if (!n_blk) return WMBUS_OK;
+    K0PowArgs a{};
+    a.bands = w.d_bands; a.band_stride = (uint64_t)WM_K0_POW_BANDS * w.blk_cap;
+    a.P = w.d_P; a.p_stride = w.blk_cap;
+    a.afc = c->afc.on ? c->afc.args.st_out : nullptr;
+    a.S = c->S; a.n_ch = c->CH; a.n_blk = n_blk; a.in_hz = w.fin;
+    if (c->k0.chan) for (uint32_t ch = 0; ch < c->CH; ch++) a.centre_hz[ch] = c->cfg.input_channel_hz[ch];
+    else a.centre_hz[0] = c->cfg.input_shift_hz;
+    if (c->cfg.simultaneous) { a.chain_hz[WMBUS_CHAIN_T1C1] = WM_K0_POW_SIM_HZ; a.chain_hz[WMBUS_CHAIN_S1] = -WM_K0_POW_SIM_HZ; }
+    w.args = a;
+    hipLaunchKernelGGL(k0_channel_power, dim3((n_blk + WM_K0_POW_THREADS / 32u - 1u) / (WM_K0_POW_THREADS / 32u), c->S, 2u), dim3(WM_K0_POW_THREADS), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy2DAsync(w.h_P, (size_t)w.blk_cap * sizeof(uint32_t), w.d_P, (size_t)w.blk_cap * sizeof(uint32_t), (size_t)n_blk * sizeof(uint32_t), (size_t)2 * c->S,
+                               hipMemcpyDeviceToHost, c->stream));
     return WMBUS_OK;
 }
 
@@ -1284,6 +1354,7 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
     if (c->spec.on) { const int rc = spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2); if (rc) return rc; }      /* per capture, in front of the rotation, behind the blocker's table */
     /* cfg.input_afc: every capture's {step, base} for this push from its max-hold as it stands now, and the state commit, in ONE short launch */
     if (c->afc.on) hipLaunchKernelGGL(k0_afc_plan, dim3(c->NC, c->afc.chan ? c->CH : 1u), dim3(WM_K0_AFC_THREADS), 0, c->stream, c->afc.args);
+    if (c->pw.on) { const int rc = power_launch(c); if (rc) return rc; }
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
         hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
@@ -1368,7 +1439,10 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
             /* the survey of a context on the plain cu8 path reads the device input window itself (a push of that path is whole 4096-byte
              * blocks and always has decimated samples: this branch is taken); the context stays on the plain path */
-            else if (c->spec.on) { rc = spec_launch(c, win + WM_HIST_BYTES, c->in_stride, (uint32_t)(nbytes / 2u) >> WM_K0_DC_LOG2); if (rc) return rc; }
+            else if (c->spec.on) {
+                rc = spec_launch(c, win + WM_HIST_BYTES, c->in_stride, (uint32_t)(nbytes / 2u) >> WM_K0_DC_LOG2); if (rc) return rc;
+                if (c->pw.on) { rc = power_launch(c); if (rc) return rc; }
+            }
             /* The hand-over of the turn costs 0.15-0.2 ms (the next context's stream sits in an event wait on another
              * hardware queue; r03 trace: median 128 us between one K1 and the next, eight times per step = 5 % of it).
              * So the turn is handed over EARLY: a push's tiles leave in two launches, the event the next context waits for
@@ -1598,6 +1672,17 @@ static int wait_gpu(wmbus_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->in_flight = false;
     c->tim = wmbus_timing{};
+    if (c->pw.on && c->pw.last_blk) {                        /* this push's P behind the history: the last pw.hist level blocks in front of it stay */
+        auto &w = c->pw;
+        const size_t drop = w.ring[0].size() > w.hist ? w.ring[0].size() - w.hist : 0u;      /* ring_first + size == last_first: every push's level blocks pass through here once */
+        for (size_t r = 0; r < w.ring.size(); r++) {
+            std::vector<uint32_t> &v = w.ring[r];
+            v.erase(v.begin(), v.begin() + drop);
+            v.insert(v.end(), w.h_P + r * w.blk_cap, w.h_P + r * w.blk_cap + w.last_blk);
+        }
+        w.ring_first += drop;
+        w.got_first = w.last_first; w.got_blk = w.last_blk; w.last_blk = 0;
+    }
     if (c->k0.on) { c->tim.input_bytes_out = c->k0.last_out; c->tim.input_clipped = c->h_scalars[SC_CLIP]; }
     if (c->last.M > 0) {
         auto span = [&](int from, int to) { float ms = 0; hipEventElapsedTime(&ms, c->ev[from], c->ev[to]); return ms; };
@@ -1665,7 +1750,7 @@ int wmbus_collect(wmbus_ctx *c)
 {
     if (!c) return WMBUS_EINVAL;
     const int rc = wait_gpu(c);
-    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); return rc; }
+    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); return rc; }
     return decode_host(c);
 }
 
@@ -1701,6 +1786,53 @@ size_t wmbus_line_levels(const wmbus_ctx *c, const wmbus_level **levels)
 {
     if (levels) *levels = c && c->lev_on ? c->levels.data() : nullptr;
     return c && c->lev_on ? c->levels.size() : 0;
+}
+
+size_t wmbus_line_power(const wmbus_ctx *c, const wmbus_power **power)
+{
+    if (power) *power = c && c->pw.on ? c->powers.data() : nullptr;
+    return c && c->pw.on ? c->powers.size() : 0;
+}
+
+long wmbus_read_waterfall(wmbus_ctx *c, unsigned capture, uint32_t *rows, uint64_t *first_block, size_t cap_rows)
+{
+    if (!c || capture >= c->NC || !rows) return WMBUS_EINVAL;
+    if (!c->pw.on) return fail(c, WMBUS_EINVAL, "read_waterfall: the context was opened without cfg.line_power");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_waterfall: collect the push first");
+    const size_t n = std::min(cap_rows, (size_t)c->pw.got_blk);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n) HIPCHK(c, hipMemcpy(rows, c->pw.d_bands + (size_t)capture * WM_K0_POW_BANDS * c->pw.blk_cap, n * WM_K0_POW_BANDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (first_block) *first_block = c->pw.got_first;
+    return (long)n;
+}
+
+long wmbus_read_channel_power(wmbus_ctx *c, int chain, unsigned stream_v, uint32_t *p, uint64_t *first_block, size_t cap)
+{
+    if (!c || chain < 0 || chain > 1 || stream_v >= c->S || !p) return WMBUS_EINVAL;
+    if (!c->pw.on) return fail(c, WMBUS_EINVAL, "read_channel_power: the context was opened without cfg.line_power");
+    if (c->in_flight) return fail(c, WMBUS_EINVAL, "read_channel_power: collect the push first");
+    const std::vector<uint32_t> &v = c->pw.ring[(size_t)chain * c->S + stream_v];
+    const size_t n = std::min(cap, (size_t)c->pw.got_blk);
+    if (n) memcpy(p, v.data() + (v.size() - c->pw.got_blk), n * sizeof(uint32_t));
+    if (first_block) *first_block = c->pw.got_first;
+    return (long)n;
+}
+
+int wmbus_line_power_rule(const uint32_t *p, uint64_t first_block, size_t n, uint64_t ka, uint64_t ke, unsigned in_hz, wmbus_power *out)
+{
+    if (!out || (!p && n) || in_hz < 800000u) return WMBUS_EINVAL;
+    std::vector<uint32_t> scratch;
+    power_record(out, k0_line_power_rule(p, first_block, n, ka, ke, in_hz, scratch));
+    return WMBUS_OK;
+}
+
+int wmbus_line_power_block(unsigned decimation, unsigned input_rate_hz, uint64_t sample, uint64_t *block)
+{
+    if (!block || decimation < 1 || decimation > WM_MAX_DECIM) return WMBUS_EINVAL;
+    unsigned L = 1, M = 1, T = 0;
+    if (input_rate_hz && input_rate_hz != decimation * 800000u && k0_design(input_rate_hz, decimation * 800000u, &L, &M, &T, nullptr, 0)) return WMBUS_EINVAL;
+    *block = k0_pow_block_of(sample, decimation, L, M);
+    return WMBUS_OK;
 }
 
 const char *wmbus_lines_text(const wmbus_ctx *c, size_t *len)

@@ -194,7 +194,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
  * and the decoders only, so the NEXT push's front may already be on the GPU. */
 static int decode_host(wmbus_ctx *c)
 {
-    c->lines.clear(); c->text.clear(); c->levels.clear();
+    c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear();
     c->short_burst.store(0);
     if (!c->done.valid) return WMBUS_OK;
     c->done.valid = false;
@@ -270,6 +270,7 @@ static int decode_host(wmbus_ctx *c)
         }
         all.swap(kept);
     }
+    std::vector<uint32_t> pw_scratch;
     for (auto &r : all) {
         wmbus_line l{};
         /* r.stream is the pipeline stream v = capture * CH + channel (the sort above: captures ascending, channels within a capture) */
@@ -279,6 +280,16 @@ static int decode_host(wmbus_ctx *c)
         c->text.append(parts[r.part].text, r.off, r.len);
         c->lines.push_back(l);
         if (c->lev_on) c->levels.push_back(parts[r.part].levs[r.lev]);
+        if (c->pw.on) {
+            /* cfg.line_power: the line's record from its row's P history (wm_k0_power.h).  Its access-code sample came with the level record
+             * -- for a burst finished in a later push the decoder kept it -- its completing sample is the line's; both are decimated
+             * samples of the pipeline's stream, m(n) = floor(n D M / L) the raw input sample they stand for. */
+            const std::vector<uint32_t> &p = c->pw.ring[(size_t)r.chain * c->S + r.stream];
+            const uint64_t ka = k0_pow_block_of(parts[r.part].levs[r.lev].sync_sample, c->d, c->k0.L, c->k0.M), ke = k0_pow_block_of(r.sample, c->d, c->k0.L, c->k0.M);
+            wmbus_power rec{};
+            power_record(&rec, k0_line_power_rule(p.data(), c->pw.ring_first, p.size(), ka, ke, c->pw.fin, pw_scratch));
+            c->powers.push_back(rec);
+        }
     }
     c->tim.host_decode_ms = (float)(now_ms() - t0);
     if (const uint32_t sb = c->short_burst.load()) {       /* formatted once, after the pool has joined */

@@ -35,6 +35,14 @@
  * below: the one owner of that decision, shared with the emulator harness of the tests); the AGE form of the kernel leaves out the level
  * blocks of epochs below e_keep -- a prefix of the push, not transformed at all -- and flushes its registers whenever the epoch changes
  * inside a wave's run, and at its end, with the same atomics.  AGE = false is the code above.
+ *
+ * The band form (cfg.line_power, include/wmbus_hip.h, CHANNEL POWER; tests/power_ref.py): BANDS = true keeps the time axis, coarsely.  At
+ * the end of a level block a lane holds pw of bins 64 (q ^ 4) + lane, q = 0 .. 7: a band of 16 bins is 16 consecutive lanes of one q, a
+ * DPP row.  Each row is summed in 64 bits in four steps (quad_perm 1 0 3 2, quad_perm 2 3 0 1, row_half_mirror, row_mirror: after every
+ * step the partners hold the same sum, so the mirrors reach the other half as the xor would), clamped to 32 bits, and lane q of every
+ * row keeps q's value: ONE store of 32 lanes writes the level block's 32 bands, a contiguous 128-byte row of K0SpecArgs.bands.  No LDS,
+ * no atomics.  With AGE every level block of the push is transformed and written -- the prefix of old epochs too -- and only the
+ * accumulation into the slots keeps skipping it.  BANDS = false is the code above.
  */
 #ifndef WM_K0_SPECTRUM_H
 #define WM_K0_SPECTRUM_H
@@ -64,6 +72,9 @@ struct K0SpecArgs {
     uint64_t k_first;            /* the stream's index of this push's first level block                        */
     uint64_t e_keep;             /* level blocks of epochs below this one are left out                         */
     uint64_t slot_stride;        /* slot 1 of sum / blocks lies this many uint64 behind slot 0, of peak twice as many uint32 */
+    /* the band form only (behind everything else again) */
+    uint32_t *bands;             /* [NC][band_stride] level block `blk` of the push: 32 uint32 at 32 blk, band j = bins [16 j, 16 j + 16) */
+    uint64_t band_stride;
 };
 
 /* What a push of n_blk > 0 level blocks, the first of them the stream's k_first, does to the two slots of an ageing survey.  The push
@@ -146,9 +157,31 @@ __device__ __forceinline__ void k0_spec_flush(const K0SpecArgs &a, uint32_t s, u
     if (lane == 0u) k0_add64(a.blocks + slot * a.slot_stride + s, (uint64_t)n);
 }
 
+/* v of the lane `step` away within its row of 16 lanes, for a value every lane of each aligned group of `step` lanes already shares (the
+ * sum so far): steps 1 and 2 are quad permutations, 4 and 8 the mirrors of half a row and of a row.  The block emulator exchanges by xor. */
+template <int STEP> __device__ __forceinline__ uint32_t k0_row_partner(uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int ctrl = STEP == 1 ? 0xB1 : STEP == 2 ? 0x4E : STEP == 4 ? 0x141 : 0x140;
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xF, 0xF, false);
+#else
+    return __shfl_xor(v, STEP);
+#endif
+}
+template <int STEP> __device__ __forceinline__ uint64_t k0_row_add(uint64_t v)
+{
+    return v + (((uint64_t)k0_row_partner<STEP>((uint32_t)(v >> 32)) << 32) | k0_row_partner<STEP>((uint32_t)v));
+}
+/* the sum of v over the lane's row of 16 lanes, in every lane of the row, clamped to 32 bits */
+__device__ __forceinline__ uint32_t k0_row_sum_clamped(uint64_t v)
+{
+    v = k0_row_add<1>(v); v = k0_row_add<2>(v); v = k0_row_add<4>(v); v = k0_row_add<8>(v);
+    return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v;
+}
+
 /* One block of WM_K0_SPEC_WAVES waves: blockIdx.x = four runs, blockIdx.y = capture.  lds: WM_K0_SPEC_WAVES x 2 x WM_K0_SPEC_PLANE dwords.
  * Lanes of a wave leave together or not at all. */
-template <int FMT, bool DC, bool AGE = false> __device__ __forceinline__ void k0_spectrum_block(const K0SpecArgs &a, int32_t *lds)
+template <int FMT, bool DC, bool AGE = false, bool BANDS = false> __device__ __forceinline__ void k0_spectrum_block(const K0SpecArgs &a, int32_t *lds)
 {
     constexpr uint32_t BPS = k0_bps(FMT), SPL = 16u / BPS, LOADS = (BPS << WM_K0_DC_LOG2) / (64u * 16u);
     static_assert(SPL * LOADS == 8u, "a lane loads 8 of a level block's 512 samples");
@@ -156,12 +189,17 @@ template <int FMT, bool DC, bool AGE = false> __device__ __forceinline__ void k0
     uint32_t first = (blockIdx.x * (blockDim.x >> 6) + wave) * a.run;
     if (first >= a.n_blk) return;
     const uint32_t last = a.n_blk - first < a.run ? a.n_blk : first + a.run;
+    uint32_t keep_from = first;                                  /* the first level block of the run that accumulates (BANDS: the ones in front of it are only written) */
     if constexpr (AGE) {                                         /* the level blocks of epochs below e_keep are a prefix of the push */
         const uint64_t k_keep = a.e_keep << a.age;
         if (k_keep > a.k_first) {
             const uint64_t skip = k_keep - a.k_first;
-            if (skip >= last) return;                            /* the same in every lane of the wave */
-            first = skip > first ? (uint32_t)skip : first;
+            if constexpr (BANDS) keep_from = skip >= last ? last : skip > first ? (uint32_t)skip : first;
+            else {
+                if (skip >= last) return;                        /* the same in every lane of the wave */
+                first = skip > first ? (uint32_t)skip : first;
+                keep_from = first;
+            }
         }
     }
     int32_t *re = lds + wave * 2u * WM_K0_SPEC_PLANE, *im = re + WM_K0_SPEC_PLANE;
@@ -197,12 +235,12 @@ template <int FMT, bool DC, bool AGE = false> __device__ __forceinline__ void k0
     uint32_t top[8];
 #pragma unroll
     for (uint32_t q = 0; q < 8u; q++) { acc[q] = 0u; top[q] = 0u; }
-    uint32_t since = first;                                      /* AGE: the first level block the registers hold */
+    uint32_t since = keep_from;                                  /* AGE: the first level block the registers hold */
 
     for (uint32_t blk = first; blk < last; blk++) {
         if constexpr (AGE) {                                     /* an epoch edge inside the run: what the registers hold goes to its slot */
             const uint64_t e = (a.k_first + blk) >> a.age;
-            if (blk != since && e != (a.k_first + since) >> a.age) {
+            if (blk > since && e != (a.k_first + since) >> a.age) {
                 k0_spec_flush(a, s, lane, ((a.k_first + since) >> a.age) & 1u, acc, top, blk - since);
 #pragma unroll
                 for (uint32_t q = 0; q < 8u; q++) { acc[q] = 0u; top[q] = 0u; }
@@ -246,22 +284,31 @@ template <int FMT, bool DC, bool AGE = false> __device__ __forceinline__ void k0
 #pragma unroll
         for (uint32_t q = 0; q < 8u; q++) { zr[q] = re[at_2 + 72u * q]; zi[q] = im[at_2 + 72u * q]; }
         k0_spec_pass<false>(zr, zi, tw2);
+        uint32_t band = 0u;                                      /* BANDS: lane q of a row keeps the row's band of q */
 #pragma unroll
         for (uint32_t q = 0; q < 8u; q++) {                      /* |z| <= 2^23.5: the sum of the squares is below 2^48, pw below 2^32 */
             const uint64_t pw = ((uint64_t)((int64_t)zr[q] * zr[q]) + (uint64_t)((int64_t)zi[q] * zi[q])) >> 16;
+            if constexpr (BANDS) {
+                const uint32_t bp = k0_row_sum_clamped(pw);
+                band = (lane & 15u) == q ? bp : band;
+                if (AGE && blk < keep_from) continue;            /* a level block of an epoch the view no longer holds: written, not accumulated */
+            }
             acc[q] += pw;
             top[q] = (uint32_t)pw > top[q] ? (uint32_t)pw : top[q];
         }
+        if constexpr (BANDS) {                                   /* bins 64 (q ^ 4) + lane: band 4 (q ^ 4) + (lane >> 4), q = lane & 15 */
+            if ((lane & 15u) < 8u) a.bands[(uint64_t)s * a.band_stride + 32u * (uint64_t)blk + 4u * ((lane & 15u) ^ 4u) + (lane >> 4)] = band;
+        }
     }
-    if constexpr (AGE) k0_spec_flush(a, s, lane, ((a.k_first + since) >> a.age) & 1u, acc, top, last - since);
+    if constexpr (AGE) { if (!BANDS || last > since) k0_spec_flush(a, s, lane, ((a.k_first + since) >> a.age) & 1u, acc, top, last - since); }
     else k0_spec_flush(a, s, lane, 0u, acc, top, last - first);
 }
 
 #if defined(__HIPCC__)
-template <int FMT, bool DC, bool AGE = false> __global__ void __launch_bounds__(64 * WM_K0_SPEC_WAVES) k0_spectrum(K0SpecArgs a)
+template <int FMT, bool DC, bool AGE = false, bool BANDS = false> __global__ void __launch_bounds__(64 * WM_K0_SPEC_WAVES) k0_spectrum(K0SpecArgs a)
 {
     __shared__ int32_t k0_spec_lds[WM_K0_SPEC_WAVES * 2u * WM_K0_SPEC_PLANE];
-    k0_spectrum_block<FMT, DC, AGE>(a, k0_spec_lds);
+    k0_spectrum_block<FMT, DC, AGE, BANDS>(a, k0_spec_lds);
 }
 #endif
 

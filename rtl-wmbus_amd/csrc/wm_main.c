@@ -71,6 +71,7 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t   keeps the second fixed); -v prints afc[<channel Hz>]: <Hz> Hz x<strength> over the floor.  A bare auto inside a list is not taken\n");
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
+    fprintf(stdout, "\t-n append ;signal;noise;x<strength> to every line (behind -l's fields, in front of a channel's): the power in the telegram's 200 kHz channel, the noise floor in the 20 ms in front of its preamble and their ratio, measured on the GPU from the raw input, in front of every gain and of the AGC; a field is empty where no level block could be counted\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
     fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
     fprintf(stdout, "\t-E seconds the survey of -w and -O auto forgets: it holds the last seconds ... 2 x seconds of the input (epochs of 2^A x 512 samples, the smallest A that\n");
@@ -235,13 +236,21 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
 
 /* -l: the line with ";offset_hz;dev_hz" in front of its newline, both fields empty for a level that could not be measured.  -O with a
  * list (chan_hz != NULL): ";<channel Hz>" of the line's channel behind that. */
-static void write_line(const char *text, size_t len, const wmbus_level *lev, const int *chan_hz)
+/* -n: ";signal;noise;x<ratio>" behind -l's fields and in front of the channel's: the power in the telegram's channel, the noise floor in
+ * front of it (each empty where no level block could be counted) and the strength the way the spectrum: lines print theirs (empty without
+ * either). */
+static void write_line(const char *text, size_t len, const wmbus_level *lev, const wmbus_power *pw, const int *chan_hz)
 {
-    if (!lev && !chan_hz) { fwrite(text, 1, len, stdout); return; }
+    if (!lev && !pw && !chan_hz) { fwrite(text, 1, len, stdout); return; }
     if (len && text[len - 1] == '\n') len--;
     fwrite(text, 1, len, stdout);
     if (lev && lev->n) fprintf(stdout, ";%d;%u", (int)lev->offset_hz, (unsigned)lev->dev_hz);
     else if (lev) fputs(";;", stdout);
+    if (pw) {
+        if (pw->n_signal) fprintf(stdout, ";%u", (unsigned)pw->signal); else fputc(';', stdout);
+        if (pw->n_noise) fprintf(stdout, ";%u", (unsigned)pw->noise); else fputc(';', stdout);
+        if (pw->n_signal && pw->n_noise) fprintf(stdout, ";x%.1f", (double)pw->ratio_q8 / 256.0); else fputc(';', stdout);
+    }
     if (chan_hz) fprintf(stdout, ";%d", *chan_hz);
     fputc('\n', stdout);
 }
@@ -256,8 +265,9 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     struct batch_job *j = user;
     (void)n;
     const wmbus_level *lev = NULL;
+    const wmbus_power *pw = NULL;
     pthread_mutex_lock(&out_lock);
-    if (j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+    if ((j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) || (j->cfg.line_power && wmbus_batch_line_power(j->b, first, &pw) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
         fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing; the lines are not printed\n", nl);
         j->lev_missing = 1;
         pthread_mutex_unlock(&out_lock);
@@ -267,7 +277,7 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
-        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, line_channel_hz(&j->cfg, ln + i));
+        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, line_channel_hz(&j->cfg, ln + i));
     }
     if (nl) fflush(stdout);
     pthread_mutex_unlock(&out_lock);
@@ -534,14 +544,15 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
             if (lv->cfg->input_channel_afc_hz[ch]) print_afc(lv->ctx, ch, NULL, &lv->afc_ch_changes[ch], &lv->cfg->input_channel_hz[ch]);
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
-    if (len && (lv->levels || lv->cfg->input_channels > 1u)) {
+    if (len && (lv->levels || lv->cfg->line_power || lv->cfg->input_channels > 1u)) {
         const wmbus_line *ln; const wmbus_level *lev = NULL;
+        const wmbus_power *pw = NULL;
         const size_t nl = wmbus_lines(lv->ctx, &ln);
-        if (lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+        if ((lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) || (lv->cfg->line_power && wmbus_line_power(lv->ctx, &pw) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
             fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
             return -1;
         }
-        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lev ? lev + i : NULL, line_channel_hz(lv->cfg, ln + i));
+        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lv->levels && lev ? lev + i : NULL, pw ? pw + i : NULL, line_channel_hz(lv->cfg, ln + i));
         fflush(stdout);
     } else if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
     return 0;
@@ -559,7 +570,7 @@ int main(int argc, char **argv)
     double age_seconds = 0.0;                                /* -E */
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:n")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -591,6 +602,7 @@ int main(int argc, char **argv)
         case 'L': max_latency_ms = (unsigned)strtoul(optarg, NULL, 10); break;
         case 'S': stats = 1; break;
         case 'l': cfg.line_levels = 1; break;
+        case 'n': cfg.line_power = 1; break;
         case 'w': cfg.input_spectrum = 1; break;
         case 'E': {
             char *end;
