@@ -97,6 +97,17 @@ typedef struct wmbus_cfg {
      * push path; as configuration two contexts of one process can differ, and nothing in a push calls getenv.) */
     unsigned rounds_on_host;    /* 1: no hand-off rounds are enqueued unattended: every hand-off failure is finished by the host-driven
                                    path of wmbus_collect (wmbus_timing.slow_path); the GPU test suites run once with it */
+    /* 0 (default): off.  1: CHANNEL ACTIVITY -- every collect comes with one record per burst of energy in each pipeline row's 200 kHz
+     * channel, whether a framer locked on it or not (wmbus_burst, wmbus_activity() below): the census that answers "how much of what was
+     * sent did I get?".  Made on the GPU from the timeline of CHANNEL POWER, in the integer arithmetic defined below under CHANNEL
+     * ACTIVITY.  The field switches line_power's stage on by itself, as line_power switches the survey on (wmbus_line_power,
+     * wmbus_read_channel_power work).  The lines do not change.  0 is in every respect the context without these two fields: the same
+     * kernels, buffers and bytes.  Anything above 1 is WMBUS_EINVAL.
+     * channel_activity_ratio_q8 = T: a level block is active where its power lies above T / 256 times the floor.  0: 1024 (x 4).  Any
+     * other value outside 257 ... 65535, and a non-zero T without channel_activity, is WMBUS_EINVAL.  (The newest fields: in front of
+     * the two RSSI knobs, which stay directly in front of line_power; nothing behind them moves.) */
+    unsigned channel_activity;
+    unsigned channel_activity_ratio_q8;
     unsigned rssi_full;         /* 1: the RSSI of every sample in the demodulation kernel even without debug views (A/B of RSSI on demand) */
     unsigned rssi_dense_pm;     /* RSSI on demand pauses for 16 pushes when more than this many per mille of a push's tiles were listed
                                    (0: 200; configs[2] lists 310 and is faster on the full pass) */
@@ -105,8 +116,8 @@ typedef struct wmbus_cfg {
      * front of every gain and independent of input_agc, in the integer arithmetic defined below under CHANNEL POWER.  The field switches
      * the survey on by itself, as input_afc does (wmbus_read_spectrum works), and the level records of line_levels, which carry every
      * line's access-code sample (wmbus_line_levels works).  The lines themselves do not change.  0 is in every respect the context
-     * without this field: the same kernels, buffers and bytes.  Anything above 1 is WMBUS_EINVAL.  (The newest field: directly in front
-     * of bursts_to_host, nothing behind it moves.) */
+     * without this field: the same kernels, buffers and bytes.  Anything above 1 is WMBUS_EINVAL.  (Directly in front of bursts_to_host,
+     * nothing behind it moves.) */
     unsigned line_power;
     unsigned bursts_to_host;    /* 1: every burst travels to the host packet decoders as chips (round 1's path) instead of being decoded
                                    on the GPU where it lies inside the push */
@@ -604,6 +615,47 @@ long wmbus_read_waterfall(wmbus_ctx *ctx, unsigned capture, uint32_t *rows, uint
 long wmbus_read_channel_power(wmbus_ctx *ctx, int chain, unsigned stream_v, uint32_t *p, uint64_t *first_block, size_t cap);
 int  wmbus_line_power_rule(const uint32_t *p, uint64_t first_block, size_t n, uint64_t ka, uint64_t ke, unsigned in_hz, wmbus_power *out);
 int  wmbus_line_power_block(unsigned decimation, unsigned input_rate_hz, uint64_t sample, uint64_t *block);
+/* CHANNEL ACTIVITY (cfg.channel_activity = 1; tests/activity_ref.py restates it in Python integers on top of tests/power_ref.py).  Integers
+ * only; every division floors.  For every pipeline row r = chain x S + v on its own, with P[K] = CHANNEL POWER's P[r][K] and K counted
+ * from the stream's first sample, T = cfg.channel_activity_ratio_q8 (0: 1024):
+ *   epoch        e(K) = K >> 6, 64 level blocks.  q[e] = the element at index 16 of the epoch's 64 values of P sorted ascending (the lower
+ *                quartile: telegrams inside the epoch do not lift it).  It exists once the epoch is complete
+ *   floor        H = min(63, ceil(0.16 Fin / 32768) + 1) (9 at 1.6 MS/s);  floor[e] = min of q[e'] over max(0, e - H) <= e' <= e.  The
+ *                window is longer than the longest telegram: an epoch that lies wholly inside an S1 telegram does not lift the floor
+ *   active       act[K] = (P[K] x 256 > T x floor[e(K)]), products in 64 bits
+ *   burst        a maximal run of active level blocks of length >= 2, evaluated when the epoch that holds the first inactive block behind
+ *                it is complete:  first_block;  blocks;  mean = floor(sum of P / blocks), the sum in 64 bits;  floor = the floor of the
+ *                epoch the run began in;  stream (the capture), channel and chain of the row
+ *   not evaluated  a run of one block is dropped.  The stream's last incomplete epoch is never evaluated (as the reference drops a partial
+ *                block): a burst whose closing block lies in it is not reported, and wmbus_close reports nothing more
+ *   carrier      a carrier that never ends closes by itself: once all H + 1 epochs of the floor hold it, the floor is the carrier's own
+ *                level and no block lies T / 256 above it.  One long record, then silence until the carrier goes: the rule's behaviour
+ * The records of a stream, concatenated over its collects, are a function of the stream alone and do not depend on how the input is cut
+ * into pushes -- the row's state (the incomplete epoch's P, the last H quartiles, the epoch count, the open run) stays on the GPU and moves
+ * on once per push.  The one exception is AFC's, as in CHANNEL POWER: P itself follows the lock push by push.
+ * What the rule rests on (measured with the restatement): synthetic captures of 2^19 samples, 40 frames/s, sigma 3, amplitudes 60, 8 and
+ * 5: every frame found, both ends within one level block, nothing else reported.  cu8 noise of sigma 1, 3 and 30, 2048 level blocks each:
+ * no record at x 4 or x 2, the largest P at most 1.88 x its lower quartile.  The bundled 1.6 MS/s capture: two records, (first_block,
+ * blocks) = (748, 21) and (1424, 46), its two telegrams; at x 2 the same capture gives 76 records, real-world noise excursions, hence the
+ * default of x 4.  The bundled 2.4 MS/s capture with cfg.simultaneous: one record (143, 33) on the T1/C1 row, none on the S1 row.  The
+ * default rests on these two captures and on synthetic noise only; a site with impulsive interference may want a higher T.
+ *
+ * wmbus_activity: the records the last collect delivered, rows ascending (chain, then capture, then channel), first_block ascending within
+ * a row.  A context opened without cfg.channel_activity, or a collect that closed no burst: 0, and *records = NULL.
+ * wmbus_activity_progress (beyond the rule: what a caller needs to know when a burst can no longer get a line): the level blocks of the
+ * stream the collects so far have taken in; every burst that closed in an epoch complete by then has been delivered.  0 without the field.
+ * wmbus_activity_rule: the rule above over one row's whole timeline p[0 .. n) from level block 0; host only, no device needed.  Writes at
+ * most cap records (stream, channel and chain 0) and returns the number found.  WMBUS_EINVAL for in_hz < 800000, a ratio_q8 that
+ * cfg.channel_activity_ratio_q8 would refuse, or NULL pointers (p may be NULL for n = 0, out for cap = 0).
+ * wmbus_activity_match: host only.  A line matches a burst of its row when its access-code level block ka -- wmbus_line_power_block of
+ * wmbus_level.sync_sample -- satisfies first_block - 1 <= ka < first_block + blocks; the - 1 covers rates at which the preamble is shorter
+ * than a level block.  Bursts of a row are separated by at least one inactive block, so these intervals are disjoint.  Returns the index
+ * of the matching record among records[0 .. n) for the row (stream, channel, chain), or -1. */
+typedef struct wmbus_burst { uint64_t first_block; uint32_t blocks, mean, floor; uint32_t stream; uint8_t channel, chain; uint8_t pad[2]; } wmbus_burst;
+size_t wmbus_activity(const wmbus_ctx *ctx, const wmbus_burst **records);
+uint64_t wmbus_activity_progress(const wmbus_ctx *ctx);
+long wmbus_activity_rule(const uint32_t *p, size_t n, unsigned in_hz, unsigned ratio_q8, wmbus_burst *out, size_t cap);
+long wmbus_activity_match(const wmbus_burst *records, size_t n, unsigned stream, unsigned channel, int chain, uint64_t ka);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):
@@ -721,6 +773,9 @@ int  wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats
 size_t wmbus_batch_line_levels(const wmbus_batch *b, unsigned first_stream, const wmbus_level **levels);
 /* The same for a batch opened with cfg.line_power: the power records of the lines the `lines` callback has just been handed. */
 size_t wmbus_batch_line_power(const wmbus_batch *b, unsigned first_stream, const wmbus_power **power);
+/* The same for a batch opened with cfg.channel_activity: the bursts of the collect whose lines the `lines` callback has just been handed;
+ * wmbus_burst.stream counts from first_stream. */
+size_t wmbus_batch_activity(const wmbus_batch *b, unsigned first_stream, const wmbus_burst **records);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,8 @@ class Cfg(ctypes.Structure):
                 ("keep_taps", ctypes.c_int), ("prefilter", ctypes.c_int), ("atan_mode", ctypes.c_int), ("spill_words", ctypes.c_uint), ("dedup_twins", ctypes.c_int), ("only_crc_ok", ctypes.c_int),
                 ("input_windows", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
-                ("rounds_on_host", ctypes.c_uint), ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("line_power", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
+                ("rounds_on_host", ctypes.c_uint), ("channel_activity", ctypes.c_uint), ("channel_activity_ratio_q8", ctypes.c_uint),
+                ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("line_power", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
                 ("input_spectrum_age", ctypes.c_uint), ("input_channel_afc_hz", ctypes.c_uint * MAX_CHANNELS),
                 ("burst_caps", ctypes.c_uint * 4), ("input_afc", ctypes.c_uint), ("input_afc_range_hz", ctypes.c_uint), ("k1_small_tile", ctypes.c_uint),
                 ("input_spectrum", ctypes.c_uint), ("input_channels", ctypes.c_uint), ("input_channel_hz", ctypes.c_int * MAX_CHANNELS),
@@ -83,6 +84,16 @@ class Power(ctypes.Structure):
     def as_dict(self):
         return dict(first_block=int(self.first_block), signal=int(self.signal), noise=int(self.noise), ratio_q8=int(self.ratio_q8),
                     n_signal=int(self.n_signal), n_noise=int(self.n_noise))
+
+
+class Burst(ctypes.Structure):
+    """wmbus_burst: one burst of energy in a pipeline row's channel (cfg.channel_activity), decoded or not."""
+    _fields_ = [("first_block", ctypes.c_uint64), ("blocks", ctypes.c_uint32), ("mean", ctypes.c_uint32), ("floor", ctypes.c_uint32),
+                ("stream", ctypes.c_uint32), ("channel", ctypes.c_uint8), ("chain", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+    def as_dict(self):
+        return dict(first_block=int(self.first_block), blocks=int(self.blocks), mean=int(self.mean), floor=int(self.floor),
+                    stream=int(self.stream), channel=int(self.channel), chain=int(self.chain))
 
 
 class ChannelHit(ctypes.Structure):
@@ -150,7 +161,8 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
            "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
            "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc",
-           "wmbus_line_power", "wmbus_batch_line_power", "wmbus_read_waterfall", "wmbus_read_channel_power", "wmbus_line_power_rule", "wmbus_line_power_block"]
+           "wmbus_line_power", "wmbus_batch_line_power", "wmbus_read_waterfall", "wmbus_read_channel_power", "wmbus_line_power_rule", "wmbus_line_power_block",
+           "wmbus_activity", "wmbus_activity_progress", "wmbus_batch_activity", "wmbus_activity_rule", "wmbus_activity_match"]
 
 _lib = None
 
@@ -194,6 +206,11 @@ def lib():
         L.wmbus_read_channel_power.argtypes = [vp, ctypes.c_int, u, vp, ctypes.POINTER(ctypes.c_uint64), sz]; L.wmbus_read_channel_power.restype = ctypes.c_long
         L.wmbus_line_power_rule.argtypes = [vp, ctypes.c_uint64, sz, ctypes.c_uint64, ctypes.c_uint64, u, ctypes.POINTER(Power)]
         L.wmbus_line_power_block.argtypes = [u, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.wmbus_activity.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Burst))]; L.wmbus_activity.restype = sz
+        L.wmbus_activity_progress.argtypes = [vp]; L.wmbus_activity_progress.restype = ctypes.c_uint64
+        L.wmbus_batch_activity.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Burst))]; L.wmbus_batch_activity.restype = sz
+        L.wmbus_activity_rule.argtypes = [vp, sz, u, u, ctypes.POINTER(Burst), sz]; L.wmbus_activity_rule.restype = ctypes.c_long
+        L.wmbus_activity_match.argtypes = [ctypes.POINTER(Burst), sz, u, u, ctypes.c_int, ctypes.c_uint64]; L.wmbus_activity_match.restype = ctypes.c_long
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -275,6 +292,27 @@ def line_power_block(sample, decimation=2, input_rate_hz=0):
     return int(out.value)
 
 
+def activity_rule(p, in_hz, ratio_q8=0):
+    """wmbus_activity_rule (host only): the bursts of one row's whole timeline p = P of level blocks 0 ... (CHANNEL ACTIVITY); a list of
+    dicts like Receiver.activity()'s, stream, channel and chain 0."""
+    p = np.ascontiguousarray(p, np.uint32)
+    cap = p.size // 3 + 2
+    out = (Burst * cap)()
+    n = lib().wmbus_activity_rule(p.ctypes.data if p.size else None, p.size, int(in_hz), int(ratio_q8), out, cap)
+    if n < 0:
+        raise WmbusError(f"wmbus_activity_rule failed: {n}")
+    return [out[i].as_dict() for i in range(n)]
+
+
+def activity_match(records, stream, channel, chain, ka):
+    """wmbus_activity_match (host only): the index in `records` (dicts as Receiver.activity() returns them) of the burst of row (stream,
+    channel, chain) that a line with access-code level block ka belongs to, or -1."""
+    arr = (Burst * max(1, len(records)))()
+    for i, r in enumerate(records):
+        arr[i] = Burst(r["first_block"], r["blocks"], r["mean"], r["floor"], r["stream"], r["channel"], r["chain"])
+    return int(lib().wmbus_activity_match(arr, len(records), int(stream), int(channel), int(chain), int(ka)))
+
+
 def pinned_array(nbytes):
     """uint8 numpy array over page-locked host memory (kept alive by the array's base object)."""
     p = lib().wmbus_alloc_pinned(nbytes)
@@ -317,7 +355,8 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               prefilter=0, atan_mode=0, keep_taps=True, spill_words=0, input_windows=1, dedup_twins=False, only_crc_ok=False, tolerance_mode=0,
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
-              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None, line_power=0):
+              input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None, line_power=0,
+              channel_activity=0, channel_activity_ratio_q8=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
@@ -351,6 +390,8 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     # library's limit are dropped here; one beyond the channel list is passed on, so that wmbus_open refuses it with its message
     for i, r in enumerate(list(input_channel_afc_hz if input_channel_afc_hz is not None else ())[:MAX_CHANNELS]):
         c.input_channel_afc_hz[i] = int(r)
+    c.channel_activity = int(channel_activity)                      # 1: a record per burst of energy in every row's channel, decoded or not: Receiver.activity()
+    c.channel_activity_ratio_q8 = int(channel_activity_ratio_q8)    # its threshold over the floor in Q8 (0: 1024)
     c.line_power = int(line_power)           # 1: a power record (signal, noise floor, ratio) per line from the raw input: Receiver.line_power(), read_waterfall(), read_channel_power()
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
     # several channels of one wideband capture: signed Hz from the capture's centre to each channel (as input_shift_hz, which stays 0);
@@ -388,6 +429,7 @@ class Batch:
             L.wmbus_batch_close(self._h)
             self._h = None
             raise WmbusError(f"wmbus_batch_open failed ({rc}): {msg}")
+        self.bursts = {}                                    # channel_activity: first stream of a context -> every burst its pushes delivered
         self.contexts = []                                  # (Receiver view, first stream, streams)
         for i in range(L.wmbus_batch_contexts(self._h)):
             f, n = ctypes.c_uint(), ctypes.c_uint()
@@ -437,6 +479,10 @@ class Batch:
 
         def c_lines(user, first, n, lines, n_lines, text, timing):
             recs = None
+            if self.cfg.channel_activity:              # the bursts of the collect these lines came with: Batch.bursts[first stream], stream counted from it
+                p = ctypes.POINTER(Burst)()
+                nb = lib().wmbus_batch_activity(self._h, first, ctypes.byref(p))
+                self.bursts.setdefault(first, []).extend(p[k].as_dict() for k in range(nb))
             if want_lines:
                 recs = []
                 for k in range(n_lines):
@@ -554,6 +600,17 @@ class Receiver:
         p = ctypes.POINTER(Power)()
         n = lib().wmbus_line_power(self._h, ctypes.byref(p))
         return [p[i].as_dict() for i in range(n)]
+
+    def activity(self):
+        """The bursts the last collect delivered (a context opened with channel_activity=1; else []): dicts of first_block, blocks, mean,
+        floor, stream, channel, chain; rows ascending, first_block ascending."""
+        p = ctypes.POINTER(Burst)()
+        n = lib().wmbus_activity(self._h, ctypes.byref(p))
+        return [p[i].as_dict() for i in range(n)]
+
+    def activity_progress(self):
+        """The level blocks of the stream the collects so far have taken in (channel_activity=1; else 0)."""
+        return int(lib().wmbus_activity_progress(self._h))
 
     def read_waterfall(self, capture, max_rows=1 << 20):
         """(rows uint32 [n, 32], first_block): the band rows of the last push of one capture (a context with line_power): band j of a row

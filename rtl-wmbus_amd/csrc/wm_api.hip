@@ -176,6 +176,20 @@ struct wmbus_ctx {
         uint64_t got_first = 0; uint32_t got_blk = 0;  /* the last collected push */
     } pw;
     std::vector<wmbus_power> powers;                   /* parallel to `lines` */
+    /* cfg.channel_activity: the census of bursts (wm_k0_activity.h) -- k0_activity, behind k0_channel_power, walks every row's complete
+     * epochs and leaves this push's records in an arena in ticket order; the ticket count travels with the push, wait_gpu fetches that many
+     * records, sorts them by (row, first_block) and keeps them for wmbus_activity.  The tickets are never reset: `taken` is the count in
+     * front of the push in flight.  All nullptr / empty without the option. */
+    struct {
+        bool on = false;
+        uint32_t T = 0, H = 0, cap = 0, taken = 0;
+        bool launched = false;                         /* the push in flight ran the kernel */
+        K0ActState *d_state = nullptr;                 /* [2 S] */
+        K0ActRecord *d_arena = nullptr;                /* [cap] */
+        uint32_t *d_count = nullptr, *h_count = nullptr;
+        std::vector<K0ActRecord> raw;
+        std::vector<wmbus_burst> bursts;               /* what the last collect delivered */
+    } act;
     /* device buffers */
     uint8_t *d_in = nullptr;                           /* [n_win][S][in_stride] */
     uint8_t *d_hist = nullptr;                         /* [S][4096] the input history of the next push (see k_copy_hist) */
@@ -602,8 +616,15 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         return fail(c, WMBUS_EINVAL, "input_agc takes the place of input_gain_q8: leave that 0 or 256 (got %u)", cfg->input_gain_q8);
     if (cfg->line_levels > 1u) return fail(c, WMBUS_EINVAL, "line_levels must be 0 or 1, got %u", cfg->line_levels);
     if (cfg->line_power > 1u) return fail(c, WMBUS_EINVAL, "line_power must be 0 or 1, got %u", cfg->line_power);
-    c->lev_on = cfg->line_levels != 0u || cfg->line_power != 0u;      /* a power record needs its line's access-code sample: the level record carries it */
-    c->pw.on = cfg->line_power != 0u;
+    if (cfg->channel_activity > 1u) return fail(c, WMBUS_EINVAL, "channel_activity must be 0 or 1, got %u", cfg->channel_activity);
+    if (cfg->channel_activity_ratio_q8 && !cfg->channel_activity)
+        return fail(c, WMBUS_EINVAL, "channel_activity_ratio_q8 = %u without channel_activity", cfg->channel_activity_ratio_q8);
+    if (cfg->channel_activity_ratio_q8 && (cfg->channel_activity_ratio_q8 < 257u || cfg->channel_activity_ratio_q8 > 65535u))
+        return fail(c, WMBUS_EINVAL, "channel_activity_ratio_q8 must be 0 or 257 ... 65535, got %u", cfg->channel_activity_ratio_q8);
+    c->act.on = cfg->channel_activity != 0u;
+    c->act.T = cfg->channel_activity_ratio_q8 ? cfg->channel_activity_ratio_q8 : WM_K0_ACT_RATIO_Q8;
+    c->pw.on = cfg->line_power != 0u || c->act.on;                    /* the census reads the timeline of CHANNEL POWER */
+    c->lev_on = cfg->line_levels != 0u || c->pw.on;                   /* a power record needs its line's access-code sample: the level record carries it */
     if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
     c->spec.on = cfg->input_spectrum != 0u || c->pw.on;          /* the band rows are the survey's */
     auto &k = c->k0;
@@ -706,6 +727,7 @@ static int open_geometry(wmbus_ctx *c)
         w.blk_cap = (uint32_t)(cfg->max_push_bytes / c->k0.bps) >> WM_K0_DC_LOG2;
         /* Nn + G + ceil(0.15 Fin / 512) level blocks in front of the current push: the noise window of the longest telegram that ends in it */
         w.hist = (w.fin + 25599u) / 25600u + (w.fin + 51199u) / 51200u + (uint32_t)((3ull * w.fin + 10239u) / 10240u);
+        if (c->act.on) { c->act.H = k0_act_epochs(w.fin); c->act.cap = 2u * c->S * k0_act_row_cap(w.blk_cap); }
     }
     /* Time segments: 32768 / 8192 decimated samples for batches of whole waves (r02 / r03 A/Bs: clock 65536 -8 %, 16384 -25 %;
      * run-length 16384 -9 %, 4096 -20 %).  A batch with fewer captures than a wave has lanes is bound by how long ONE lane
@@ -846,6 +868,12 @@ static int open_allocate(wmbus_ctx *c)
         A(m.halloc(&c->pw.h_P, (size_t)rows * c->pw.blk_cap));
         c->pw.ring.assign((size_t)rows, std::vector<uint32_t>());
     }
+    if (c->act.on) {
+        A(m.dalloc(&c->act.d_state, (size_t)rows));
+        A(m.dalloc(&c->act.d_arena, (size_t)c->act.cap));
+        A(m.dalloc(&c->act.d_count, (size_t)1));
+        A(m.halloc(&c->act.h_count, (size_t)1));
+    }
     if (c->afc.on) {
         c->afc.n = c->afc.chan ? c->S : c->NC;
         A(m.dalloc(&c->afc.d_state, (size_t)2 * c->afc.n));
@@ -937,6 +965,14 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         A(hipMemcpyAsync(c->afc.d_state, afc_init.data(), afc_init.size() * sizeof(K0AfcState), hipMemcpyHostToDevice, c->stream));
         A(hipMemsetAsync(c->afc.d_push, 0, (size_t)c->afc.n * sizeof(K0AfcPush), c->stream));
     }
+    std::vector<K0ActState> act_init;
+    if (c->act.on) {                                         /* no epoch yet: an empty ring, no open run, no ticket taken */
+        act_init.assign((size_t)rows, K0ActState{});
+        for (K0ActState &s : act_init) std::fill(s.ring, s.ring + 64, WM_K0_ACT_NONE);
+        A(hipMemcpyAsync(c->act.d_state, act_init.data(), act_init.size() * sizeof(K0ActState), hipMemcpyHostToDevice, c->stream));
+        A(hipMemsetAsync(c->act.d_count, 0, sizeof(uint32_t), c->stream));
+        *c->act.h_count = 0u;
+    }
     if (c->k0.shift || c->k0.chan || c->spec.on) {           /* {c, s} per entry: the dword the kernels read */
         shift_tab.resize(2u * WM_K0_SHIFT_ENTRIES);
         k0_shift_design(800000u, 0, nullptr, shift_tab.data(), shift_tab.size());
@@ -965,7 +1001,7 @@ static int open_init(wmbus_ctx *c, const std::vector<int16_t> &k0_taps)
         lut[32 * WM_MAX_DECIM + n] = -sinf(phi);
     }
     A(hipMemcpyAsync(c->d_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    A(hipStreamSynchronize(c->stream));                      /* k0_taps, shift_tab, afc_init, init and lut leave with this function */
+    A(hipStreamSynchronize(c->stream));                      /* k0_taps, shift_tab, afc_init, act_init, init and lut leave with this function */
     if (e != hipSuccess) return fail(c, WMBUS_EDEVICE, "initialisation failed: %s", hipGetErrorString(e));
 
     c->decs.resize((size_t)c->S * 4);                        /* [stream][chain][algo] */
@@ -1311,6 +1347,17 @@ static int power_launch(wmbus_ctx *c)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpy2DAsync(w.h_P, (size_t)w.blk_cap * sizeof(uint32_t), w.d_P, (size_t)w.blk_cap * sizeof(uint32_t), (size_t)n_blk * sizeof(uint32_t), (size_t)2 * c->S,
                                hipMemcpyDeviceToHost, c->stream));
+    if (c->act.on) {
+        /* cfg.channel_activity: the rows' state moves on over this push's P, here and nowhere else -- once per push, as pw.K does */
+        K0ActArgs ca{};
+        ca.P = w.d_P; ca.p_stride = w.blk_cap; ca.n_blk = n_blk; ca.rows = 2u * c->S;
+        ca.T = c->act.T; ca.H = c->act.H;
+        ca.st = c->act.d_state; ca.arena = c->act.d_arena; ca.count = c->act.d_count; ca.base = c->act.taken; ca.cap = c->act.cap;
+        hipLaunchKernelGGL(k0_activity, dim3(2u * c->S), dim3(64u), 0, c->stream, ca);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->act.h_count, c->act.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        c->act.launched = true;
+    }
     return WMBUS_OK;
 }
 
@@ -1661,6 +1708,32 @@ static int finish_slowly(wmbus_ctx *c, bool ema_left, bool left[2], bool rs_left
     return 0;
 }
 
+/* cfg.channel_activity: the records the push has closed, from the arena's ticket order into rows ascending, first_block ascending.  Only a
+ * push that closed any pays the second copy. */
+static int activity_collect(wmbus_ctx *c)
+{
+    auto &t = c->act;
+    t.bursts.clear();
+    if (!t.launched) return WMBUS_OK;
+    t.launched = false;
+    const uint32_t n = *t.h_count - t.taken;
+    t.taken = *t.h_count;
+    if (n > t.cap) { c->poisoned = true; return fail(c, WMBUS_EDEVICE, "internal error: %u activity records, the arena holds %u", n, t.cap); }
+    if (!n) return WMBUS_OK;
+    t.raw.resize(n);
+    HIPCHK(c, hipMemcpyAsync(t.raw.data(), t.d_arena, (size_t)n * sizeof(K0ActRecord), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::sort(t.raw.begin(), t.raw.end(), [](const K0ActRecord &x, const K0ActRecord &y) { return x.row != y.row ? x.row < y.row : x.first_block < y.first_block; });
+    for (const K0ActRecord &r : t.raw) {
+        const uint32_t v = r.row % c->S;
+        wmbus_burst b{};
+        b.first_block = r.first_block; b.blocks = r.blocks; b.mean = r.mean; b.floor = r.floor;
+        b.stream = v / c->CH; b.channel = (uint8_t)(v % c->CH); b.chain = (uint8_t)(r.row / c->S);
+        t.bursts.push_back(b);
+    }
+    return WMBUS_OK;
+}
+
 /* First half of wmbus_collect: wait for the push, finish leftover hand-off rounds, read the counters.  Afterwards the
  * candidate telegrams sit in pinned host memory and nothing of this push is left on the GPU. */
 static int wait_gpu(wmbus_ctx *c)
@@ -1672,6 +1745,7 @@ static int wait_gpu(wmbus_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->in_flight = false;
     c->tim = wmbus_timing{};
+    if (c->act.on) { const int rc = activity_collect(c); if (rc) return rc; }
     if (c->pw.on && c->pw.last_blk) {                        /* this push's P behind the history: the last pw.hist level blocks in front of it stay */
         auto &w = c->pw;
         const size_t drop = w.ring[0].size() > w.hist ? w.ring[0].size() - w.hist : 0u;      /* ring_first + size == last_first: every push's level blocks pass through here once */
@@ -1792,6 +1866,40 @@ size_t wmbus_line_power(const wmbus_ctx *c, const wmbus_power **power)
 {
     if (power) *power = c && c->pw.on ? c->powers.data() : nullptr;
     return c && c->pw.on ? c->powers.size() : 0;
+}
+
+size_t wmbus_activity(const wmbus_ctx *c, const wmbus_burst **records)
+{
+    const bool on = c && c->act.on && !c->act.bursts.empty();
+    if (records) *records = on ? c->act.bursts.data() : nullptr;
+    return on ? c->act.bursts.size() : 0;
+}
+
+uint64_t wmbus_activity_progress(const wmbus_ctx *c)
+{
+    return c && c->act.on ? c->pw.got_first + c->pw.got_blk : 0u;
+}
+
+long wmbus_activity_rule(const uint32_t *p, size_t n, unsigned in_hz, unsigned ratio_q8, wmbus_burst *out, size_t cap)
+{
+    if ((!p && n) || (!out && cap) || in_hz < 800000u || (ratio_q8 && (ratio_q8 < 257u || ratio_q8 > 65535u))) return WMBUS_EINVAL;
+    std::vector<K0ActBurst> found;
+    k0_activity_rule(p, n, in_hz, ratio_q8 ? ratio_q8 : WM_K0_ACT_RATIO_Q8, found);
+    for (size_t i = 0; i < found.size() && i < cap; i++) {
+        wmbus_burst b{};
+        b.first_block = found[i].first_block; b.blocks = found[i].blocks; b.mean = found[i].mean; b.floor = found[i].floor;
+        out[i] = b;
+    }
+    return (long)found.size();
+}
+
+long wmbus_activity_match(const wmbus_burst *records, size_t n, unsigned stream, unsigned channel, int chain, uint64_t ka)
+{
+    if (!records && n) return WMBUS_EINVAL;
+    for (size_t i = 0; i < n; i++)
+        if (records[i].stream == stream && records[i].channel == channel && records[i].chain == chain && k0_activity_matches(records[i].first_block, records[i].blocks, ka))
+            return (long)i;
+    return -1;
 }
 
 long wmbus_read_waterfall(wmbus_ctx *c, unsigned capture, uint32_t *rows, uint64_t *first_block, size_t cap_rows)

@@ -57,6 +57,7 @@
 #include "wm_k0_spectrum.h"
 #include "wm_k0_afc.h"
 #include "wm_k0_power.h"
+#include "wm_k0_activity.h"
 #include "wm_k1_demod.h"
 #include "wm_k2_common.h"
 #include "wm_k2_clock.h"

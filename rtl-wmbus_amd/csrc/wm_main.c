@@ -72,6 +72,8 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-C R remove the I/Q DC offset of the input, time constant 2^R x 512 samples, R = 1 ... 12; 6 suits zero-IF receivers (HackRF, E4000, Pluto, Lime)\n");
     fprintf(stdout, "\t-l append ;offset_hz;dev_hz to every line: frequency offset (what -O should add) and mean absolute deviation of the telegram's preamble, measured on the GPU; empty where the preamble lies before the stream\n");
     fprintf(stdout, "\t-n append ;signal;noise;x<strength> to every line (behind -l's fields, in front of a channel's): the power in the telegram's 200 kHz channel, the noise floor in the 20 ms in front of its preamble and their ratio, measured on the GPU from the raw input, in front of every gain and of the AGC; a field is empty where no level block could be counted\n");
+    fprintf(stdout, "\t-m census of transmissions: stderr gets one line per burst of energy in the channel, decoded or not (activity: block <first level block of 512 samples> <duration> ms x<strength over the floor> decoded|crc-failed|missed,\n");
+    fprintf(stdout, "\t   with the file name in batch mode and the channel Hz of a list), and at the end of the input a summary per capture and channel (activity: N transmissions, N decoded, N CRC-clean); measured on the GPU from the raw input; stdout does not change\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
     fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
     fprintf(stdout, "\t-E seconds the survey of -w and -O auto forgets: it holds the last seconds ... 2 x seconds of the input (epochs of 2^A x 512 samples, the smallest A that\n");
@@ -118,6 +120,17 @@ static int open_tcp(const char *hostport)
  * One wmbus_batch per device (include/wmbus_hip.h): the library splits the device's files over several receiver
  * contexts, drives each on its own thread and overlaps them; this file only supplies the bytes (fread into the page-locked
  * slab the library hands out) and prints the lines. */
+/* -m: the census of transmissions (below, in front of batch_lines) */
+struct census_line { uint64_t ka; uint32_t stream; uint8_t channel, chain, crc_ok; };
+struct census {
+    const wmbus_cfg *cfg; char **names;                      /* names: the files of a batch (NULL: a live stream) */
+    unsigned fin, n_streams, ch;                             /* channels per capture (1 without a list) */
+    uint64_t margin, keep;                                   /* level blocks: 0.15 s; how long a line may wait for its burst */
+    wmbus_burst *pend; size_t n_pend, cap_pend;
+    struct census_line *lines; size_t n_lines, cap_lines;
+    unsigned long long (*sum)[3];                            /* [(stream x ch + channel) x 2 + chain]: transmissions, decoded, CRC-clean */
+};
+
 struct batch_job {
     wmbus_cfg cfg; int n; char **names; FILE **f; int *live; int rc;
     unsigned fill_threads;                               /* readers per fill call (a context's files are read side by side) */
@@ -125,6 +138,7 @@ struct batch_job {
     int stats, fast_exit, lev_missing;                   /* lev_missing: -l and a push came without its levels (the run fails) */
     wmbus_batch *b;                                      /* -l: the sink asks it for the levels of the lines it is handed */
     wmbus_batch_stats st;
+    struct census census;                                /* -m */
     unsigned long long bytes_out, clipped;               /* wmbus_timing.input_bytes_out / input_clipped over the run */
 };
 
@@ -260,10 +274,110 @@ static const int *line_channel_hz(const wmbus_cfg *cfg, const wmbus_line *ln)
     return cfg->input_channels > 1u ? &cfg->input_channel_hz[ln->channel] : NULL;
 }
 
+
+/* ---- -m: the census of transmissions (cfg.channel_activity) -------------------------------------------------------------------------
+ * Every collect delivers the bursts of energy that closed in it (wmbus_activity) and the lines decoded in it; a line belongs to the burst
+ * of its channel that holds its access-code level block (wmbus_activity_match).  A line may come before its burst or after it, so both
+ * wait here: a burst is resolved -- decoded, crc-failed or missed -- once the stream has moved 0.15 s, the longest telegram, past its
+ * end (wmbus_activity_progress), or at the end of the input.  stderr gets a line per resolved burst and a summary per capture and
+ * channel at exit; stdout does not change.  Without -s both chains listen on the same channel and see the same bursts: the T1/C1 row's
+ * are counted, lines of either chain match them.  Callers hold out_lock or are single-threaded. */
+static int census_open(struct census *cs, const wmbus_cfg *cfg, unsigned n_streams, char **names)
+{
+    memset(cs, 0, sizeof *cs);
+    cs->cfg = cfg; cs->names = names; cs->n_streams = n_streams;
+    cs->fin = cfg->input_rate_hz ? cfg->input_rate_hz : cfg->decimation * 800000u;
+    cs->ch = cfg->input_channels > 1u ? cfg->input_channels : 1u;
+    cs->margin = (3ull * cs->fin + 10239u) / 10240u;         /* ceil(0.15 Fin / 512) */
+    cs->keep = cs->margin + 66u * 64u;                       /* the longest run the floor allows (H + 2 <= 65 epochs), and its epoch's end */
+    cs->sum = calloc((size_t)n_streams * cs->ch * 2u, sizeof *cs->sum);
+    return cs->sum ? 0 : -1;
+}
+
+static void census_print_row(const struct census *cs, unsigned stream, unsigned channel, unsigned chain)
+{
+    if (cs->names) fprintf(stderr, "%s: ", cs->names[stream]);
+    fputs("activity", stderr);
+    if (cs->ch > 1u && cs->cfg->simultaneous) fprintf(stderr, "[%d %s]", cs->cfg->input_channel_hz[channel], chain ? "S1" : "T1/C1");
+    else if (cs->ch > 1u) fprintf(stderr, "[%d]", cs->cfg->input_channel_hz[channel]);
+    else if (cs->cfg->simultaneous) fprintf(stderr, "[%s]", chain ? "S1" : "T1/C1");
+    fputs(": ", stderr);
+}
+
+/* first: the context's first stream (a batch); progress: the context's level blocks so far; all: the input has ended, resolve everything
+ * of streams [first, first + n) */
+static void census_resolve(struct census *cs, unsigned first, unsigned n, uint64_t progress, int all)
+{
+    size_t kept = 0;
+    for (size_t i = 0; i < cs->n_pend; i++) {
+        const wmbus_burst *b = &cs->pend[i];
+        if (b->stream < first || b->stream >= first + n) { cs->pend[kept++] = *b; continue; }
+        if (!all && progress < b->first_block + b->blocks + cs->margin) { cs->pend[kept++] = *b; continue; }
+        int matched = 0, clean = 0;
+        for (size_t k = 0; k < cs->n_lines; k++) {
+            const struct census_line *l = &cs->lines[k];
+            if (wmbus_activity_match(b, 1, l->stream, l->channel, cs->cfg->simultaneous ? l->chain : b->chain, l->ka) == 0) { matched = 1; clean |= l->crc_ok; }
+        }
+        unsigned long long *sum = cs->sum[((size_t)b->stream * cs->ch + b->channel) * 2u + b->chain];
+        sum[0]++; sum[1] += (unsigned)matched; sum[2] += (unsigned)clean;
+        census_print_row(cs, b->stream, b->channel, b->chain);
+        fprintf(stderr, "block %llu %.1f ms x%.1f %s\n", (unsigned long long)b->first_block, (double)b->blocks * 512e3 / (double)cs->fin,
+                (double)b->mean / (double)(b->floor ? b->floor : 1u), clean ? "decoded" : matched ? "crc-failed" : "missed");
+    }
+    cs->n_pend = kept;
+    kept = 0;                                                /* a line too old for any burst still to come leaves */
+    for (size_t k = 0; k < cs->n_lines; k++) {
+        const struct census_line *l = &cs->lines[k];
+        const int mine = l->stream >= first && l->stream < first + n;
+        if (mine && (all || l->ka + cs->keep < progress)) continue;
+        cs->lines[kept++] = *l;
+    }
+    cs->n_lines = kept;
+}
+
+/* one collect of one context: its lines (stream already counted over the whole batch), their levels, its bursts (stream counted from `first`) */
+static int census_push(struct census *cs, unsigned first, unsigned n, const wmbus_line *ln, const wmbus_level *lev, size_t nl, const wmbus_burst *bu, size_t nb, uint64_t progress)
+{
+    if (cs->n_lines + nl > cs->cap_lines) {
+        void *p = realloc(cs->lines, (cs->n_lines + nl + 64u) * sizeof *cs->lines);
+        if (!p) return -1;
+        cs->lines = p; cs->cap_lines = cs->n_lines + nl + 64u;
+    }
+    if (cs->n_pend + nb > cs->cap_pend) {
+        void *p = realloc(cs->pend, (cs->n_pend + nb + 64u) * sizeof *cs->pend);
+        if (!p) return -1;
+        cs->pend = p; cs->cap_pend = cs->n_pend + nb + 64u;
+    }
+    for (size_t i = 0; i < nl; i++) {
+        uint64_t ka = 0;
+        if (wmbus_line_power_block(cs->cfg->decimation, cs->cfg->input_rate_hz, lev[i].sync_sample, &ka)) continue;
+        cs->lines[cs->n_lines++] = (struct census_line){ka, ln[i].stream, ln[i].channel, ln[i].chain, ln[i].crc_ok};
+    }
+    for (size_t i = 0; i < nb; i++) {
+        if (!cs->cfg->simultaneous && bu[i].chain != WMBUS_CHAIN_T1C1) continue;
+        cs->pend[cs->n_pend] = bu[i];
+        cs->pend[cs->n_pend++].stream += first;
+    }
+    census_resolve(cs, first, n, progress, 0);
+    return 0;
+}
+
+static void census_close(struct census *cs)
+{
+    for (unsigned s = 0; s < cs->n_streams; s++)
+        for (unsigned c = 0; c < cs->ch; c++)
+            for (unsigned chain = 0; chain < (cs->cfg->simultaneous ? 2u : 1u); chain++) {
+                const unsigned long long *sum = cs->sum[((size_t)s * cs->ch + c) * 2u + chain];
+                census_print_row(cs, s, c, chain);
+                fprintf(stderr, "%llu transmissions, %llu decoded, %llu CRC-clean\n", sum[0], sum[1], sum[2]);
+            }
+    free(cs->pend); free(cs->lines); free(cs->sum);
+    memset(cs, 0, sizeof *cs);
+}
+
 static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line *ln, size_t nl, const char *text, const wmbus_timing *t)
 {
     struct batch_job *j = user;
-    (void)n;
     const wmbus_level *lev = NULL;
     const wmbus_power *pw = NULL;
     pthread_mutex_lock(&out_lock);
@@ -280,6 +394,18 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
         write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, line_channel_hz(&j->cfg, ln + i));
     }
     if (nl) fflush(stdout);
+    if (j->cfg.channel_activity) {                           /* -m: this collect's bursts and lines into the census */
+        const wmbus_burst *bu = NULL;
+        const wmbus_level *lv = NULL;
+        const size_t nb = wmbus_batch_activity(j->b, first, &bu);
+        uint64_t progress = 0;
+        for (unsigned i = 0; i < wmbus_batch_contexts(j->b); i++) {
+            unsigned f = 0, m = 0;
+            wmbus_ctx *ctx = wmbus_batch_context(j->b, i, &f, &m);
+            if (ctx && f == first) progress = wmbus_activity_progress(ctx);
+        }
+        if (wmbus_batch_line_levels(j->b, first, &lv) != nl || census_push(&j->census, first, n, ln, lv, nl, bu, nb, progress)) j->lev_missing = 1;
+    }
     pthread_mutex_unlock(&out_lock);
 }
 
@@ -326,11 +452,18 @@ static int run_batch(struct batch_job *j)
     }
     clock_gettime(CLOCK_MONOTONIC, &t_open1);
     j->b = b;
+    if (j->cfg.channel_activity && census_open(&j->census, &j->cfg, (unsigned)j->n, j->names)) { fprintf(stderr, "rtl_wmbus_hip: out of memory\n"); goto out; }
     if (j->stats) fprintf(stderr, "rtl_wmbus_hip: device %d: contexts open after %.3f s\n", j->cfg.device, (double)(t_open1.tv_sec - t_open0.tv_sec) + (t_open1.tv_nsec - t_open0.tv_nsec) * 1e-9);
     wmbus_batch_io io;
     memset(&io, 0, sizeof io);
     io.fill = batch_fill_padded; io.lines = batch_lines; io.user = j;
     if (wmbus_batch_run(b, &io, &j->st)) { fprintf(stderr, "rtl_wmbus_hip: %s\n", wmbus_batch_last_error(b)); goto out; }
+    if (j->cfg.channel_activity) {                           /* -m: what is still open is resolved by the end of the input, then every file's summary */
+        pthread_mutex_lock(&out_lock);
+        census_resolve(&j->census, 0, (unsigned)j->n, 0, 1);
+        census_close(&j->census);
+        pthread_mutex_unlock(&out_lock);
+    }
     if (j->stats)
         fprintf(stderr, "rtl_wmbus_hip: device %d: %d files, %u contexts, %llu samples, %llu lines, %u pushes in %.3f s = %.1f Msamples/s\n", j->cfg.device, j->n,
                 wmbus_batch_contexts(b), (unsigned long long)j->st.samples, (unsigned long long)j->st.lines, j->st.pushes, j->st.seconds,
@@ -506,7 +639,7 @@ static int parse_devices(const char *arg, int *devs, int cap)
 }
 
 /* ---- live stream (stdin / TCP): wm_reader.c stages the bytes, this is where a push leaves -------- */
-struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; unsigned afc_changes; unsigned afc_ch_changes[WMBUS_MAX_CHANNELS]; };
+struct live { wmbus_ctx *ctx; unsigned told; int levels; const wmbus_cfg *cfg; unsigned afc_changes; unsigned afc_ch_changes[WMBUS_MAX_CHANNELS]; struct census census; };
 
 /* a list with auto: entries (cfg.input_channel_afc_hz): is any channel following its transmitter? */
 static int any_channel_afc(const wmbus_cfg *cfg)
@@ -542,6 +675,14 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     if (lv->cfg->show_algorithm)                             /* a list with auto: entries: every following channel's lock */
         for (unsigned ch = 0; ch < lv->cfg->input_channels; ch++)
             if (lv->cfg->input_channel_afc_hz[ch]) print_afc(lv->ctx, ch, NULL, &lv->afc_ch_changes[ch], &lv->cfg->input_channel_hz[ch]);
+    if (lv->cfg->channel_activity) {                         /* -m */
+        const wmbus_line *ln; const wmbus_level *lev = NULL; const wmbus_burst *bu = NULL;
+        const size_t nl = wmbus_lines(lv->ctx, &ln), nb = wmbus_activity(lv->ctx, &bu);
+        if (wmbus_line_levels(lv->ctx, &lev) != nl || census_push(&lv->census, 0, 1, ln, lev, nl, bu, nb, wmbus_activity_progress(lv->ctx))) {
+            fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
+            return -1;
+        }
+    }
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
     if (len && (lv->levels || lv->cfg->line_power || lv->cfg->input_channels > 1u)) {
@@ -570,7 +711,7 @@ int main(int argc, char **argv)
     double age_seconds = 0.0;                                /* -E */
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:n")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:nm")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -603,6 +744,7 @@ int main(int argc, char **argv)
         case 'S': stats = 1; break;
         case 'l': cfg.line_levels = 1; break;
         case 'n': cfg.line_power = 1; break;
+        case 'm': cfg.channel_activity = 1; break;
         case 'w': cfg.input_spectrum = 1; break;
         case 'E': {
             char *end;
@@ -728,7 +870,7 @@ int main(int argc, char **argv)
     int fd = 0;
     if (tcp && (fd = open_tcp(tcp)) < 0) return EXIT_FAILURE;
 
-    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg, 0, {0}};
+    struct live lv = {NULL, 0, (int)cfg.line_levels, &cfg, 0, {0}, {0}};
     int rc = wmbus_open(&cfg, &lv.ctx);
     if (rc) {
         fprintf(stderr, "rtl_wmbus_hip: cannot open GPU back end: %s\n", lv.ctx ? wmbus_last_error(lv.ctx) : "out of memory");
@@ -737,7 +879,9 @@ int main(int argc, char **argv)
     }
     /* -f: the reference arms alarm(2) around every fread (rtl_wmbus.c:1300-1302) */
     const wm_reader_cfg rc_cfg = {fd, cfg.max_push_bytes, max_latency_ms, check_flow ? 2000u : 0u};
+    if (cfg.channel_activity && census_open(&lv.census, &cfg, 1u, NULL)) { fprintf(stderr, "rtl_wmbus_hip: out of memory\n"); wmbus_close(lv.ctx); return EXIT_FAILURE; }
     const int how = wm_reader_run(&rc_cfg, live_push, &lv);
+    if (cfg.channel_activity) { census_resolve(&lv.census, 0, 1u, 0, 1); census_close(&lv.census); }      /* -m: the end of the input resolves the rest */
     if (cfg.input_spectrum && how == WM_READER_EOF) print_spectrum(lv.ctx, 0, &cfg, NULL);
     wmbus_close(lv.ctx);
     if (how == WM_READER_FLOW_STOPPED) {

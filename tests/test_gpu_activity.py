@@ -1,0 +1,324 @@
+"""Channel activity on the GPU (cfg.channel_activity): the records of every pipeline row equal tests/activity_ref.py evaluated on
+tests/power_ref.py's timeline, do not depend on how the input is cut into pushes, every row carries its own, they mean what the header
+says on synthetic and bundled captures, and nothing else of a context moves."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import activity_ref as AR
+import afc_age_ref as AG
+import format_ref as FR
+import power_ref as PW
+import spectrum_ref as PR
+
+pytestmark = pytest.mark.gpu
+
+FS = 1600000
+CUTS = [1, 3, 16, 5, 64, 7]                         # 4096-byte units per push, repeated until the capture ends
+N_BLK = 1024                                        # 2^19 samples: 16 epochs, more than H + 2 = 11
+# (first level block, level blocks) of the loud runs of capture "runs": lengths 1 and 2, a start in lane 0, ends in lane 63, runs across two
+# and three epochs (one holds an epoch wholly), and one that the stream's end leaves open
+RUNS = [(10, 1), (20, 2), (60, 1), (64, 5), (120, 8), (190, 2), (250, 10), (300, 140), (600, 1), (700, 3), (1020, 4)]
+
+
+def cut_sizes(total, cuts=CUTS):
+    out, left, k = [], total // 4096 * 4096, 0
+    while left:
+        n = min(4096 * cuts[k % len(cuts)], left)
+        out.append(n); left -= n; k += 1
+    return out
+
+
+def noise_blocks(sigma_of_block, seed):
+    """cu8: complex Gaussian noise whose sigma (in units of the byte) is set level block by level block."""
+    rng = np.random.default_rng(seed)
+    sig = np.repeat(np.asarray(sigma_of_block, float), 2 * PR.N)
+    return np.clip(np.rint(127.5 + sig * rng.standard_normal(sig.size)), 0, 255).astype(np.uint8)
+
+
+def built(kind):
+    sigma = np.full(N_BLK, 3.0)
+    if kind == "runs":
+        for first, blocks in RUNS:
+            sigma[first:first + blocks] = 15.0
+    elif kind == "carrier":                         # never ends: closes by itself at the start of epoch H + 2
+        sigma[100:] = 15.0
+    elif kind == "forgets":                         # a quiet first epoch: everything behind it is a burst until the floor forgets it
+        sigma[:64] = 0.8
+        sigma[800:806] = 15.0
+    return noise_blocks(sigma, {"runs": 11, "carrier": 12, "forgets": 13}[kind])
+
+
+def run_activity(wm, caps, sizes, **kw):
+    """All pushes of `caps` through one context with channel_activity = 1.  Returns a dict: bursts = the records of all collects in
+    order, per_push = [records], P[(chain, v)] = the row's timeline over the whole stream, lines = [(line, level)], progress = [..]."""
+    kw.setdefault("channel_activity", 1)
+    kw.setdefault("keep_taps", False)
+    out = dict(bursts=[], per_push=[], P={}, lines=[], progress=[], powers=[])
+    with wm.Receiver(n_streams=len(caps), max_push_bytes=max(sizes), **kw) as rx:
+        S = len(caps) * rx.n_channels
+        off = 0
+        for n in sizes:
+            rx.push([c[off:off + n] for c in caps]); off += n
+            got = rx.activity()
+            assert got == sorted(got, key=lambda b: (b["chain"], b["stream"], b["channel"], b["first_block"]))      # rows ascending, first_block ascending
+            out["bursts"] += got; out["per_push"].append(got)
+            out["lines"] += list(zip(rx.lines(), rx.line_levels()))
+            out["powers"] += rx.line_power()
+            out["progress"].append(rx.activity_progress())
+            for ch in (0, 1):
+                for v in range(S):
+                    out["P"].setdefault((ch, v), []).append(rx.read_channel_power(ch, v)[0])
+        out["channels"] = rx.n_channels
+    out["P"] = {k: np.concatenate(v) for k, v in out["P"].items()}
+    return out
+
+
+def of_row(run, chain, v):
+    ch = run["channels"]
+    return AR.strip([b for b in run["bursts"] if b["chain"] == chain and b["stream"] * ch + b["channel"] == v])
+
+
+def rows_equal_the_rule(run, fin, want_P, T=0):
+    """want_P[(chain, v)]: the restatement's timeline.  The library's P equals it, and every row's records equal the rule on it."""
+    for key, p in want_P.items():
+        assert np.array_equal(run["P"][key], p), key
+        assert of_row(run, *key) == AR.rule(p, fin, T), key
+    assert len(run["bursts"]) == sum(len(AR.rule(p, fin, T)) for p in want_P.values())
+
+
+@pytest.fixture(scope="module")
+def constructed():
+    """The three constructed captures and their reference timelines: computed once, left unchanged."""
+    caps = {k: built(k) for k in ("runs", "carrier", "forgets")}
+    return dict(caps=caps, P={k: PW.channel_power(PW.band_rows(c, FR.CU8), FS, 0) for k, c in caps.items()})
+
+
+def test_constructed_runs(wm, constructed):
+    """1.  Level blocks of two noise amplitudes place the runs of the rule test; three captures side by side in one context.  The cases
+    are there on the restatement, and the records equal it."""
+    names = ("runs", "carrier", "forgets")
+    P = constructed["P"]
+    want = {k: AR.rule(P[k], FS) for k in names}
+    assert [(b["first_block"], b["blocks"]) for b in want["runs"]] == [r for r in RUNS if r[1] >= 2 and r[0] + r[1] < N_BLK]
+    H = AR.epochs_back(FS)
+    assert [(b["first_block"], b["blocks"]) for b in want["carrier"]] == [(100, 64 * (H + 2) - 100)]
+    assert [(b["first_block"], b["blocks"]) for b in want["forgets"]] == [(64, 64 * H), (800, 6)]
+    caps = [constructed["caps"][k] for k in names]
+    for T in (0, 512):
+        run = run_activity(wm, caps, [caps[0].size], channel_activity_ratio_q8=T)
+        rows_equal_the_rule(run, FS, {(ch, v): P[k] for ch in (0, 1) for v, k in enumerate(names)}, T)
+        assert run["progress"] == [N_BLK]
+    assert of_row(run, 0, 0) != of_row(run, 0, 1) != of_row(run, 0, 2)
+
+
+def test_cut_independence(wm, constructed):
+    """2.  Pushed once, in pushes of 4096 x {1, 3, 16, 5, 64, 7} bytes -- also with every burst through the host decoders and with every
+    hand-off round on the host -- and as cf32 in single level blocks: the concatenated records are identical."""
+    cu8, P = constructed["caps"]["runs"], constructed["P"]["runs"]
+    want = AR.rule(P, FS)
+    one = run_activity(wm, [cu8], [cu8.size])
+    assert of_row(one, 0, 0) == want == of_row(one, 1, 0)
+    sizes = cut_sizes(cu8.size)
+    for kw in (dict(), dict(bursts_to_host=True), dict(rounds_on_host=True)):
+        cut = run_activity(wm, [cu8], sizes, **kw)
+        assert of_row(cut, 0, 0) == want == of_row(cut, 1, 0), kw
+        assert cut["progress"] == [int(v) for v in np.cumsum([n // 1024 for n in sizes])]
+        # a record leaves with the push that completes the epoch of its closing block, not later and not earlier
+        done = 0
+        for got, prog in zip(cut["per_push"], cut["progress"]):
+            due = [b for b in want if (b["first_block"] + b["blocks"]) // 64 * 64 + 64 <= prog]
+            assert AR.strip([b for b in got if b["chain"] == 0]) == due[done:], prog
+            done = len(due)
+        assert sum(1 for got in cut["per_push"] if got) >= 3                # the records leave over several collects
+    cf32 = FR.raw_bytes((2.0 * cu8.astype(np.float32) - 255.0) / 256.0, FR.CF32)
+    Pf = PW.channel_power(PW.band_rows(cf32, FR.CF32), FS, 0)
+    whole = run_activity(wm, [cf32], [cf32.size], input_format=FR.CF32)
+    single = run_activity(wm, [cf32], [4096] * (cf32.size // 4096), input_format=FR.CF32)
+    assert np.array_equal(whole["P"][(0, 0)], Pf) and np.array_equal(single["P"][(0, 0)], Pf)
+    assert of_row(whole, 0, 0) == AR.rule(Pf, FS) == of_row(single, 0, 0) and of_row(whole, 1, 0) == of_row(single, 1, 0) == of_row(whole, 0, 0)
+    assert [(b["first_block"], b["blocks"]) for b in of_row(single, 0, 0)] == [(b["first_block"], b["blocks"]) for b in want]
+
+
+def tone_bursts(fin, n, plan, seed):
+    """Complex samples: noise of sigma 0.01 of full scale, and for every (f_hz, first block, blocks) of `plan` a tone of amplitude 0.2."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n)
+    x = 0.01 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    for f, first, blocks in plan:
+        on = (t >= first * PR.N) & (t < (first + blocks) * PR.N)
+        x = x + np.where(on, 0.2 * np.exp(2j * np.pi * f / fin * t), 0)
+    return np.stack([x.real, x.imag], axis=1).reshape(-1)
+
+
+def test_every_row_carries_its_own(wm, constructed):
+    """3.  Two captures with different content; two channels of a 4.0 MS/s cs16 capture; -s at 2.4 MS/s, whose chains listen 650 kHz apart."""
+    caps, P = constructed["caps"], constructed["P"]
+    run = run_activity(wm, [caps["forgets"], caps["runs"]], cut_sizes(caps["runs"].size, [64, 7, 33]))
+    rows_equal_the_rule(run, FS, {(ch, v): P[k] for ch in (0, 1) for v, k in enumerate(("forgets", "runs"))})
+    assert of_row(run, 0, 0) != of_row(run, 0, 1)
+
+    n = 1 << 18                                      # 512 level blocks, 8 epochs
+    fin, hz = 4000000, [1600000, -1240000]
+    plans = ([(hz[0], 70, 9), (hz[1], 130, 2), (hz[0], 200, 70), (hz[1], 300, 5)], [(hz[1], 66, 3), (hz[0], 383, 3)])
+    raws = [FR.raw_bytes(np.clip(np.rint(32767 * tone_bursts(fin, n, plan, 40 + k)), -32768, 32767), FR.CS16) for k, plan in enumerate(plans)]
+    run = run_activity(wm, raws, cut_sizes(raws[0].size, [64, 5, 200]), input_rate_hz=fin, input_format=FR.CS16, input_channel_hz=hz)
+    want = {}
+    for k, raw in enumerate(raws):
+        rows = PW.band_rows(raw, FR.CS16)
+        for c, f in enumerate(hz):
+            for ch in (0, 1):
+                want[(ch, 2 * k + c)] = PW.channel_power(rows, fin, f)
+    rows_equal_the_rule(run, fin, want)
+    got = {key: [(b["first_block"], b["blocks"]) for b in of_row(run, *key)] for key in want}
+    assert got[(0, 0)] == [(70, 9), (200, 70)] and got[(0, 1)] == [(130, 2), (300, 5)] and got[(0, 2)] == [(383, 3)] and got[(0, 3)] == [(66, 3)], got
+    assert all(b["stream"] == v // 2 and b["channel"] == v % 2 for v in range(4) for b in run["bursts"] if b["stream"] * 2 + b["channel"] == v)
+
+    fin = 2400000
+    cu8 = np.clip(np.rint(127.5 + 127.5 * tone_bursts(fin, n, [(325000, 80, 6), (-325000, 150, 4), (325000, 250, 2)], 50)), 0, 255).astype(np.uint8)
+    run = run_activity(wm, [cu8], [cu8.size], decimation=3, simultaneous=True)
+    rows = PW.band_rows(cu8, FR.CU8)
+    rows_equal_the_rule(run, fin, {(ch, 0): PW.channel_power(rows, fin, PW.chain_hz(ch, True)) for ch in (0, 1)})
+    assert [(b["first_block"], b["blocks"]) for b in of_row(run, 0, 0)] == [(80, 6), (250, 2)]
+    assert [(b["first_block"], b["blocks"]) for b in of_row(run, 1, 0)] == [(150, 4)]
+
+
+def frames_and_records(wm, seed, amplitude):
+    cu8, frames = wm.synth_capture(seed=seed, n_samples=1 << 19, kinds=wm.T1 | wm.C1A | wm.S1, frames_per_s=40.0, amplitude=amplitude, noise_sigma=3.0)
+    return cu8, frames, run_activity(wm, [cu8], [cu8.size])
+
+
+def every_frame_has_its_record(frames, bursts):
+    """Every complete frame whose closing block lies in a complete epoch has exactly one record within one level block at both ends."""
+    n_eval = N_BLK // 64 * 64
+    seen = 0
+    for f in frames:
+        first, last = f["start"] // PR.N, (f["start"] + f["n"] - 1) // PR.N
+        if not f["complete"] or last + 2 >= n_eval:
+            continue
+        mine = [b for b in bursts if b["first_block"] <= last and b["first_block"] + b["blocks"] > first]
+        print(f"frame blocks {first} ... {last}: {[(b['first_block'], b['blocks']) for b in mine]}")
+        assert len(mine) == 1, (f, mine)
+        assert abs(mine[0]["first_block"] - first) <= 1 and abs(mine[0]["first_block"] + mine[0]["blocks"] - 1 - last) <= 1, (f, mine)
+        seen += 1
+    return seen
+
+
+def test_meaning_strong_frames(wm):
+    """4a.  Seed 1, amplitude 60, sigma 3: a record per frame, and every line matches a record (checked on the restatement: 12 of 12)."""
+    cu8, frames, run = frames_and_records(wm, 1, 60.0)
+    bursts = [b for b in run["bursts"] if b["chain"] == 0]
+    assert AR.strip(bursts) == AR.rule(PW.channel_power(PW.band_rows(cu8, FR.CU8), FS, 0), FS)
+    assert every_frame_has_its_record(frames, bursts) >= 10
+    n_eval = N_BLK // 64 * 64
+    matched = 0
+    for ln, lv in run["lines"]:
+        ka = wm.line_power_block(lv["sync_sample"])
+        assert ka == PW.block_of(lv["sync_sample"])
+        k = wm.activity_match(run["bursts"], ln["stream"], ln["channel"], ln["chain"], ka)
+        assert k == AR.match(of_row(run, ln["chain"], 0), ka) + (len(bursts) if ln["chain"] and k >= 0 else 0)      # rows ascending: chain 1's records follow chain 0's
+        if PW.block_of(ln["sample"]) + 2 < n_eval:               # a telegram the stream's last epoch holds has no record yet
+            assert k >= 0, (ln, lv)
+            matched += 1
+    assert matched >= 10
+
+
+def test_meaning_weak_frames(wm):
+    """4b.  Seed 3, amplitude 5: the frames are still found (on the restatement: 11 of 11), whatever the framers make of them."""
+    cu8, frames, run = frames_and_records(wm, 3, 5.0)
+    assert every_frame_has_its_record(frames, [b for b in run["bursts"] if b["chain"] == 0]) >= 9
+
+
+def test_meaning_noise_and_the_bundled_capture(wm, samples):
+    """4c.  2^20 samples of cu8 noise, sigma 3: no record.  The bundled 1.6 MS/s capture: (748, 21) and (1424, 46) on either chain's row; the
+    bundled 2.4 MS/s capture with -s: (143, 33) on the T1/C1 row alone.  How the first capture's four lines match the two records is printed, not asserted (DESIGN.md section 6 records it)."""
+    noise = noise_blocks(np.full(2048, 3.0), 21)
+    run = run_activity(wm, [noise], [noise.size])
+    assert run["bursts"] == [] and run["progress"] == [2048]
+    cu8 = samples["samples2"][:samples["samples2"].size // 4096 * 4096]
+    run = run_activity(wm, [cu8], [cu8.size])
+    for ch in (0, 1):
+        assert [(b["first_block"], b["blocks"]) for b in of_row(run, ch, 0)] == [(748, 21), (1424, 46)]
+    wide = samples["issue48"][:samples["issue48"].size // 4096 * 4096]         # 2.4 MS/s, -s: one record on the T1/C1 row, none on the S1 row
+    sim = run_activity(wm, [wide], [wide.size], decimation=3, simultaneous=True)
+    assert [(b["first_block"], b["blocks"]) for b in of_row(sim, 0, 0)] == [(143, 33)] and of_row(sim, 1, 0) == []
+    for ln, lv in run["lines"]:
+        ka = wm.line_power_block(lv["sync_sample"])
+        k = wm.activity_match(run["bursts"], ln["stream"], ln["channel"], ln["chain"], ka)
+        print(f"line chain {ln['chain']} algo {ln['algo']} crc {ln['crc_ok']} access-code block {ka}: " + (f"record {run['bursts'][k]['first_block']}" if k >= 0 else "no record"))
+
+
+def test_under_afc_the_records_follow_the_timeline(wm):
+    """5.  input_afc on the two-tone capture of the ageing tests: P follows the lock push by push, and the records equal the restatement
+    on the P wmbus_read_channel_power returned."""
+    raw, cuts = AG.two_tones()
+    run = run_activity(wm, [raw], cuts, input_afc=1, input_spectrum_age=6)
+    for ch in (0, 1):
+        assert of_row(run, ch, 0) == AR.rule(run["P"][(ch, 0)], FS)
+    assert run["progress"][-1] == raw.size // 2 // PR.N
+
+
+def test_nothing_else_moves(wm):
+    """6.  Lines, levels and power records with the field equal those without; without it wmbus_activity returns 0 and NULL; the EINVAL
+    cases."""
+    cu8, _ = wm.synth_capture(seed=1, n_samples=1 << 18, kinds=wm.T1 | wm.C1A | wm.S1, frames_per_s=40.0, amplitude=60.0, noise_sigma=3.0)
+    on = run_activity(wm, [cu8], [cu8.size], line_power=1, line_levels=1)
+    with wm.Receiver(n_streams=1, max_push_bytes=cu8.size, keep_taps=False, line_power=1, line_levels=1) as rx:
+        rx.push([cu8])
+        assert rx.lines() == [ln for ln, _ in on["lines"]] and rx.line_levels() == [lv for _, lv in on["lines"]] and rx.line_power() == on["powers"]
+        assert len(rx.lines()) >= 4 and on["bursts"]
+        assert rx.activity() == [] and rx.activity_progress() == 0
+        p = ctypes.POINTER(wm.Burst)()
+        assert wm.lib().wmbus_activity(rx._h, ctypes.byref(p)) == 0 and not p
+    alone = run_activity(wm, [cu8], [cu8.size])                  # the field alone switches line_power's stage on
+    assert alone["bursts"] == on["bursts"] and alone["lines"] == on["lines"] and alone["powers"] == on["powers"]
+    for kw in (dict(channel_activity=2), dict(channel_activity=0, channel_activity_ratio_q8=1024), dict(channel_activity=1, channel_activity_ratio_q8=256),
+               dict(channel_activity=1, channel_activity_ratio_q8=65536), dict(channel_activity=1, channel_activity_ratio_q8=1)):
+        with pytest.raises(wm.WmbusError):
+            wm.Receiver(n_streams=1, **kw)
+    for T in (257, 65535):
+        wm.Receiver(n_streams=1, keep_taps=False, channel_activity=1, channel_activity_ratio_q8=T).close()
+
+
+def test_cli_switch(wm, constructed, tmp_path):
+    """7.  -m: stdout is byte-identical to the run without it; stderr carries one line per burst with the library's values and the
+    summary, alone and with -S."""
+    cu8, _ = wm.synth_capture(seed=1, n_samples=1 << 19, kinds=wm.T1 | wm.C1A | wm.S1, frames_per_s=40.0, amplitude=60.0, noise_sigma=3.0)
+    run = run_activity(wm, [cu8], [cu8.size])
+    bursts = [b for b in run["bursts"] if b["chain"] == 0]
+    status = []
+    for b in bursts:
+        hits = [ln for ln, lv in run["lines"] if AR.matches(b, PW.block_of(lv["sync_sample"]))]
+        status.append("decoded" if any(ln["crc_ok"] for ln in hits) else "crc-failed" if hits else "missed")
+    want = [f"activity: block {b['first_block']} {b['blocks'] * 512e3 / FS:.1f} ms x{b['mean'] / max(b['floor'], 1):.1f} {s}" for b, s in zip(bursts, status)]
+    summary = f"activity: {len(bursts)} transmissions, {sum(s != 'missed' for s in status)} decoded, {status.count('decoded')} CRC-clean"
+    assert len(bursts) >= 10 and status.count("decoded") >= 8
+    env = dict(os.environ, WMBUS_FIXED_TS="1")
+
+    def cli(*args, **kw):
+        p = subprocess.run([wm.CLI_PATH, "-v", *args], capture_output=True, env=env, timeout=120, **kw)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return p.stdout, [ln for ln in p.stderr.decode().splitlines() if "activity" in ln]
+    plain, none = cli(input=cu8.tobytes())
+    assert none == [] and plain
+    out, err = cli("-m", input=cu8.tobytes())
+    assert out == plain
+    assert sorted(err[:-1], key=lambda s: int(s.split()[2])) == want and err[-1] == summary
+    out, err = cli("-m", "-B", "65536", input=cu8.tobytes())      # pushes of 64 KiB: resolved along the way, the same lines
+    assert out == plain and sorted(err[:-1], key=lambda s: int(s.split()[2])) == want and err[-1] == summary
+    cu8.tofile(tmp_path / "a.cu8")
+    constructed["caps"]["runs"].tofile(tmp_path / "b.cu8")
+    plain_s, _ = cli("-S", "a.cu8", "b.cu8", cwd=tmp_path)
+    out, err = cli("-m", "-S", "a.cu8", "b.cu8", cwd=tmp_path)
+    assert out == plain_s
+    a = [ln[len("a.cu8: "):] for ln in err if ln.startswith("a.cu8: ")]
+    assert sorted(a[:-1], key=lambda s: int(s.split()[2])) == want and a[-1] == summary
+    b = [ln[len("b.cu8: "):] for ln in err if ln.startswith("b.cu8: ")]
+    runs = AR.rule(constructed["P"]["runs"], FS)
+    assert [int(s.split()[2]) for s in b[:-1]] == [r["first_block"] for r in runs] and all(s.endswith(" missed") for s in b[:-1])
+    assert b[-1] == f"activity: {len(runs)} transmissions, 0 decoded, 0 CRC-clean"
+    p = subprocess.run([wm.CLI_PATH, "-h"], capture_output=True, env=env, timeout=60)
+    assert p.stdout.decode().count("\t-m census of transmissions") == 1
