@@ -93,6 +93,16 @@ typedef struct wmbus_cfg {
      * [-1, 1]) instead of bit for bit; RSSI, clock recovery and framers stay exact on those symbols.  A telegram whose
      * decision hangs on the last bits of a soft symbol may decode differently (DESIGN_HISTORY.md section 12 and DESIGN.md section 6 count them). */
     int tolerance_mode;
+    /* 0 (default): off.  1: CRC REPAIR -- a telegram of the time2 framer that the GPU has decoded whole inside a push and that fails a block
+     * CRC is repaired on the GPU by flipping its least reliable chips, by the fixed integer rule defined below under CRC REPAIR; a
+     * repaired telegram is printed as if those chips had been received (CRC flag 1, wmbus_line.crc_ok = 1), every other line is the one
+     * of a context without the field, and every line comes with a repair record (wmbus_repair, wmbus_line_repairs() below).  The field
+     * switches the level records of line_levels on by itself, as line_power does (wmbus_line_levels works): the rule reads the soft
+     * symbols and the preamble window they are measured on.  0 is in every respect the context without this field: the same kernels,
+     * buffers, bytes and lines.  WMBUS_EINVAL: anything above 1; together with bursts_to_host (nothing is decoded on the GPU then: there
+     * is nothing it could repair).  (The newest field: directly in front of rounds_on_host -- every field from there to the end of the struct is
+     * pinned to its neighbours by the features before this one -- nothing behind it moves.) */
+    unsigned crc_repair;
     /* Tuning and test knobs, 0 = the library's default.  (Rounds 1-4 read these from WMBUS_* environment variables inside the
      * push path; as configuration two contexts of one process can differ, and nothing in a push calls getenv.) */
     unsigned rounds_on_host;    /* 1: no hand-off rounds are enqueued unattended: every hand-off failure is finished by the host-driven
@@ -528,6 +538,7 @@ int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t 
  * The limits:
  *   - the result depends on how the input is cut into pushes -- the first feature of this library of which that is true (a host that
  *     set input_shift_hz between pushes would have the same property);
+ *     (cfg.crc_repair is the second: which telegrams it examines depends on the cut, CRC REPAIR below)
  *   - a telegram that straddles a change is rotated with two frequencies;
  *   - telegrams in pushes before the first lock are decoded at the nominal;
  *   - the max-hold never forgets: wmbus_read_spectrum(reset) is the remedy on a long live stream;
@@ -656,6 +667,51 @@ size_t wmbus_activity(const wmbus_ctx *ctx, const wmbus_burst **records);
 uint64_t wmbus_activity_progress(const wmbus_ctx *ctx);
 long wmbus_activity_rule(const uint32_t *p, size_t n, unsigned in_hz, unsigned ratio_q8, wmbus_burst *out, size_t cap);
 long wmbus_activity_match(const wmbus_burst *records, size_t n, unsigned stream, unsigned channel, int chain, uint64_t ka);
+/* CRC REPAIR (cfg.crc_repair = 1; tests/repair_ref.py restates it in numpy and Python integers on top of tests/telegram_ref.py and
+ * tests/level_ref.py).  Integers only behind LINE LEVELS' rint.
+ *   subject      a burst of the TIME2 framer (WMBUS_ALGO_T2A) that the GPU has decoded whole inside the push that holds its access code,
+ *                whose decoder completed the telegram, whose CRC verdict is 0 and whose length L (air bytes, CRC bytes included) is at
+ *                least 12.  Nothing else is examined: not the lines of the run-length framer (its chips record the end of a run, not a
+ *                decision instant: the soft symbol there says nothing about the chip), not a burst cut by the end of a push and finished
+ *                by the host decoders, not a decoder that gave up.  An S1 telegram with an invalid Manchester pair never completes, so
+ *                S1 is repaired only where BOTH chips of a pair are wrong.
+ *   chips        j = 0 is the access-code chip.  Byte b of the telegram holds the chips j = 1 + 12 b ... 12 + 12 b (T1),
+ *                17 + 8 b ... 24 + 8 b (C1), 1 + 16 b ... 16 + 16 b (S1).  For chip j: p[j] its decimated sample, s the soft symbol there
+ *                (LINE LEVELS' s: in front of -o; with cfg.tolerance_mode that mode's symbols), q[j] = LINE LEVELS' clamp(rint(s 2^20),
+ *                -2^20, 2^20), c = LINE LEVELS' mean over the telegram's preamble window, 0 where that record is invalid (n = 0).  The
+ *                reliability of the chip is r[j] = |q[j] - c|.
+ *   blocks       the CRC blocks of the L air bytes: frame A 12 bytes, then blocks of 18; frame B blocks of 128; the last block is as
+ *                long as what is left.  A bad block of fewer than 3 bytes cannot be repaired.
+ *   candidates   of a bad block: the chips of its bytes, except those of the telegram's byte 0, the L-field (a flip there would change
+ *                the length).  K = min(8, their number); the K candidates with the smallest (r, j), ascending; bit i of a pattern m is
+ *                the i-th of them.
+ *   patterns     m = 1 ... 2^K - 1: flip the chips of m and decode the block's bytes by the mode's code.  m is valid if every
+ *                3-out-of-6 symbol (T1) or Manchester pair (S1) of the block is a code word and the block's CRC equals the CRC-16 of the
+ *                bytes before it.  C1 is NRZ: every chip pattern is a code word, the CRC alone decides.  w(m) = sum of r over the flipped
+ *                chips (64 bits).  The repair of the block is the valid m with the smallest (w, m); none valid: the block stays bad.
+ *   telegram     repaired only if EVERY bad block has a repair.  Then its bytes are the repaired bytes, its line is formatted as if the
+ *                GPU had decoded those chips -- CRC flag 1, the 3-out-of-6 flag recomputed over the whole telegram -- and
+ *                wmbus_line.crc_ok = 1.  Otherwise line and bytes are exactly those of crc_repair = 0.  cfg.dedup_twins and
+ *                cfg.only_crc_ok act behind the repair.
+ *   record       one wmbus_repair per line, the count and the order of wmbus_lines() as for the level records.  All zero for a clean
+ *                line and for a line that was no subject.  A subject that stayed bad reports blocks_bad and the repairs found for single
+ *                blocks (blocks_repaired < blocks_bad), its line unchanged.  weight = sum of w over the repaired blocks, below 2^29
+ *                (17 blocks of 8 chips of at most 2^21).
+ * Only integers follow rint and a minimum over patterns does not depend on the order of a reduction, so the result for a subject depends
+ * on the stream alone.  The limit, beside AFC's: WHICH telegrams are subjects depends on how the input is cut into pushes -- a telegram
+ * that straddles a push edge is finished by the host decoders and is not repaired.
+ * What a repair is worth.  A T1 or S1 pattern has to pass the line code AND the CRC; a C1 pattern only the CRC: an unrepairable C1 block
+ * has at most 255 chances in 65 536 of matching by accident.  K = 8 and the rule rest on three captures and nothing else: the bundled
+ * 1.6 MS/s capture (its second telegram, 117 air bytes, one invalid symbol in the last block: one chip flipped, weight 24 800, the
+ * telegram the capture otherwise yields only when re-run 10.29 kHz lower) and two synthetic captures of 60 telegrams each near the
+ * discriminator's threshold (T1 and C1 frame A; tests/golden/repair.json holds the counts), on which every repaired telegram equals the
+ * bytes that were sent.  The errors of an FM discriminator near threshold come in clicks, not in single chips: most bad telegrams stay
+ * bad.  Nobody has measured the rule on a capture with interference.
+ *
+ * wmbus_line_repairs: the repair records of the last push's lines, the same count and the same order as wmbus_lines() (cfg.dedup_twins /
+ * only_crc_ok drop a record with its line).  A context opened without cfg.crc_repair: 0, and *records = NULL. */
+typedef struct wmbus_repair { uint16_t blocks_bad, blocks_repaired, chips_flipped, pad; uint32_t weight; } wmbus_repair;
+size_t wmbus_line_repairs(const wmbus_ctx *ctx, const wmbus_repair **records);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):
@@ -776,6 +832,8 @@ size_t wmbus_batch_line_power(const wmbus_batch *b, unsigned first_stream, const
 /* The same for a batch opened with cfg.channel_activity: the bursts of the collect whose lines the `lines` callback has just been handed;
  * wmbus_burst.stream counts from first_stream. */
 size_t wmbus_batch_activity(const wmbus_batch *b, unsigned first_stream, const wmbus_burst **records);
+/* The same for a batch opened with cfg.crc_repair: the repair records of the lines the `lines` callback has just been handed. */
+size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, const wmbus_repair **records);
 
 #ifdef __cplusplus
 }

@@ -241,6 +241,12 @@ struct wmbus_ctx {
     WmLevel *h_lev_pkts = nullptr, *h_lev_hdr = nullptr;
     void *dv_lev_pkts = nullptr, *dv_lev_hdr = nullptr;
     std::vector<wmbus_level> levels;                    /* parallel to `lines` */
+    /* cfg.crc_repair (wm_k3_repair.h): the repair records k3_repair writes beside h_pkts (pinned, zero-copy like those); it switches
+     * lev_on on.  nullptr without the option. */
+    bool rep_on = false;
+    WmRepair *h_rep_pkts = nullptr;
+    void *dv_rep_pkts = nullptr;
+    std::vector<wmbus_repair> repairs;                  /* parallel to `lines` */
     K1Entry k1[K1_ROLES];                               /* the demodulation kernels of this context */
     K1Args k1a{}; uint32_t ntiles = 0;                  /* this push's launch arguments (collect's slow path re-uses them) */
     std::vector<HostDecoder> decs;                      /* [stream][chain][algo] */
@@ -624,7 +630,12 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     c->act.on = cfg->channel_activity != 0u;
     c->act.T = cfg->channel_activity_ratio_q8 ? cfg->channel_activity_ratio_q8 : WM_K0_ACT_RATIO_Q8;
     c->pw.on = cfg->line_power != 0u || c->act.on;                    /* the census reads the timeline of CHANNEL POWER */
-    c->lev_on = cfg->line_levels != 0u || c->pw.on;                   /* a power record needs its line's access-code sample: the level record carries it */
+    if (cfg->crc_repair > 1u) return fail(c, WMBUS_EINVAL, "crc_repair must be 0 or 1, got %u", cfg->crc_repair);
+    if (cfg->crc_repair && cfg->bursts_to_host)
+        return fail(c, WMBUS_EINVAL, "crc_repair works on the telegrams the GPU decodes: with bursts_to_host there is nothing it could repair");
+    c->rep_on = cfg->crc_repair != 0u;
+    /* a power record needs its line's access-code sample: the level record carries it; the repair reads that sample and the soft-symbol tail */
+    c->lev_on = cfg->line_levels != 0u || c->pw.on || c->rep_on;
     if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
     c->spec.on = cfg->input_spectrum != 0u || c->pw.on;          /* the band rows are the survey's */
     auto &k = c->k0;
@@ -929,6 +940,10 @@ static int open_allocate(wmbus_ctx *c)
         A(m.halloc(&c->h_lev_hdr, (size_t)c->hdr_cap));
         if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_lev_pkts, c->h_lev_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_lev_hdr, c->h_lev_hdr, 0)); }
     }
+    if (c->rep_on) {
+        A(m.halloc(&c->h_rep_pkts, (size_t)c->pkts_cap));
+        if (e == hipSuccess) A(hipHostGetDevicePointer(&c->dv_rep_pkts, c->h_rep_pkts, 0));
+    }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_hdr, c->h_hdr, 0)); A(hipHostGetDevicePointer(&c->dv_words, c->h_words, 0)); }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_pkts, c->h_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_bytes, c->h_bytes, 0)); }
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e));
@@ -1230,6 +1245,13 @@ static int launch_k3(wmbus_ctx *c, bool again)
         lv.lev_pkts = (WmLevel *)c->dv_lev_pkts; lv.lev_hdr = (WmLevel *)c->dv_lev_hdr;
         hipLaunchKernelGGL(k3_levels, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, lv);
         hipLaunchKernelGGL(k3_level_tail, dim3((WM_LEV_TAIL + 255u) / 256u, 2u * c->S), dim3(256), 0, c->stream, lv);
+        if (c->rep_on && k3.pkts) {
+            /* cfg.crc_repair: behind the bursts and the levels, on the packets k3_bursts has just written (in place: their flags, their
+             * bytes), with the same soft symbols and the same tail as the levels; a record per packet slot beside them */
+            K3RepArgs ra{};
+            ra.k3 = k3; ra.dphi = lv.dphi; ra.tail_in = lv.tail_in; ra.src_pkts = k3.lev_pkt; ra.rep_pkts = (WmRepair *)c->dv_rep_pkts;
+            hipLaunchKernelGGL(k3_repair, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, ra);
+        }
     }
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -1824,7 +1846,7 @@ int wmbus_collect(wmbus_ctx *c)
 {
     if (!c) return WMBUS_EINVAL;
     const int rc = wait_gpu(c);
-    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); return rc; }
+    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); return rc; }
     return decode_host(c);
 }
 
@@ -1860,6 +1882,12 @@ size_t wmbus_line_levels(const wmbus_ctx *c, const wmbus_level **levels)
 {
     if (levels) *levels = c && c->lev_on ? c->levels.data() : nullptr;
     return c && c->lev_on ? c->levels.size() : 0;
+}
+
+size_t wmbus_line_repairs(const wmbus_ctx *c, const wmbus_repair **records)
+{
+    if (records) *records = c && c->rep_on ? c->repairs.data() : nullptr;
+    return c && c->rep_on ? c->repairs.size() : 0;
 }
 
 size_t wmbus_line_power(const wmbus_ctx *c, const wmbus_power **power)

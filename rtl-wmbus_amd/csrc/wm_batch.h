@@ -259,6 +259,15 @@ size_t wmbus_batch_activity(const wmbus_batch *b, unsigned first_stream, const w
     return 0;
 }
 
+size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, const wmbus_repair **records)
+{
+    if (records) *records = nullptr;
+    if (!b || !b->opened) return 0;
+    for (size_t i = 0; i < b->ctx.size(); i++)
+        if (b->first[i] == first_stream) return wmbus_line_repairs(b->ctx[i], records);
+    return 0;
+}
+
 int wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats *stats)
 {
     if (!b || !io) return WMBUS_EINVAL;

@@ -40,6 +40,9 @@
  *   k3_levels    option (cfg.line_levels): frequency offset and deviation of every candidate telegram from the soft symbols of its
  *                preamble, in integers; k3_level_tail carries the last 782 soft symbols of every row to the next push.
  *                                  (no counterpart: the reference prints two RSSI bytes only)
+ *   k3_repair    option (cfg.crc_repair): a time2 telegram decoded inside the push that fails a block CRC gets its least reliable chips
+ *                flipped, 255 patterns per bad block over the lanes of a wave, in integers; the packet is rewritten in place.
+ *                                  (no counterpart: the reference prints such a telegram with CRC flag 0)
  *
  * Exactness: every float operation the reference performs is performed here in the same order
  * with separate roundings (wm_exact.h; the file is also built with -ffp-contract=off).  The
@@ -126,3 +129,4 @@ __global__ void k2_finish(WmPush g, K2Finish f)
 
 #include "wm_k3_bursts.h"
 #include "wm_k3_levels.h"
+#include "wm_k3_repair.h"

@@ -74,6 +74,8 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-n append ;signal;noise;x<strength> to every line (behind -l's fields, in front of a channel's): the power in the telegram's 200 kHz channel, the noise floor in the 20 ms in front of its preamble and their ratio, measured on the GPU from the raw input, in front of every gain and of the AGC; a field is empty where no level block could be counted\n");
     fprintf(stdout, "\t-m census of transmissions: stderr gets one line per burst of energy in the channel, decoded or not (activity: block <first level block of 512 samples> <duration> ms x<strength over the floor> decoded|crc-failed|missed,\n");
     fprintf(stdout, "\t   with the file name in batch mode and the channel Hz of a list), and at the end of the input a summary per capture and channel (activity: N transmissions, N decoded, N CRC-clean); measured on the GPU from the raw input; stdout does not change\n");
+    fprintf(stdout, "\t-x repair time2 telegrams that fail a block CRC: the least reliable chips of a bad block are flipped on the GPU (up to 8 candidates per block, the line code and the CRC decide);\n");
+    fprintf(stdout, "\t   a repaired line is printed with CRC flag 1 and ;x<blocks repaired>/<chips flipped> appended (behind -l's and -n's fields, in front of a channel's); with -v stderr gets repair: N subjects, M repaired at the end\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
     fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
     fprintf(stdout, "\t-E seconds the survey of -w and -O auto forgets: it holds the last seconds ... 2 x seconds of the input (epochs of 2^A x 512 samples, the smallest A that\n");
@@ -253,9 +255,15 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
 /* -n: ";signal;noise;x<ratio>" behind -l's fields and in front of the channel's: the power in the telegram's channel, the noise floor in
  * front of it (each empty where no level block could be counted) and the strength the way the spectrum: lines print theirs (empty without
  * either). */
-static void write_line(const char *text, size_t len, const wmbus_level *lev, const wmbus_power *pw, const int *chan_hz)
+/* -x: the repair records of the lines printed so far (callers hold out_lock or are single-threaded); a subject has a bad block */
+static unsigned long long repair_subjects, repair_repaired;
+static int line_repaired(const wmbus_repair *rp) { return rp && rp->blocks_bad && rp->blocks_repaired == rp->blocks_bad; }
+
+static void write_line(const char *text, size_t len, const wmbus_level *lev, const wmbus_power *pw, const wmbus_repair *rp, const int *chan_hz)
 {
-    if (!lev && !pw && !chan_hz) { fwrite(text, 1, len, stdout); return; }
+    if (rp && rp->blocks_bad) { repair_subjects++; repair_repaired += (unsigned)line_repaired(rp); }
+    if (!line_repaired(rp)) rp = NULL;                       /* only a repaired line gets the field */
+    if (!lev && !pw && !rp && !chan_hz) { fwrite(text, 1, len, stdout); return; }
     if (len && text[len - 1] == '\n') len--;
     fwrite(text, 1, len, stdout);
     if (lev && lev->n) fprintf(stdout, ";%d;%u", (int)lev->offset_hz, (unsigned)lev->dev_hz);
@@ -265,6 +273,7 @@ static void write_line(const char *text, size_t len, const wmbus_level *lev, con
         if (pw->n_noise) fprintf(stdout, ";%u", (unsigned)pw->noise); else fputc(';', stdout);
         if (pw->n_signal && pw->n_noise) fprintf(stdout, ";x%.1f", (double)pw->ratio_q8 / 256.0); else fputc(';', stdout);
     }
+    if (rp) fprintf(stdout, ";x%u/%u", (unsigned)rp->blocks_repaired, (unsigned)rp->chips_flipped);
     if (chan_hz) fprintf(stdout, ";%d", *chan_hz);
     fputc('\n', stdout);
 }
@@ -380,8 +389,10 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     struct batch_job *j = user;
     const wmbus_level *lev = NULL;
     const wmbus_power *pw = NULL;
+    const wmbus_repair *rp = NULL;
     pthread_mutex_lock(&out_lock);
-    if ((j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) || (j->cfg.line_power && wmbus_batch_line_power(j->b, first, &pw) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+    if ((j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) || (j->cfg.line_power && wmbus_batch_line_power(j->b, first, &pw) != nl) ||
+        (j->cfg.crc_repair && wmbus_batch_line_repairs(j->b, first, &rp) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
         fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing; the lines are not printed\n", nl);
         j->lev_missing = 1;
         pthread_mutex_unlock(&out_lock);
@@ -391,7 +402,7 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
-        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, line_channel_hz(&j->cfg, ln + i));
+        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, rp ? rp + i : NULL, line_channel_hz(&j->cfg, ln + i));
     }
     if (nl) fflush(stdout);
     if (j->cfg.channel_activity) {                           /* -m: this collect's bursts and lines into the census */
@@ -685,15 +696,17 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     }
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
-    if (len && (lv->levels || lv->cfg->line_power || lv->cfg->input_channels > 1u)) {
+    if (len && (lv->levels || lv->cfg->line_power || lv->cfg->crc_repair || lv->cfg->input_channels > 1u)) {
         const wmbus_line *ln; const wmbus_level *lev = NULL;
         const wmbus_power *pw = NULL;
+        const wmbus_repair *rp = NULL;
         const size_t nl = wmbus_lines(lv->ctx, &ln);
-        if ((lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) || (lv->cfg->line_power && wmbus_line_power(lv->ctx, &pw) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+        if ((lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) || (lv->cfg->line_power && wmbus_line_power(lv->ctx, &pw) != nl) ||
+            (lv->cfg->crc_repair && wmbus_line_repairs(lv->ctx, &rp) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
             fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
             return -1;
         }
-        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lv->levels && lev ? lev + i : NULL, pw ? pw + i : NULL, line_channel_hz(lv->cfg, ln + i));
+        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lv->levels && lev ? lev + i : NULL, pw ? pw + i : NULL, rp ? rp + i : NULL, line_channel_hz(lv->cfg, ln + i));
         fflush(stdout);
     } else if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
     return 0;
@@ -711,7 +724,7 @@ int main(int argc, char **argv)
     double age_seconds = 0.0;                                /* -E */
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:nm")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:nmx")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -745,6 +758,7 @@ int main(int argc, char **argv)
         case 'l': cfg.line_levels = 1; break;
         case 'n': cfg.line_power = 1; break;
         case 'm': cfg.channel_activity = 1; break;
+        case 'x': cfg.crc_repair = 1; break;
         case 'w': cfg.input_spectrum = 1; break;
         case 'E': {
             char *end;
@@ -862,7 +876,9 @@ int main(int argc, char **argv)
          * pipeline's first and last push, and the pinning, long.  So: 1 MiB per file and push from 384 files per device on, else 2 MiB */
         if (n_devs == 0) { devs[0] = cfg.device; n_devs = 1; }
         if (cfg.max_push_bytes == 0) cfg.max_push_bytes = (argc - optind + n_devs - 1) / n_devs >= 384 ? 1u << 20 : 2u << 20;
-        finish(run_sharded(cfg, argc - optind, argv + optind, devs, n_devs, map_only, stats));
+        const int rc_batch = run_sharded(cfg, argc - optind, argv + optind, devs, n_devs, map_only, stats);
+        if (cfg.crc_repair && cfg.show_algorithm && !map_only) fprintf(stderr, "repair: %llu subjects, %llu repaired\n", repair_subjects, repair_repaired);
+        finish(rc_batch);
     }
     if (cfg.max_push_bytes == 0) cfg.max_push_bytes = 1u << 20;
 
@@ -883,6 +899,7 @@ int main(int argc, char **argv)
     const int how = wm_reader_run(&rc_cfg, live_push, &lv);
     if (cfg.channel_activity) { census_resolve(&lv.census, 0, 1u, 0, 1); census_close(&lv.census); }      /* -m: the end of the input resolves the rest */
     if (cfg.input_spectrum && how == WM_READER_EOF) print_spectrum(lv.ctx, 0, &cfg, NULL);
+    if (cfg.crc_repair && cfg.show_algorithm) fprintf(stderr, "repair: %llu subjects, %llu repaired\n", repair_subjects, repair_repaired);
     wmbus_close(lv.ctx);
     if (how == WM_READER_FLOW_STOPPED) {
         fprintf(stderr, "rtl_wmbus: exiting since incoming data stopped flowing!\n");      /* rtl_wmbus.c:76 */
