@@ -87,6 +87,16 @@ typedef struct wmbus_cfg {
                                    that wmbus_stage() for the next push may run while the previous one is in flight (the
                                    copies run on their own HIP stream).  wmbus_device_input() names the window the next
                                    wmbus_process() will read. */
+    /* 0 (default): off.  1: LINE QUALITY -- every datagram line comes with a quality record (wmbus_quality, wmbus_line_quality() below):
+     * the transmitter's chip rate, the jitter of the decision instants and the eye opening of the soft symbols at them, measured on the
+     * GPU by the fixed integer rule defined below under LINE QUALITY, for the telegrams of the time2 framer that the GPU decoded whole
+     * inside a push (n = 0 for every other line).  The lines themselves do not change.  The field switches the level records of
+     * line_levels on by itself, as line_power and crc_repair do.  0 is in every respect the context without this field: the same
+     * kernels, buffers, bytes and lines.  WMBUS_EINVAL: anything above 1; together with bursts_to_host (nothing is decoded on the GPU
+     * then: there is nothing it could measure).  (The newest field: directly in front of tolerance_mode -- every field from
+     * tolerance_mode to the end of the struct is pinned to its neighbours by the tests of the features before this one, and
+     * input_windows / tolerance_mode was the last seam no test pinned -- nothing else moves.) */
+    unsigned line_quality;
     /* 0 (default): every soft symbol, RSSI byte and chip is bit-identical to the reference's.  1: TOLERANCE MODE for the
      * default switches (both chains, cargf arctangent, no -P): the discriminator uses a polynomial arctangent and the two
      * FIR low-passes fused multiply-adds, so soft symbols agree with the reference's to 2e-6 (absolute; they lie in
@@ -538,7 +548,8 @@ int wmbus_spectrum_channels(unsigned in_hz, const uint64_t *sum, const uint32_t 
  * The limits:
  *   - the result depends on how the input is cut into pushes -- the first feature of this library of which that is true (a host that
  *     set input_shift_hz between pushes would have the same property);
- *     (cfg.crc_repair is the second: which telegrams it examines depends on the cut, CRC REPAIR below)
+ *     (cfg.crc_repair is the second: which telegrams it examines depends on the cut, CRC REPAIR below; cfg.line_quality the third, for
+ *     the same reason: LINE QUALITY below)
  *   - a telegram that straddles a change is rotated with two frequencies;
  *   - telegrams in pushes before the first lock are decoded at the nominal;
  *   - the max-hold never forgets: wmbus_read_spectrum(reset) is the remedy on a long live stream;
@@ -712,6 +723,54 @@ long wmbus_activity_match(const wmbus_burst *records, size_t n, unsigned stream,
  * only_crc_ok drop a record with its line).  A context opened without cfg.crc_repair: 0, and *records = NULL. */
 typedef struct wmbus_repair { uint16_t blocks_bad, blocks_repaired, chips_flipped, pad; uint32_t weight; } wmbus_repair;
 size_t wmbus_line_repairs(const wmbus_ctx *ctx, const wmbus_repair **records);
+/* LINE QUALITY (cfg.line_quality = 1; tests/quality_ref.py restates it in Python integers on top of tests/repair_ref.py and
+ * tests/level_ref.py).  Integers only behind LINE LEVELS' rint; floor(a / b) floors for negative a too.
+ *   subject      a packet record of the burst kernel that is complete (WM_PKT_DONE), of the TIME2 framer (WMBUS_ALGO_T2A), with a length
+ *                L (air bytes, CRC bytes included) of at most 292, whose n = off + cpb L chips lie whole inside this push's chip stream:
+ *                the chips count from the access-code chip j = 0, off = 1, 17, 1 and cpb = 12, 8, 16 for T1, C1, S1 (CRC REPAIR's chips).
+ *                These are CRC REPAIR's subjects without "not CRC-clean" and "L >= 12".  Everything else gets the all-zero record,
+ *                n = 0: the lines of the run-length framer (its chips mark the end of a run, not a decision instant), a burst cut by a
+ *                push edge and finished by the host decoders, a decoder that gave up.
+ *   chips        pos[j] the push-relative decimated sample of chip j, v[j] its value, p[j] = pos[j] - pos[0].  The record is invalid
+ *                (all zero) too if n < 2, if p[n-1] >= 2^17, if num <= 0 below, or if one of the two chip values does not occur.
+ *   timing       64-bit integers.  With n <= 1 + 16 x 292 = 4673 and p < 2^17 every intermediate stays below 2^63: the largest is
+ *                80 000 000 den, about 2.7 10^18.
+ *                  j' = 2 j - (n - 1);  num = sum j' p[j];  den = sum j'^2 = n (n^2 - 1) / 3
+ *                  chip_rate_chz = floor((80 000 000 den + num) / (2 num))
+ *                the least-squares chip rate in hundredths of a chip per second (800 kHz den / (2 num), rounded): T1 / C1 nominal is
+ *                10 000 000, S1 3 276 800.  (A framer decides at most one chip per sample, so p[j] >= j, num >= den / 2 and the figure is at
+ *                most 80 000 000.)
+ *                  B = floor((4 x 65536 num + den) / (2 den))          samples per chip in Q16
+ *                  s = sum (65536 p[j] - B j);  A = floor((2 s + n) / (2 n))
+ *                  e = sum |65536 p[j] - B j - A|
+ *                  jitter_ns = floor((1250 e + 32768 n) / (65536 n))
+ *                the mean absolute distance of a decision instant from the fitted clock; one decimated sample is 1250 ns.  Positions are
+ *                whole samples: a perfect clock that does not sit on the sample grid reads a few hundred ns, not 0.
+ *   eye          q[j] = LINE LEVELS' quantised soft symbol at pos[j], of the row CRC REPAIR reads (in front of -o; with
+ *                cfg.tolerance_mode that mode's symbols).  n1, n0 the chips of value 1 and 0, S1, S0 the sums of their q (64 bits:
+ *                4673 x 2^20 exceeds 2^31).
+ *                  m1 = floor((2 S1 + n1) / (2 n1)), m0 likewise;  mid = floor((m1 + m0) / 2)
+ *                  spread = sum |q[j] - m(v[j])|;  sigma = +1 if m1 >= m0, else -1
+ *                  margin of chip j = sigma (q[j] - mid) for v[j] = 1, sigma (mid - q[j]) for v[j] = 0;  eye = the smallest margin
+ *                and with hz(x, N) = floor((3125 x + 4096 N) / (8192 N)), LINE LEVELS' unit:
+ *                  hi_hz = hz(m1, 1), lo_hz = hz(m0, 1), spread_hz = hz(spread, n), eye_hz = hz(eye, 1)
+ *                eye_hz <= 0: a chip lies on the wrong side of the midpoint -- the direct cause of a bad CRC block.
+ * The record is measured on the chips as received: cfg.crc_repair does not change it (a repair flips chips in its own copy).  Integer
+ * sums do not depend on the order of a reduction, so a subject's record depends on the stream alone.  The limit, CRC REPAIR's: WHICH
+ * telegrams are subjects depends on how the input is cut into pushes -- a telegram that straddles a push edge has n = 0.
+ * The bundled 1.6 MS/s capture: its T1 telegram of 48 air bytes reads 99 800.14 chip/s, 1367 ns, hi 41 642, lo -68 343, eye 32 214 Hz; the
+ * one of 117 bytes that fails its CRC 99 765.30 chip/s, 775 ns, eye -9 951 Hz: closed.
+ *
+ * wmbus_line_quality: the quality records of the last push's lines, the same count and the same order as wmbus_lines() (cfg.dedup_twins /
+ * only_crc_ok drop a record with its line).  A context opened without cfg.line_quality: 0, and *records = NULL. */
+typedef struct wmbus_quality {
+    uint32_t n, chip_rate_chz, jitter_ns;
+    int32_t  hi_hz, lo_hz;
+    uint32_t spread_hz;
+    int32_t  eye_hz;
+    uint32_t pad;
+} wmbus_quality;   /* 32 bytes */
+size_t wmbus_line_quality(const wmbus_ctx *ctx, const wmbus_quality **records);
 /* I/Q DC BLOCKER (cfg.input_dc = R, 1 ... 12; tests/dc_ref.py restates it in numpy).  With x the format's int16 sample per I and per Q
  * by the UNSHIFTED rules above (cu8 2 u - 255, cs8 2 s + 1, cs16 s, cf32 as it is), m the sample's index within the stream (64 bits) and
  * level block k = m >> 9 (512 input samples):
@@ -834,6 +893,8 @@ size_t wmbus_batch_line_power(const wmbus_batch *b, unsigned first_stream, const
 size_t wmbus_batch_activity(const wmbus_batch *b, unsigned first_stream, const wmbus_burst **records);
 /* The same for a batch opened with cfg.crc_repair: the repair records of the lines the `lines` callback has just been handed. */
 size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, const wmbus_repair **records);
+/* The same for a batch opened with cfg.line_quality: the quality records of the lines the `lines` callback has just been handed. */
+size_t wmbus_batch_line_quality(const wmbus_batch *b, unsigned first_stream, const wmbus_quality **records);
 
 #ifdef __cplusplus
 }

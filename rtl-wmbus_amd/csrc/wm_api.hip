@@ -247,6 +247,12 @@ struct wmbus_ctx {
     WmRepair *h_rep_pkts = nullptr;
     void *dv_rep_pkts = nullptr;
     std::vector<wmbus_repair> repairs;                  /* parallel to `lines` */
+    /* cfg.line_quality (wm_k3_quality.h): the quality records k3_quality writes beside h_rep_pkts, pinned and zero-copy like those; it
+     * switches lev_on on.  nullptr without the option. */
+    bool q_on = false;
+    WmQuality *h_q_pkts = nullptr;
+    void *dv_q_pkts = nullptr;
+    std::vector<wmbus_quality> qualities;               /* parallel to `lines` */
     K1Entry k1[K1_ROLES];                               /* the demodulation kernels of this context */
     K1Args k1a{}; uint32_t ntiles = 0;                  /* this push's launch arguments (collect's slow path re-uses them) */
     std::vector<HostDecoder> decs;                      /* [stream][chain][algo] */
@@ -635,7 +641,11 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
         return fail(c, WMBUS_EINVAL, "crc_repair works on the telegrams the GPU decodes: with bursts_to_host there is nothing it could repair");
     c->rep_on = cfg->crc_repair != 0u;
     /* a power record needs its line's access-code sample: the level record carries it; the repair reads that sample and the soft-symbol tail */
-    c->lev_on = cfg->line_levels != 0u || c->pw.on || c->rep_on;
+    if (cfg->line_quality > 1u) return fail(c, WMBUS_EINVAL, "line_quality must be 0 or 1, got %u", cfg->line_quality);
+    if (cfg->line_quality && cfg->bursts_to_host)
+        return fail(c, WMBUS_EINVAL, "line_quality works on the telegrams the GPU decodes: with bursts_to_host there is nothing it could measure");
+    c->q_on = cfg->line_quality != 0u;                                /* k3_quality reads each packet's access-code sample: k3_bursts leaves it for the level stage */
+    c->lev_on = cfg->line_levels != 0u || c->pw.on || c->rep_on || c->q_on;
     if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
     c->spec.on = cfg->input_spectrum != 0u || c->pw.on;          /* the band rows are the survey's */
     auto &k = c->k0;
@@ -944,6 +954,10 @@ static int open_allocate(wmbus_ctx *c)
         A(m.halloc(&c->h_rep_pkts, (size_t)c->pkts_cap));
         if (e == hipSuccess) A(hipHostGetDevicePointer(&c->dv_rep_pkts, c->h_rep_pkts, 0));
     }
+    if (c->q_on) {
+        A(m.halloc(&c->h_q_pkts, (size_t)c->pkts_cap));
+        if (e == hipSuccess) A(hipHostGetDevicePointer(&c->dv_q_pkts, c->h_q_pkts, 0));
+    }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_hdr, c->h_hdr, 0)); A(hipHostGetDevicePointer(&c->dv_words, c->h_words, 0)); }
     if (e == hipSuccess) { A(hipHostGetDevicePointer(&c->dv_pkts, c->h_pkts, 0)); A(hipHostGetDevicePointer(&c->dv_bytes, c->h_bytes, 0)); }
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? WMBUS_ENOMEM : WMBUS_EDEVICE, "allocation failed: %s", hipGetErrorString(e));
@@ -1251,6 +1265,13 @@ static int launch_k3(wmbus_ctx *c, bool again)
             K3RepArgs ra{};
             ra.k3 = k3; ra.dphi = lv.dphi; ra.tail_in = lv.tail_in; ra.src_pkts = k3.lev_pkt; ra.rep_pkts = (WmRepair *)c->dv_rep_pkts;
             hipLaunchKernelGGL(k3_repair, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, ra);
+        }
+        if (c->q_on && k3.pkts) {
+            /* cfg.line_quality: a record per packet slot from the chip regions, the counts and the soft symbols -- nothing k3_repair
+             * changes, so its place behind it is a matter of order only */
+            K3QualArgs qa{};
+            qa.k3 = k3; qa.dphi = lv.dphi; qa.src_pkts = k3.lev_pkt; qa.q_pkts = (WmQuality *)c->dv_q_pkts;
+            hipLaunchKernelGGL(k3_quality, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, qa);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -1846,7 +1867,7 @@ int wmbus_collect(wmbus_ctx *c)
 {
     if (!c) return WMBUS_EINVAL;
     const int rc = wait_gpu(c);
-    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); return rc; }
+    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->qualities.clear(); return rc; }
     return decode_host(c);
 }
 
@@ -1888,6 +1909,12 @@ size_t wmbus_line_repairs(const wmbus_ctx *c, const wmbus_repair **records)
 {
     if (records) *records = c && c->rep_on ? c->repairs.data() : nullptr;
     return c && c->rep_on ? c->repairs.size() : 0;
+}
+
+size_t wmbus_line_quality(const wmbus_ctx *c, const wmbus_quality **records)
+{
+    if (records) *records = c && c->q_on ? c->qualities.data() : nullptr;
+    return c && c->q_on ? c->qualities.size() : 0;
 }
 
 size_t wmbus_line_power(const wmbus_ctx *c, const wmbus_power **power)

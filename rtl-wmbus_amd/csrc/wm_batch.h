@@ -268,6 +268,15 @@ size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, con
     return 0;
 }
 
+size_t wmbus_batch_line_quality(const wmbus_batch *b, unsigned first_stream, const wmbus_quality **records)
+{
+    if (records) *records = nullptr;
+    if (!b || !b->opened) return 0;
+    for (size_t i = 0; i < b->ctx.size(); i++)
+        if (b->first[i] == first_stream) return wmbus_line_quality(b->ctx[i], records);
+    return 0;
+}
+
 int wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats *stats)
 {
     if (!b || !io) return WMBUS_EINVAL;

@@ -13,7 +13,7 @@ struct LineRec {
     uint64_t sample; uint32_t stream; uint8_t chain, algo, crc_ok; uint32_t seq; uint32_t part, off, len;
     uint32_t lev;              /* cfg.line_levels: its level record in its part's `levs` */
 };
-struct LinePart { std::vector<LineRec> recs; std::string text; std::vector<wmbus_level> levs; std::vector<wmbus_repair> reps; };   /* reps: cfg.crc_repair, beside levs */
+struct LinePart { std::vector<LineRec> recs; std::string text; std::vector<wmbus_level> levs; std::vector<wmbus_repair> reps; std::vector<wmbus_quality> quals; };   /* reps: cfg.crc_repair, quals: cfg.line_quality, beside levs */
 
 /* Persistent host worker pool of a context (packet decoders): run(n, f) executes f(0..n-1) on the
  * workers and the caller; threads are created once, not per push. */
@@ -112,11 +112,13 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
     /* the level travels with its item to the line it produces: a packet's is record idx of h_lev_pkts, a burst's the one its decoder keeps */
     /* the repair record likewise (cfg.crc_repair switches the levels on: the two vectors run in step): a packet's is record idx of
      * h_rep_pkts, a burst the host decoders finished was no subject */
-    auto keep = [&](LineRec &r, const char *line, size_t n, const wmbus_level *lev, const wmbus_repair *rep) {
+    /* and the quality record (cfg.line_quality): record idx of h_q_pkts, n = 0 for a burst the host decoders finished */
+    auto keep = [&](LineRec &r, const char *line, size_t n, const wmbus_level *lev, const wmbus_repair *rep, const wmbus_quality *ql) {
         r.part = part_no; r.off = (uint32_t)part.text.size(); r.len = (uint32_t)n;
         r.lev = (uint32_t)part.levs.size();
         if (c->lev_on) part.levs.push_back(*lev);
         if (c->rep_on) part.reps.push_back(rep ? *rep : wmbus_repair{});
+        if (c->q_on) part.quals.push_back(ql ? *ql : wmbus_quality{});
         part.text.append(line, n);
         out.push_back(r);
     };
@@ -150,7 +152,8 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                                                   (p.flags & WM_PKTF_ERR3OF6) != 0, ok, p.L, pkt, p.pkt_rssi, p.rssi_now, tag, ts, line, sizeof line);
                 LineRec r; r.sample = p.sample; r.stream = p.stream; r.chain = p.chain; r.algo = p.algo;
                 r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                keep(r, line, n, c->lev_on ? &c->h_lev_pkts[order[j].idx] : nullptr, c->rep_on ? &c->h_rep_pkts[order[j].idx] : nullptr);
+                keep(r, line, n, c->lev_on ? &c->h_lev_pkts[order[j].idx] : nullptr, c->rep_on ? &c->h_rep_pkts[order[j].idx] : nullptr,
+                     c->q_on ? &c->h_q_pkts[order[j].idx] : nullptr);
                 continue;
             }
             const WmBurstHdr &h = c->h_hdr[order[j].idx];
@@ -175,7 +178,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                     const size_t n = wm_decoder_format(&hd.dec, tag, ts, rssi, line, sizeof line, &ok);
                     LineRec r; r.sample = h.pos0 + (word >> 11); r.stream = h.stream; r.chain = h.chain; r.algo = h.algo;
                     r.crc_ok = (uint8_t)ok; r.seq = seq++;
-                    keep(r, line, n, &hd.lev, nullptr);
+                    keep(r, line, n, &hd.lev, nullptr, nullptr);
                     st = WM_DEC_IDLE;
                 }
                 if (st == WM_DEC_IDLE) { k++; break; }
@@ -197,7 +200,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
  * and the decoders only, so the NEXT push's front may already be on the GPU. */
 static int decode_host(wmbus_ctx *c)
 {
-    c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear();
+    c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->qualities.clear();
     c->short_burst.store(0);
     if (!c->done.valid) return WMBUS_OK;
     c->done.valid = false;
@@ -284,6 +287,7 @@ static int decode_host(wmbus_ctx *c)
         c->lines.push_back(l);
         if (c->lev_on) c->levels.push_back(parts[r.part].levs[r.lev]);
         if (c->rep_on) c->repairs.push_back(parts[r.part].reps[r.lev]);
+        if (c->q_on) c->qualities.push_back(parts[r.part].quals[r.lev]);
         if (c->pw.on) {
             /* cfg.line_power: the line's record from its row's P history (wm_k0_power.h).  Its access-code sample came with the level record
              * -- for a burst finished in a later push the decoder kept it -- its completing sample is the line's; both are decimated

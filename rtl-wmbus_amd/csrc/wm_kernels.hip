@@ -43,6 +43,9 @@
  *   k3_repair    option (cfg.crc_repair): a time2 telegram decoded inside the push that fails a block CRC gets its least reliable chips
  *                flipped, 255 patterns per bad block over the lanes of a wave, in integers; the packet is rewritten in place.
  *                                  (no counterpart: the reference prints such a telegram with CRC flag 0)
+ *   k3_quality   option (cfg.line_quality): chip rate, jitter of the decision instants and eye of the soft symbols of every time2
+ *                telegram decoded inside the push, one wave per packet, two walks over its chips, 64-bit integer sums.
+ *                                  (no counterpart: the reference prints two RSSI bytes only)
  *
  * Exactness: every float operation the reference performs is performed here in the same order
  * with separate roundings (wm_exact.h; the file is also built with -ffp-contract=off).  The
@@ -130,3 +133,4 @@ __global__ void k2_finish(WmPush g, K2Finish f)
 #include "wm_k3_bursts.h"
 #include "wm_k3_levels.h"
 #include "wm_k3_repair.h"
+#include "wm_k3_quality.h"
