@@ -291,7 +291,8 @@ typedef struct wmbus_level {
 
 /* Per-push timings measured with HIP events on the library's own stream (ms). */
 typedef struct wmbus_timing {
-    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it, with cfg.input_spectrum the survey */
+    float demod_ms;             /* front end + discriminator + FIR + RSSI kernel; with cfg.input_rate_hz also the resampler in front of it, with cfg.input_spectrum the survey
+                                   (in a batch lane, wmbus_batch_lane_stats: this context's own launches -- its mate's follow on the same stream, in the mate's figure) */
     float clock_ms;             /* IIR clock recovery + time2 framer (incl. re-runs)  */
     float rla_ms;               /* run-length framer (incl. re-runs)                  */
     float gather_ms;            /* burst extraction (and, without debug views, the RSSI of the tiles the bursts touch; with cfg.line_levels the level kernels) */
@@ -881,6 +882,13 @@ int  wmbus_batch_stage(wmbus_batch *b, unsigned stream, const uint8_t *cu8, size
 void *wmbus_batch_device_input(wmbus_batch *b, unsigned stream);
 /* Runs until every group's source has ended (or `passes` pushes per context).  Returns 0 or the first error. */
 int  wmbus_batch_run(wmbus_batch *b, const wmbus_batch_io *io, wmbus_batch_stats *stats);
+/* Lanes.  With fewer hardware queues than contexts (GPU_MAX_HW_QUEUES as the caller has it; HIP's own default is 4) neighbouring
+ * contexts share a lane: one worker thread, one stream, and the latency-bound framer and burst kernels of the two leave as ONE launch
+ * (streams that share a queue would run their pushes one after the other).  A lane holds two contexts at most; with a queue per
+ * context every context is its own lane.  WMBUS_BATCH_LANES=N in the environment, read by wmbus_batch_open, overrides the count.
+ * *lanes: the lanes of this batch; *paired_launches / *single_launches: kernel launches of the last wmbus_batch_run that carried two
+ * contexts / one.  Any pointer may be NULL.  Returns 0, or WMBUS_EINVAL for a batch that is not open. */
+int  wmbus_batch_lane_stats(const wmbus_batch *b, unsigned *lanes, unsigned long long *paired_launches, unsigned long long *single_launches);
 /* For the SINK of a batch opened with cfg.line_levels: the level records of the lines the `lines` callback has just been handed, in
  * their order.  Valid only during that callback, with the first_stream it was called with (the group's context is decoding nothing else
  * meanwhile and the calls are serialised: no race).  Returns the count; 0 with *levels = NULL for any other first_stream or without

@@ -174,7 +174,7 @@ class BatchStats(ctypes.Structure):
 
 
 EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_batch_last_error", "wmbus_batch_contexts", "wmbus_batch_context", "wmbus_batch_stage",
-           "wmbus_batch_device_input", "wmbus_batch_run",
+           "wmbus_batch_device_input", "wmbus_batch_run", "wmbus_batch_lane_stats",
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
            "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
@@ -246,6 +246,9 @@ def lib():
         L.wmbus_batch_close.argtypes = [vp]
         L.wmbus_batch_last_error.argtypes = [vp]; L.wmbus_batch_last_error.restype = ctypes.c_char_p
         L.wmbus_batch_contexts.argtypes = [vp]; L.wmbus_batch_contexts.restype = u
+        if hasattr(L, "wmbus_batch_lane_stats"):            # an A/B against a build from before lanes (WMBUS_HIP_LIB) still loads
+            L.wmbus_batch_lane_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+            L.wmbus_batch_lane_stats.restype = ctypes.c_int
         L.wmbus_batch_context.argtypes = [vp, u, ctypes.POINTER(u), ctypes.POINTER(u)]; L.wmbus_batch_context.restype = vp
         L.wmbus_batch_stage.argtypes = [vp, u, vp, sz]
         L.wmbus_batch_device_input.argtypes = [vp, u]; L.wmbus_batch_device_input.restype = vp
@@ -482,6 +485,13 @@ class Batch:
     def stage(self, stream, cu8):
         cu8 = np.ascontiguousarray(cu8, dtype=np.uint8)
         self._chk(lib().wmbus_batch_stage(self._h, stream, cu8.ctypes.data, cu8.size))
+
+    def lane_stats(self):
+        """wmbus_batch_lane_stats: the batch's lanes (contexts that share a hardware queue are driven as one lane, two at most) and the
+        kernel launches of the last run that carried two contexts (`paired`) or one (`single`)."""
+        lanes, paired, single = ctypes.c_uint(), ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        self._chk(lib().wmbus_batch_lane_stats(self._h, ctypes.byref(lanes), ctypes.byref(paired), ctypes.byref(single)))
+        return dict(lanes=lanes.value, paired=paired.value, single=single.value)
 
     def run_resident(self, nbytes, passes, on_push=None, want_lines=True):
         """Every context makes `passes` pushes of the `nbytes` staged per stream.  on_push(first_stream, n_streams,

@@ -30,12 +30,15 @@
 #include "wm_decoder.h"
 #include "wm_dev.h"
 #include "wm_kernels.hip"
+#include "wm_lane_merge.h"
 #include "wm_resample_design.h"
 #include "wm_spectrum_channels.h"
 
 namespace {
 
 class WorkerPool;              /* wm_host_decode.h */
+struct WmLaneRec;              /* wm_launch.h */
+thread_local hipStream_t wm_open_on_stream = nullptr;      /* wmbus_batch_open: the context this thread opens next runs on its lane mate's stream */
 
 struct HostDecoder {           /* persistent across pushes */
     wm_decoder dec;
@@ -81,7 +84,10 @@ enum { EV_PUSH, EV_K1, EV_K1_END, EV_CLK, EV_RLA, EV_FR_END, EV_K3, EV_K3_END, E
 struct wmbus_ctx {
     wmbus_cfg cfg{};
     char err[256] = {0};
-    hipStream_t stream = nullptr;                      /* every kernel of the context */
+    hipStream_t stream = nullptr;                      /* every kernel of the context (inside a batch lane: the lane's stream, wm_batch.h) */
+    bool stream_owned = true;                          /* false: the stream is the lane mate's, which closes behind this context */
+    WmLaneRec *rec = nullptr;                          /* a batch lane is recording this half of the push: operations are listed, not issued (wm_launch.h) */
+    unsigned long long n_single = 0;                   /* kernel launches that left singly (wmbus_batch_lane_stats) */
     hipStream_t copy_stream = nullptr;                 /* wmbus_stage's H2D copies (north_star: "pinned hipMemcpyAsync on a side stream") */
     hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t ev_staged = nullptr;                    /* recorded on copy_stream at process(): the push's input is in HBM */
@@ -286,6 +292,8 @@ int fail(wmbus_ctx *c, int code, const char *fmt, ...)
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
     return fail((c), WMBUS_EDEVICE, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
+#include "wm_launch.h"
+
 /* Hand-off verification runs a few rounds WITHOUT asking the host: verify -> re-run list on the device -> list launch
  * with a fixed grid -> verify ..., each round with its own counter; the host only looks at the last counters when it
  * collects the push and finishes the (rare) leftovers round by round. */
@@ -400,7 +408,7 @@ int k1_resolve(wmbus_ctx *c)
 int launch_k1(wmbus_ctx *c, K1Role role, const K1Args &a, dim3 grid)
 {
     const K1Entry &e = c->k1[role];
-    hipLaunchKernelGGL(e.kernel, grid, dim3(e.threads), e.lds, c->stream, a);
+    wm_launch(c, e.kernel, grid, dim3(e.threads), e.lds, a);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -442,9 +450,49 @@ __global__ void __launch_bounds__(256) k_selftest_fir(const float *x, float *out
 struct K1Chain { std::mutex m; hipEvent_t last = nullptr; const wmbus_ctx *owner = nullptr; };
 K1Chain k1_chain[WM_MAX_DEVICES];
 
+/* A context's turn in that chain: taken in front of its K1 launches, handed on behind them.  Outside a batch lane the chain's
+ * mutex is held across the launches, for the life of this object.  A lane RECORDS the push (wm_launch.h), so the turn is
+ * taken and handed on by two recorded operations, when the launches are issued and not when they are listed; the lane's
+ * merge keeps the operations between them together (wm_lane_merge.h).  wm_turn_held: the chain this thread holds between
+ * those two operations -- the lane lets go of it if an operation in between fails. */
+thread_local K1Chain *wm_turn_held = nullptr;
+struct K1Turn {
+    wmbus_ctx *const c; K1Chain &kc; bool locked = false;
+    K1Turn(wmbus_ctx *c_, K1Chain &kc_) : c(c_), kc(kc_) {}
+    ~K1Turn() { if (locked) kc.m.unlock(); }
+    int take()
+    {
+        wmbus_ctx *const cc = c; K1Chain *const k = &kc;
+        if (!c->rec) {
+            kc.m.lock(); locked = true;
+            if (kc.last && kc.owner != c) HIPCHK(c, hipStreamWaitEvent(c->stream, kc.last, 0));
+            return 0;
+        }
+        return wm_op(c, "taking the K1 turn", [=]() -> hipError_t {
+            if (wm_turn_held) return hipErrorInvalidValue;          /* the merge never interleaves two turns */
+            k->m.lock(); wm_turn_held = k;
+            return k->last && k->owner != cc ? hipStreamWaitEvent(cc->stream, k->last, 0) : hipSuccess;
+        });
+    }
+    int hand_on(hipEvent_t ev)
+    {
+        wmbus_ctx *const cc = c; K1Chain *const k = &kc;
+        if (!c->rec) { kc.last = ev; kc.owner = c; return 0; }
+        return wm_op(c, "handing on the K1 turn", [=]() -> hipError_t {
+            if (wm_turn_held != k) return hipErrorInvalidValue;
+            k->last = ev; k->owner = cc;
+            wm_turn_held = nullptr; k->m.unlock();
+            return hipSuccess;
+        });
+    }
+};
+
 /* One HIP stream per receiver context (two with cfg.input_windows = 2); ROCm maps streams onto GPU_MAX_HW_QUEUES hardware
  * queues (4 by default) round robin, and streams that share a queue serialise against each other: eight contexts on four
- * queues run at 81 instead of 143 Gsamples/s, ten on eight at 107 (r03 A/B).  The runtime reads the variable when it
+ * queues run at 81 instead of 143 Gsamples/s, ten on eight at 107 (r03 A/B).  (That, and not the hosts' CPU quota, is also the
+ * 100-110 Gsamples/s of rounds 7-18: their hosts preset four queues, and a caller's setting wins.  Since round 19 a batch with
+ * fewer queues than contexts drives neighbouring contexts as one lane on one stream, with paired launches -- wm_batch.h -- and
+ * runs at the rate of a queue per context: 174 against 102)  The runtime reads the variable when it
  * initialises (the first HIP call of the process), so wmbus_runtime_init() (include/wmbus_hip.h) must run before that:
  * wmbus_batch_open calls it, the CLI calls it first thing, an embedder that uses HIP itself calls it (or sets the
  * variable) before its own first HIP call -- a caller's own setting wins.  (Rounds 2-3 did this in a load-time constructor:
@@ -601,7 +649,7 @@ void wmbus_close(wmbus_ctx *c)
     for (auto &e : c->ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : {c->ev_staged, c->ev_turn}) if (e) hipEventDestroy(e);
     if (c->copy_stream && c->copy_stream != c->stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
-    if (c->stream) hipStreamDestroy(c->stream);
+    if (c->stream && c->stream_owned) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -847,7 +895,10 @@ static int open_allocate(wmbus_ctx *c)
     const uint64_t rows = 2ull * c->S;
     hipError_t e = hipSuccess;
     auto A = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    A(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    /* the second context of a batch lane runs on its mate's stream (wm_batch.h): a stream of its own would take a place on a
+     * hardware queue, beside some other lane's, for nothing */
+    if (wm_open_on_stream) { c->stream = wm_open_on_stream; c->stream_owned = false; }
+    else A(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     /* the side stream for wmbus_stage's copies exists where it can overlap something: with two input windows.  (Every
      * stream takes a hardware queue -- ROCm maps streams onto GPU_MAX_HW_QUEUES of them round robin -- and two contexts'
      * compute streams that end up on one queue serialise: an idle copy stream per context halved the 8-context rate.) */
@@ -1114,8 +1165,8 @@ static void *st_carry(wmbus_ctx *c, int algo, bool out)
 static void ema_verify(wmbus_ctx *c, uint32_t cnt)
 {
     const uint32_t rows = 2 * c->S, ntiles = c->ntiles;
-    hipLaunchKernelGGL(k1_verify, dim3((rows + 63) / 64, ntiles), dim3(64), 0, c->stream, c->d_ema_head, c->d_ema_tail, ema_carry(c, false), ntiles, rows, c->d_first_bad);
-    hipLaunchKernelGGL(k1_collect, dim3((rows + 63) / 64), dim3(64), 0, c->stream, c->d_first_bad, ntiles, rows, c->S, c->d_list_ema, c->d_scalars + cnt);
+    wm_launch(c, k1_verify, dim3((rows + 63) / 64, ntiles), dim3(64), 0, c->d_ema_head, c->d_ema_tail, ema_carry(c, false), ntiles, rows, c->d_first_bad);
+    wm_launch(c, k1_collect, dim3((rows + 63) / 64), dim3(64), 0, c->d_first_bad, ntiles, rows, c->S, c->d_list_ema, c->d_scalars + cnt);
 }
 
 static int ema_repair(wmbus_ctx *c, uint32_t cnt)          /* list launch: a fixed grid walks d_list[0 .. scalar cnt) */
@@ -1127,7 +1178,7 @@ static int ema_repair(wmbus_ctx *c, uint32_t cnt)          /* list launch: a fix
 
 static void ema_commit(wmbus_ctx *c)
 {
-    hipLaunchKernelGGL(k1_commit, dim3((2 * c->S + 63) / 64), dim3(64), 0, c->stream, c->d_ema_tail, ema_carry(c, true), c->ntiles, 2 * c->S);
+    wm_launch(c, k1_commit, dim3((2 * c->S + 63) / 64), dim3(64), 0, c->d_ema_tail, ema_carry(c, true), c->ntiles, 2 * c->S);
 }
 
 /* Does the launch that reads the re-run list whose length is scalar `cnt` walk chains (K2Args.bad), or re-run every listed segment on its own?
@@ -1142,14 +1193,13 @@ static void fr_verify(wmbus_ctx *c, int algo, uint32_t cnt)
     const Framer &f = c->fr[algo];
     const K2Args &a = f.k2;
     const uint32_t lanes = 2u * a.g.nseg[algo] * a.g.S;
-    hipLaunchKernelGGL(k2_verify, dim3((lanes + 255) / 256), dim3(256), 0, c->stream, a.g, (uint32_t)algo, (const uint32_t *)a.st_start,
+    wm_launch(c, k2_verify, dim3((lanes + 255) / 256), dim3(256), 0, a.g, (uint32_t)algo, (const uint32_t *)a.st_start,
                        (const uint32_t *)a.st_final, f.state_bytes / 4u, f.d_list, c->d_scalars + cnt, f.d_bad, list_walks_chains(c, algo, cnt) ? 1u : 0u);
 }
 
 /* one framer's kernel alone: every lane (cnt == ~0) or the re-run list whose length is scalar `cnt` */
 static void fr_launch(wmbus_ctx *c, int algo, uint32_t cnt)
 {
-    const hipStream_t st = c->stream;
     K2Args a = c->fr[algo].k2;
     const uint32_t lanes = 2u * a.g.nseg[algo] * a.g.S;
     const bool all = cnt == 0xFFFFFFFFu;
@@ -1184,7 +1234,14 @@ static void fr_launch(wmbus_ctx *c, int algo, uint32_t cnt)
     else k = dc ? (coop ? k2_clock_sys<true, true> : k2_clock_sys<true, false>) : (coop ? k2_clock_sys<false, true> : k2_clock_sys<false, false>);
     const uint32_t B = sys ? 256u : 64u * (algo == WMBUS_ALGO_RLA ? WM_RLA_WPB : WM_CLK_WPB), per = sys ? 64u : B;      /* threads, lanes per block */
     const uint32_t grid = all ? (lanes + per - 1u) / per : std::max(sys ? 64u : 16u, (lanes / per) * 3u / 16u);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(B), sys ? sizeof(ClkSysLds) : 0, st, a);
+    /* the form a batch lane launches for two contexts at once (wm_k_pair.h): the run-length framer's and the systolic clock kernel's */
+    void (*kp)(WmPair<K2Args>) = nullptr;
+    if (algo == WMBUS_ALGO_RLA) kp = all ? k2_rla_pair : k2_rla_list_pair;
+    else if (sys && !all) kp = dc ? k2_clock_sys_list_pair<true> : k2_clock_sys_list_pair<false>;
+    else if (sys) kp = dc ? (coop ? k2_clock_sys_pair<true, true> : k2_clock_sys_pair<true, false>) : (coop ? k2_clock_sys_pair<false, true> : k2_clock_sys_pair<false, false>);
+    const uint32_t lds = sys ? (uint32_t)sizeof(ClkSysLds) : 0u;
+    if (!kp) { wm_launch(c, k, dim3(grid), dim3(B), lds, a); return; }
+    wm_launch_pairable(c, [=](hipStream_t st) { hipLaunchKernelGGL(k, dim3(grid), dim3(B), lds, st, a); }, kp, dim3(grid), B, lds, a);
 }
 
 static void fr_carry(wmbus_ctx *c)
@@ -1194,10 +1251,14 @@ static void fr_carry(wmbus_ctx *c)
         const Framer &f = c->fr[al];
         const WmPush &g = f.k2.g;
         if (al == WMBUS_ALGO_T2A || (c->flags & WM_F_RLA))
-            hipLaunchKernelGGL(k_carry, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)f.k2.st_final,
+            wm_launch(c, k_carry, dim3((rows + 255) / 256), dim3(256), 0, (const uint32_t *)f.k2.st_final,
                                (uint32_t *)st_carry(c, al, true), f.state_bytes / 4u, rows, g.nseg_cap[al], g.nseg[al]);
         else   /* a disabled run-length framer keeps its state */
-            hipMemcpyAsync(st_carry(c, al, true), st_carry(c, al, false), (size_t)rows * f.state_bytes, hipMemcpyDeviceToDevice, c->stream);
+        {
+            void *const dst = st_carry(c, al, true), *const src = st_carry(c, al, false);
+            const size_t n = (size_t)rows * f.state_bytes;
+            (void)wm_op(c, "hipMemcpyAsync", [=] { return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream); });
+        }
     }
 }
 
@@ -1207,18 +1268,23 @@ static int launch_k3(wmbus_ctx *c, bool again)
 {
     const WmPush &g = c->last;
     if (again) {                                             /* collect's slow path: the counters of the first attempt go */
-        HIPCHK(c, hipMemsetAsync(c->d_scalars + SC_NHITS, 0, 5 * sizeof(uint32_t), c->stream));          /* NHITS .. NBYTES */
-        HIPCHK(c, hipMemsetAsync(c->d_scalars + SC_CHIPS, 0, 6 * sizeof(uint32_t), c->stream));          /* CHIPS, RS_N, RS_FAIL */
+        wm_memset(c, c->d_scalars + SC_NHITS, 0, 5 * sizeof(uint32_t));          /* NHITS .. NBYTES */
+        wm_memset(c, c->d_scalars + SC_CHIPS, 0, 6 * sizeof(uint32_t));          /* CHIPS, RS_N, RS_FAIL */
         /* ... and so does its burst-storage warning (chips dropped by the framers stay dropped: that bit is kept) */
-        hipLaunchKernelGGL(k_and_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_ERR, ~(uint32_t)WM_ERR_BURST_OVERFLOW);
+        wm_launch(c, k_and_word, dim3(1), dim3(1), 0, c->d_scalars + SC_ERR, ~(uint32_t)WM_ERR_BURST_OVERFLOW);
     }
-    hipLaunchKernelGGL(k_sum_counts, dim3(std::min(64u, (2u * (c->fr[0].nseg_cap + c->fr[1].nseg_cap) * c->S + 255u) / 256u)), dim3(256), 0, c->stream, g,
+    wm_launch(c, k_sum_counts, dim3(std::min(64u, (2u * (c->fr[0].nseg_cap + c->fr[1].nseg_cap) * c->S + 255u) / 256u)), dim3(256), 0, g,
                        c->fr[0].d_counts, c->fr[1].d_counts, c->d_scalars + SC_CHIPS);
     /* grid.y: the parts a region is scanned in -- the run-length framer's regions can be longer than their capacity (spill chunks) */
     const uint32_t scan_parts = (std::max(g.cap[0] + WM_SPILL_LEVELS * WM_SPILL_CHUNK, g.cap[1]) + WM_K3_SCAN_PART - 1u) / WM_K3_SCAN_PART;
-    hipLaunchKernelGGL(k3_scan, dim3((2u * (g.nseg[0] + g.nseg[1]) * g.S + 255u) / 256u, scan_parts), dim3(256), 0, c->stream, g, c->fr[0].d_chips, c->fr[1].d_chips,
-                       c->fr[0].d_counts, c->fr[1].d_counts, c->fr[0].d_sync_seen, c->fr[1].d_sync_seen, c->d_hits, c->d_scalars + SC_NHITS,
-                       c->hits_cap, c->d_scalars + SC_ERR);
+    {
+        const K3ScanArgs sa{g, c->fr[0].d_chips, c->fr[1].d_chips, c->fr[0].d_counts, c->fr[1].d_counts, c->fr[0].d_sync_seen, c->fr[1].d_sync_seen, c->d_hits,
+                            c->d_scalars + SC_NHITS, c->hits_cap, c->d_scalars + SC_ERR};
+        const dim3 grid((2u * (g.nseg[0] + g.nseg[1]) * g.S + 255u) / 256u, scan_parts);
+        wm_launch_pairable(c, [=](hipStream_t st) {
+            hipLaunchKernelGGL(k3_scan, grid, dim3(256), 0, st, sa.g, sa.chips0, sa.chips1, sa.counts0, sa.counts1, sa.seen0, sa.seen1, sa.hits, sa.n_hits, sa.hits_cap, sa.err);
+        }, k3_scan_pair, grid, 256u, 0u, sa);
+    }
     K3Args k3{};
     k3.g = g; k3.rssi = c->d_rssi;
     for (int al = 0; al < 2; al++) { k3.chips[al] = c->fr[al].d_chips; k3.counts[al] = c->fr[al].d_counts; }
@@ -1234,20 +1300,28 @@ static int launch_k3(wmbus_ctx *c, bool again)
         k3.plans = c->d_plans;
         /* RSSI on demand: which tiles do the bursts touch (k3_spans), then their RSSI (an RS = 2 launch of the demodulation
          * kernel over the list, a fixed grid), then the bursts */
-        HIPCHK(c, hipMemsetAsync(c->d_rs_flags, 0, (size_t)c->ntiles * c->S * sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(k3_spans, dim3(std::max(1u, std::min((4 * c->S + c->hits_cap + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, k3, c->T, c->ntiles,
-                           c->d_rs_flags, c->d_rs_list, c->d_scalars + SC_RS_N);
+        wm_memset(c, c->d_rs_flags, 0, (size_t)c->ntiles * c->S * sizeof(uint32_t));
+        {
+            const K3SpansArgs sp{k3, c->T, c->ntiles, c->d_rs_flags, c->d_rs_list, c->d_scalars + SC_RS_N};
+            const dim3 grid(std::max(1u, std::min((4 * c->S + c->hits_cap + 3u) / 4u, (uint32_t)WM_K3_BLOCKS)));
+            wm_launch_pairable(c, [=](hipStream_t st) { hipLaunchKernelGGL(k3_spans, grid, dim3(256), 0, st, sp.a, sp.tile_len, sp.ntiles, sp.flags, sp.list, sp.n_list); },
+                               k3_spans_pair, grid, 256u, 0u, sp);
+        }
         K1Args k1 = c->k1a;
         k1.relist = c->d_rs_list; k1.n_relist = c->d_scalars + SC_RS_N;
-        HIPCHK(c, hipEventRecord(c->ev[EV_RS], c->stream));
+        wm_record(c, c->ev[EV_RS]);
         const int rc = launch_k1(c, K1_RSSI, k1, dim3(std::max(1u, std::min((uint32_t)WM_RS_BLOCKS, c->ntiles * c->S)), 1));    /* r04 A/B: 512 / 1024 / 2048 / 4096 blocks: no difference */
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev[EV_RS_END], c->stream));
+        wm_record(c, c->ev[EV_RS_END]);
     }
     /* Few blocks: a latency-bound wave parked on a SIMD costs the demodulation kernel one of its eight wave slots there
      * for as long as it lives; 256 blocks put one on every SIMD of the chip (r02 sweep: 256 -> 64 blocks + 6 %, 16 blocks - 9 %: then the kernel itself becomes the longest link of the chain) */
     const uint32_t most = 4 * c->S + c->hits_cap;
-    hipLaunchKernelGGL(k3_bursts, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, k3, 0xFFFFFFFFu);
+    {
+        const K3BurstsArgs ba{k3, 0xFFFFFFFFu};
+        const dim3 grid(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS)));
+        wm_launch_pairable(c, [=](hipStream_t st) { hipLaunchKernelGGL(k3_bursts, grid, dim3(256), 0, st, ba.a, ba.n_items_host); }, k3_bursts_pair, grid, 256u, 0u, ba);
+    }
     if (c->lev_on) {
         /* cfg.line_levels: a level per record k3_bursts has written (it left every record's access-code sample in d_lev_src_*), from this push's soft symbols and the tail in front of them; then the
          * tail for the next push (into the other half: collect's slow path comes through here again and must find the same tail) */
@@ -1257,21 +1331,21 @@ static int launch_k3(wmbus_ctx *c, bool again)
         lv.src_pkts = k3.pkts ? k3.lev_pkt : nullptr; lv.n_pkts = k3.n_pkts; lv.pkts_cap = k3.pkts_cap;
         lv.src_hdr = k3.lev_hdr; lv.n_hdr = k3.n_hdr; lv.hdr_cap = k3.hdr_cap;
         lv.lev_pkts = (WmLevel *)c->dv_lev_pkts; lv.lev_hdr = (WmLevel *)c->dv_lev_hdr;
-        hipLaunchKernelGGL(k3_levels, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, lv);
-        hipLaunchKernelGGL(k3_level_tail, dim3((WM_LEV_TAIL + 255u) / 256u, 2u * c->S), dim3(256), 0, c->stream, lv);
+        wm_launch(c, k3_levels, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, lv);
+        wm_launch(c, k3_level_tail, dim3((WM_LEV_TAIL + 255u) / 256u, 2u * c->S), dim3(256), 0, lv);
         if (c->rep_on && k3.pkts) {
             /* cfg.crc_repair: behind the bursts and the levels, on the packets k3_bursts has just written (in place: their flags, their
              * bytes), with the same soft symbols and the same tail as the levels; a record per packet slot beside them */
             K3RepArgs ra{};
             ra.k3 = k3; ra.dphi = lv.dphi; ra.tail_in = lv.tail_in; ra.src_pkts = k3.lev_pkt; ra.rep_pkts = (WmRepair *)c->dv_rep_pkts;
-            hipLaunchKernelGGL(k3_repair, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, ra);
+            wm_launch(c, k3_repair, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, ra);
         }
         if (c->q_on && k3.pkts) {
             /* cfg.line_quality: a record per packet slot from the chip regions, the counts and the soft symbols -- nothing k3_repair
              * changes, so its place behind it is a matter of order only */
             K3QualArgs qa{};
             qa.k3 = k3; qa.dphi = lv.dphi; qa.src_pkts = k3.lev_pkt; qa.q_pkts = (WmQuality *)c->dv_q_pkts;
-            hipLaunchKernelGGL(k3_quality, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, c->stream, qa);
+            wm_launch(c, k3_quality, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, qa);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -1356,8 +1430,8 @@ static int spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, ui
         const K0SpecAgePlan plan = k0_spec_age_plan(c->spec.K, n_blk, c->spec.age);
         a.age = c->spec.age; a.k_first = c->spec.K; a.e_keep = plan.e_keep; a.slot_stride = c->spec.slot_stride;
         c->spec.K += n_blk;
-        if (plan.clear == 3u) HIPCHK(c, hipMemsetAsync(c->spec.d_slots, 0, (size_t)2 * c->spec.slot_stride * sizeof(uint64_t), c->stream));
-        else if (plan.clear) HIPCHK(c, hipMemsetAsync(c->spec.d_slots + (plan.clear >> 1) * c->spec.slot_stride, 0, (size_t)c->spec.slot_stride * sizeof(uint64_t), c->stream));
+        if (plan.clear == 3u) wm_memset(c, c->spec.d_slots, 0, (size_t)2 * c->spec.slot_stride * sizeof(uint64_t));
+        else if (plan.clear) wm_memset(c, c->spec.d_slots + (plan.clear >> 1) * c->spec.slot_stride, 0, (size_t)c->spec.slot_stride * sizeof(uint64_t));
     }
     if (c->pw.on) {
         /* the one place where a push's level blocks enter the waterfall: K moves on here and nowhere else */
@@ -1366,7 +1440,7 @@ static int spec_launch(wmbus_ctx *c, const uint8_t *raw, uint64_t raw_stride, ui
         c->pw.last_first = c->pw.K; c->pw.last_blk = n_blk; c->pw.K += n_blk;
     }
     const uint32_t runs = (n_blk + a.run - 1u) / a.run;
-    hipLaunchKernelGGL(c->pw.on ? banded[c->spec.age != 0u][c->k0.dc != 0u][c->k0.fmt] : (c->spec.age ? aged : kernel)[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, c->stream, a);
+    wm_launch(c, c->pw.on ? banded[c->spec.age != 0u][c->k0.dc != 0u][c->k0.fmt] : (c->spec.age ? aged : kernel)[c->k0.dc != 0u][c->k0.fmt], dim3((runs + WM_K0_SPEC_WAVES - 1u) / WM_K0_SPEC_WAVES, c->NC), dim3(64u * WM_K0_SPEC_WAVES), 0, a);
     return WMBUS_OK;
 }
 
@@ -1386,19 +1460,22 @@ static int power_launch(wmbus_ctx *c)
     else a.centre_hz[0] = c->cfg.input_shift_hz;
     if (c->cfg.simultaneous) { a.chain_hz[WMBUS_CHAIN_T1C1] = WM_K0_POW_SIM_HZ; a.chain_hz[WMBUS_CHAIN_S1] = -WM_K0_POW_SIM_HZ; }
     w.args = a;
-    hipLaunchKernelGGL(k0_channel_power, dim3((n_blk + WM_K0_POW_THREADS / 32u - 1u) / (WM_K0_POW_THREADS / 32u), c->S, 2u), dim3(WM_K0_POW_THREADS), 0, c->stream, a);
+    wm_launch(c, k0_channel_power, dim3((n_blk + WM_K0_POW_THREADS / 32u - 1u) / (WM_K0_POW_THREADS / 32u), c->S, 2u), dim3(WM_K0_POW_THREADS), 0, a);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpy2DAsync(w.h_P, (size_t)w.blk_cap * sizeof(uint32_t), w.d_P, (size_t)w.blk_cap * sizeof(uint32_t), (size_t)n_blk * sizeof(uint32_t), (size_t)2 * c->S,
-                               hipMemcpyDeviceToHost, c->stream));
+    {
+        uint32_t *const h_P = w.h_P, *const d_P = w.d_P;
+        const size_t pitch = (size_t)w.blk_cap * sizeof(uint32_t), width = (size_t)n_blk * sizeof(uint32_t), rows = (size_t)2 * c->S;
+        WM_OP(c, "hipMemcpy2DAsync", [=] { return hipMemcpy2DAsync(h_P, pitch, d_P, pitch, width, rows, hipMemcpyDeviceToHost, c->stream); });
+    }
     if (c->act.on) {
         /* cfg.channel_activity: the rows' state moves on over this push's P, here and nowhere else -- once per push, as pw.K does */
         K0ActArgs ca{};
         ca.P = w.d_P; ca.p_stride = w.blk_cap; ca.n_blk = n_blk; ca.rows = 2u * c->S;
         ca.T = c->act.T; ca.H = c->act.H;
         ca.st = c->act.d_state; ca.arena = c->act.d_arena; ca.count = c->act.d_count; ca.base = c->act.taken; ca.cap = c->act.cap;
-        hipLaunchKernelGGL(k0_activity, dim3(2u * c->S), dim3(64u), 0, c->stream, ca);
+        wm_launch(c, k0_activity, dim3(2u * c->S), dim3(64u), 0, ca);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->act.h_count, c->act.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        wm_memcpy(c, c->act.h_count, c->act.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
         c->act.launched = true;
     }
     return WMBUS_OK;
@@ -1437,17 +1514,17 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
     if (c->k0.dc) {                                      /* the level blocks' sums, then the recurrence over them: the table the K0 kernel subtracts */
         void (*const sums[4])(K0DcArgs) = {k0_dc_sums<WM_K0_CU8>, k0_dc_sums<WM_K0_CS8>, k0_dc_sums<WM_K0_CS16>, k0_dc_sums<WM_K0_CF32>};
         const K0DcArgs &da = c->k0.dca;
-        hipLaunchKernelGGL(sums[c->k0.fmt], dim3((da.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, da);
-        hipLaunchKernelGGL(k0_dc_plan, dim3(c->NC), dim3(128), 0, c->stream, da);
+        wm_launch(c, sums[c->k0.fmt], dim3((da.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, da);
+        wm_launch(c, k0_dc_plan, dim3(c->NC), dim3(128), 0, da);
         c->k0.last_dc_blocks = da.n_blk;
     }
     if (c->spec.on) { const int rc = spec_launch(c, ka.raw, ka.raw_stride, ka.n_in >> WM_K0_DC_LOG2); if (rc) return rc; }      /* per capture, in front of the rotation, behind the blocker's table */
     /* cfg.input_afc: every capture's {step, base} for this push from its max-hold as it stands now, and the state commit, in ONE short launch */
-    if (c->afc.on) hipLaunchKernelGGL(k0_afc_plan, dim3(c->NC, c->afc.chan ? c->CH : 1u), dim3(WM_K0_AFC_THREADS), 0, c->stream, c->afc.args);
+    if (c->afc.on) wm_launch(c, k0_afc_plan, dim3(c->NC, c->afc.chan ? c->CH : 1u), dim3(WM_K0_AFC_THREADS), 0, c->afc.args);
     if (c->pw.on) { const int rc = power_launch(c); if (rc) return rc; }
     if (c->k0.agc) {                                     /* every level block's gain from its peak, behind the blocker: the table the K0 kernel's output stage reads */
         const K0AgcArgs &ga = c->k0.aga;
-        hipLaunchKernelGGL(gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, c->stream, ga);
+        wm_launch(c, gain[c->k0.dc != 0u][c->k0.fmt], dim3((ga.n_blk + WM_K0_THREADS / 64u - 1u) / (WM_K0_THREADS / 64u), c->NC), dim3(WM_K0_THREADS), 0, ga);
         c->k0.last_dc_blocks = ga.n_blk;
     }
     const auto &stage = c->k0.agc ? (c->k0.resample ? resample_agc : convert_agc) : (c->k0.resample ? resample : convert);
@@ -1455,8 +1532,7 @@ static int k0_launch(wmbus_ctx *c, const K0Args &ka)
                                    : c->afc.on  ? (c->k0.resample ? resample_afc : convert_afc)[c->k0.fmt]
                                    : c->k0.chan ? (c->k0.resample ? resample_ch : convert_ch)[c->k0.fmt]
                                               : stage[c->k0.dc != 0u][c->k0.shift][c->k0.fmt];
-    hipLaunchKernelGGL(kernel, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS),
-                       c->k0.resample ? c->k0.lds : 0u, c->stream, ka);
+    wm_launch(c, kernel, dim3((ka.n_out + ka.tile - 1u) / ka.tile, c->S), dim3(WM_K0_THREADS), c->k0.resample ? c->k0.lds : 0u, ka);
     HIPCHK(c, hipGetLastError());
     c->k0.launches++;
     return WMBUS_OK;
@@ -1495,19 +1571,19 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
 
     /* the staged bytes arrive on the copy stream */
     if (c->copy_stream != c->stream) {
-        HIPCHK(c, hipEventRecord(c->ev_staged, c->copy_stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+        WM_OP(c, "hipEventRecord(ev_staged, copy_stream)", [=] { return hipEventRecord(c->ev_staged, c->copy_stream); });
+        wm_wait(c, c->ev_staged);
     }
-    HIPCHK(c, hipEventRecord(c->ev[EV_PUSH], c->stream));
-    hipLaunchKernelGGL(k_copy_hist, dim3(c->S), dim3(256), 0, c->stream, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint64_t)0, win, c->in_stride);
+    wm_record(c, c->ev[EV_PUSH]);
+    wm_launch(c, k_copy_hist, dim3(c->S), dim3(256), 0, c->d_hist, (uint64_t)WM_HIST_BYTES, (uint64_t)0, win, c->in_stride);
     if (c->k0.on && g.M == 0) {                          /* a push that completes no block: K0 alone, and its clip count */
-        HIPCHK(c, hipMemsetAsync(c->d_scalars + SC_CLIP, 0, sizeof(uint32_t), c->stream));
+        wm_memset(c, c->d_scalars + SC_CLIP, 0, sizeof(uint32_t));
         const int rc0 = k0_launch(c, k0a);
         if (rc0) return rc0;
-        HIPCHK(c, hipMemcpyAsync(c->h_scalars + SC_CLIP, c->d_scalars + SC_CLIP, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        wm_memcpy(c, c->h_scalars + SC_CLIP, c->d_scalars + SC_CLIP, sizeof(uint32_t), hipMemcpyDeviceToHost);
     }
     if (g.M > 0) {
-        HIPCHK(c, hipMemsetAsync(c->d_scalars, 0, c->zero_words * sizeof(uint32_t), c->stream));     /* scalars, region flags, spill chains */
+        wm_memset(c, c->d_scalars, 0, c->zero_words * sizeof(uint32_t));     /* scalars, region flags, spill chains */
         /* K1 */
         const uint32_t T = c->T, ntiles = (g.M + T - 1) / T;
         c->ntiles = ntiles;
@@ -1522,10 +1598,9 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
                         nullptr, ema_carry(c, false), nullptr, 0u, c->d_rs_flags, ema_carry(c, true), c->d_scalars + SC_RS_FAIL};
         int rc;
         {
-            K1Chain &kc = k1_chain[c->cfg.device];
-            std::lock_guard<std::mutex> lk(kc.m);
-            if (kc.last && kc.owner != c) HIPCHK(c, hipStreamWaitEvent(c->stream, kc.last, 0));
-            HIPCHK(c, hipEventRecord(c->ev[EV_K1], c->stream));
+            K1Turn turn(c, k1_chain[c->cfg.device]);
+            if ((rc = turn.take())) return rc;
+            wm_record(c, c->ev[EV_K1]);
             if (c->k0.on) { rc = k0_launch(c, k0a); if (rc) return rc; }      /* inside demod_ms: the demodulation kernel reads what it writes */
             /* the survey of a context on the plain cu8 path reads the device input window itself (a push of that path is whole 4096-byte
              * blocks and always has decimated samples: this branch is taken); the context stays on the plain path */
@@ -1559,13 +1634,13 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
             rc = dbg_skip ? 0 : launch_k1(c, role, k1, dim3((nt1 - n_tail + tpb - 1u) / tpb, c->S));
             if (rc) return rc;
             if (n_tail && !dbg_skip) {
-                HIPCHK(c, hipEventRecord(c->ev_turn, c->stream));
+                wm_record(c, c->ev_turn);
                 k1.tile0 = nt1 - n_tail; k1.tile_end = nt1;
                 rc = launch_k1(c, role, k1, dim3((n_tail + tpb - 1u) / tpb, c->S));
                 if (rc) return rc;
             }
-            HIPCHK(c, hipEventRecord(c->ev[EV_K1_END], c->stream));
-            kc.last = n_tail ? c->ev_turn : c->ev[EV_K1_END]; kc.owner = c;
+            wm_record(c, c->ev[EV_K1_END]);
+            if ((rc = turn.hand_on(n_tail ? c->ev_turn : c->ev[EV_K1_END]))) return rc;
         }
         /* Everything behind K1 is enqueued while it runs -- no step of a push waits for the host any more:
          * hand-off verification makes its first rounds on the device (counters per round), K3 reads its item
@@ -1602,7 +1677,7 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
         const bool rla = c->flags & WM_F_RLA;
         for (int al = 1; al >= (rla ? 0 : 1); al--) {
             const Framer &f = c->fr[al];
-            HIPCHK(c, hipEventRecord(c->ev[al ? EV_CLK : EV_RLA], c->stream));
+            wm_record(c, c->ev[al ? EV_CLK : EV_RLA]);
             fr_launch(c, al, 0xFFFFFFFFu);                           /* the first pass */
             /* (a push of one segment per row has no hand-off inside it: its only lane starts from the carried state -- no rounds to enqueue;
              * a live stream's 2^16-sample pushes are such) */
@@ -1620,19 +1695,19 @@ static int enqueue_front_impl(wmbus_ctx *c, size_t nbytes)
                 fin.heads[al] = list_walks_chains(c, al, f.sc + f.rounds);
             }
             const uint32_t most = std::max(2u * g.S, 2u * std::max(g.nseg[0], g.nseg[1]) * g.S);
-            hipLaunchKernelGGL(k2_finish, dim3((most + 255u) / 256u), dim3(256), 0, c->stream, g, fin);
-            HIPCHK(c, hipEventRecord(c->ev[EV_FR_END], c->stream));
+            wm_launch(c, k2_finish, dim3((most + 255u) / 256u), dim3(256), 0, g, fin);
+            wm_record(c, c->ev[EV_FR_END]);
         } else {
-            HIPCHK(c, hipEventRecord(c->ev[EV_RLA], c->stream));
-            HIPCHK(c, hipMemsetAsync(c->fr[0].d_counts, 0, (size_t)2 * c->S * c->fr[0].nseg_cap * sizeof(uint32_t), c->stream));
+            wm_record(c, c->ev[EV_RLA]);
+            wm_memset(c, c->fr[0].d_counts, 0, (size_t)2 * c->S * c->fr[0].nseg_cap * sizeof(uint32_t));
             fr_verify(c, WMBUS_ALGO_T2A, c->fr[1].sc + c->fr[1].rounds);
-            HIPCHK(c, hipEventRecord(c->ev[EV_FR_END], c->stream));
+            wm_record(c, c->ev[EV_FR_END]);
             fr_carry(c);
         }
         c->committed = true;
     }
     /* the next push sees the last 4096 staged bytes in front of it */
-    hipLaunchKernelGGL(k_copy_hist, dim3(c->S), dim3(256), 0, c->stream, win, c->in_stride, (uint64_t)nbytes, c->d_hist, (uint64_t)WM_HIST_BYTES);
+    wm_launch(c, k_copy_hist, dim3(c->S), dim3(256), 0, win, c->in_stride, (uint64_t)nbytes, c->d_hist, (uint64_t)WM_HIST_BYTES);
     HIPCHK(c, hipGetLastError());
     c->fill = (c->fill + 1) % c->n_win;
     c->n0 += n_new;
@@ -1653,13 +1728,13 @@ static int enqueue_back_impl(wmbus_ctx *c)
             for (int ch = 0; ch < 2; ch++)
                 for (int al = 0; al < 2; al++)
                     c->h_pending[(al * 2 + ch) * c->S + s] = c->decs[((size_t)s * 2 + ch) * 2 + al].owed;
-        HIPCHK(c, hipMemcpyAsync(c->d_pending, c->h_pending, 4 * c->S * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev[EV_K3], c->stream));
+        wm_memcpy(c, c->d_pending, c->h_pending, 4 * c->S * sizeof(uint32_t), hipMemcpyHostToDevice);
+        wm_record(c, c->ev[EV_K3]);
         const int rc = launch_k3(c, false);
         if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->ev[EV_K3_END], c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev[EV_D2H_END], c->stream));
+        wm_record(c, c->ev[EV_K3_END]);
+        wm_memcpy(c, c->h_scalars, c->d_scalars, SC_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        wm_record(c, c->ev[EV_D2H_END]);
     }
     return WMBUS_OK;
 }
@@ -1697,7 +1772,7 @@ static int finish_slowly(wmbus_ctx *c, bool ema_left, bool left[2], bool rs_left
     };
     /* verify once more, counting in SC_SLOW (cleared behind whatever launch has just read it); algo < 0: the RSSI filter's hand-offs */
     auto recheck = [&](int algo, uint32_t *n) -> int {
-        hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + SC_SLOW, 0u);
+        wm_launch(c, k_copy_word, dim3(1), dim3(1), 0, c->d_scalars + SC_SLOW, 0u);
         if (algo < 0) ema_verify(c, SC_SLOW); else fr_verify(c, algo, SC_SLOW);
         const int rc = read_scalars();
         *n = c->h_scalars[SC_SLOW];
@@ -1737,7 +1812,7 @@ static int finish_slowly(wmbus_ctx *c, bool ema_left, bool left[2], bool rs_left
             /* the run-length framer ran on slicer words that the clock re-runs have just replaced: all of it again */
             const uint32_t last = c->fr[0].sc + c->fr[0].rounds;
             fr_launch(c, WMBUS_ALGO_RLA, 0xFFFFFFFFu);
-            hipLaunchKernelGGL(k_copy_word, dim3(1), dim3(1), 0, c->stream, c->d_scalars + last, 0u);
+            wm_launch(c, k_copy_word, dim3(1), dim3(1), 0, c->d_scalars + last, 0u);
             fr_verify(c, WMBUS_ALGO_RLA, last);
             if ((rc = read_scalars())) return rc;
             left[0] = c->h_scalars[last] != 0;

@@ -93,14 +93,14 @@ __device__ uint32_t burst_need(uint32_t chain, uint32_t hb, uint32_t nb) { retur
  * the flag of one (framer, chain, capture, segment) region, and the wave then scans the flagged
  * regions (a minority) together, appending {lane | algo << 31, chip index}. */
 #define WM_K3_SCAN_PART 4096       /* a multiple of 1024 (a trip of the wave) */
-__global__ __launch_bounds__(256) void k3_scan(WmPush g, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0,
-                                               const uint32_t *counts1, const uint32_t *seen0, const uint32_t *seen1,
-                                               uint2 *hits, uint32_t *n_hits, uint32_t hits_cap, uint32_t *err)
+/* block (bx, by) of the scan: the kernel's own block index, or the one a paired launch hands a context (wm_k_pair.h) */
+__device__ __forceinline__ void k3_scan_block(const WmPush &g, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0,
+                                              const uint32_t *counts1, const uint32_t *seen0, const uint32_t *seen1,
+                                              uint2 *hits, uint32_t *n_hits, uint32_t hits_cap, uint32_t *err, const uint32_t bx, const uint32_t by)
 {
-    wm_framer_prio();
     const uint32_t n0 = 2u * g.nseg[0] * g.S;                /* run-length lanes first */
     const uint32_t ln = threadIdx.x & 63u;
-    uint32_t lane = blockIdx.x * 256u + threadIdx.x, algo = 0;
+    uint32_t lane = bx * 256u + threadIdx.x, algo = 0;
     if (lane >= n0) { lane -= n0; algo = 1; }
     uint32_t my_cnt = 0, my_sidx = 0;
     if (lane < 2u * g.nseg[algo] * g.S) {
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void k3_scan(WmPush g, const uint32_t *chips0,
         /* a region is scanned in parts of WM_K3_SCAN_PART chips, one wave (blockIdx.y) per part: the scan of a flagged region is a chain
          * of dependent trips as long as the region, and the clock framer's regions grew with its segments (65 536 samples: 16 392 chips,
          * round 6 -- the launch went from 1.3 to 2.1 ms on its own) */
-        const uint32_t k_lo = blockIdx.y * (uint32_t)WM_K3_SCAN_PART, k_hi = min(cnt, k_lo + (uint32_t)WM_K3_SCAN_PART);
+        const uint32_t k_lo = by * (uint32_t)WM_K3_SCAN_PART, k_hi = min(cnt, k_lo + (uint32_t)WM_K3_SCAN_PART);
         for (uint32_t kb = k_lo + 4u * ln; kb < k_hi; kb += 1024u) {    /* regions and spill chunks are 32-byte aligned, cap % 8 == 0 */
             uint4 v[4];
 #pragma unroll
@@ -141,6 +141,14 @@ __global__ __launch_bounds__(256) void k3_scan(WmPush g, const uint32_t *chips0,
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k3_scan(WmPush g, const uint32_t *chips0, const uint32_t *chips1, const uint32_t *counts0,
+                                               const uint32_t *counts1, const uint32_t *seen0, const uint32_t *seen1,
+                                               uint2 *hits, uint32_t *n_hits, uint32_t hits_cap, uint32_t *err)
+{
+    wm_framer_prio();
+    k3_scan_block(g, chips0, chips1, counts0, counts1, seen0, seen1, hits, n_hits, hits_cap, err, blockIdx.x, blockIdx.y);
 }
 
 /* Per-wave scratch of k3_bursts: the burst's chips as a bit string (chip j = bit j % 64 of word j / 64) and the
@@ -415,14 +423,19 @@ __device__ void burst_item(const K3Args &a, const uint32_t item, const uint32_t 
  * -- 14 000 single-wave blocks per 128 captures, each a chain of dependent loads -- took every wave
  * slot of the chip for the kernel's duration and stalled the demodulation kernel of the next
  * context (measured: K1 ran at a quarter of its speed while this kernel was resident). */
+/* block bx of gx walking the items: the kernel's own block index and grid, or the ones a paired launch hands a context (wm_k_pair.h) */
+__device__ __forceinline__ void k3_bursts_block(const K3Args &a, uint32_t n_items_host, K3Lds &lds, const uint32_t bx, const uint32_t gx)
+{
+    const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    /* the host may not know the number of hits yet (no round trip between k3_scan and this kernel): ~0 = read it here */
+    const uint32_t n_items = n_items_host != 0xFFFFFFFFu ? n_items_host : 4u * a.g.S + min(*a.n_hits, a.hits_cap);
+    for (uint32_t item = bx * 4u + wv; item < n_items; item += gx * 4u) burst_item(a, item, ln, lds.bits[wv], lds.bytes[wv]);
+}
 __global__ __launch_bounds__(256) void k3_bursts(K3Args a, uint32_t n_items_host)
 {
     wm_framer_prio();
     __shared__ K3Lds lds;
-    const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    /* the host may not know the number of hits yet (no round trip between k3_scan and this kernel): ~0 = read it here */
-    const uint32_t n_items = n_items_host != 0xFFFFFFFFu ? n_items_host : 4u * a.g.S + min(*a.n_hits, a.hits_cap);
-    for (uint32_t item = blockIdx.x * 4u + wv; item < n_items; item += gridDim.x * 4u) burst_item(a, item, ln, lds.bits[wv], lds.bytes[wv]);
+    k3_bursts_block(a, n_items_host, lds, blockIdx.x, gridDim.x);
 }
 
 /* RSSI on demand (wm_k1_demod.h): the demodulation tiles whose RSSI bytes k3_bursts is going to read -- for every item
@@ -432,14 +445,14 @@ __device__ __forceinline__ void k3_mark(uint32_t *flags, uint32_t *list, uint32_
 {
     if (atomicOr(flags + (uint64_t)tile * S + stream, bits) == 0u) list[atomicAdd(n_list, 1u)] = stream * ntiles + tile;   /* at most one entry per (tile, capture) */
 }
-__global__ __launch_bounds__(256) void k3_spans(K3Args a, uint32_t tile_len, uint32_t ntiles, uint32_t *flags, uint32_t *list, uint32_t *n_list)
+__device__ __forceinline__ void k3_spans_block(const K3Args &a, uint32_t tile_len, uint32_t ntiles, uint32_t *flags, uint32_t *list, uint32_t *n_list,
+                                               const uint32_t bx, const uint32_t gx)
 {
-    wm_framer_prio();
     const WmPush &g = a.g;
     const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    for (uint32_t s = blockIdx.x * 256u + threadIdx.x; s < g.S; s += gridDim.x * 256u) k3_mark(flags, list, n_list, g.S, ntiles, ntiles - 1u, s, 3u);
+    for (uint32_t s = bx * 256u + threadIdx.x; s < g.S; s += gx * 256u) k3_mark(flags, list, n_list, g.S, ntiles, ntiles - 1u, s, 3u);
     const uint32_t n_items = 4u * g.S + min(*a.n_hits, a.hits_cap);
-    for (uint32_t item = blockIdx.x * 4u + wv; item < n_items; item += gridDim.x * 4u) {
+    for (uint32_t item = bx * 4u + wv; item < n_items; item += gx * 4u) {
         K3Item it;
         const bool todo = k3_item(a, item, ln, it);
         if (a.plans && ln == 0) a.plans[item] = todo ? WmItemRec{it.chip0, it.avail, it.n, it.plan} : WmItemRec{};
@@ -449,6 +462,11 @@ __global__ __launch_bounds__(256) void k3_spans(K3Args a, uint32_t tile_len, uin
         const uint32_t t0 = __shfl(pm, 0) / tile_len, t1 = min(__shfl(pm, 1) / tile_len, ntiles - 1u);
         for (uint32_t tl = t0 + ln; tl <= t1; tl += 64u) k3_mark(flags, list, n_list, g.S, ntiles, tl, it.stream, 1u << it.ch);
     }
+}
+__global__ __launch_bounds__(256) void k3_spans(K3Args a, uint32_t tile_len, uint32_t ntiles, uint32_t *flags, uint32_t *list, uint32_t *n_list)
+{
+    wm_framer_prio();
+    k3_spans_block(a, tile_len, ntiles, flags, list, n_list, blockIdx.x, gridDim.x);
 }
 
 /* Debug/parity helper: flatten one (chain, algo, stream) chip stream. */

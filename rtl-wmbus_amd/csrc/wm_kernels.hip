@@ -134,3 +134,4 @@ __global__ void k2_finish(WmPush g, K2Finish f)
 #include "wm_k3_levels.h"
 #include "wm_k3_repair.h"
 #include "wm_k3_quality.h"
+#include "wm_k_pair.h"

@@ -486,10 +486,14 @@ static int run_batch(struct batch_job *j)
         census_close(&j->census);
         pthread_mutex_unlock(&out_lock);
     }
-    if (j->stats)
-        fprintf(stderr, "rtl_wmbus_hip: device %d: %d files, %u contexts, %llu samples, %llu lines, %u pushes in %.3f s = %.1f Msamples/s\n", j->cfg.device, j->n,
-                wmbus_batch_contexts(b), (unsigned long long)j->st.samples, (unsigned long long)j->st.lines, j->st.pushes, j->st.seconds,
-                j->st.seconds > 0 ? (double)j->st.samples / j->st.seconds / 1e6 : 0.0);
+    if (j->stats) {
+        unsigned lanes = 0;
+        unsigned long long paired = 0, single = 0;
+        wmbus_batch_lane_stats(b, &lanes, &paired, &single);
+        fprintf(stderr, "rtl_wmbus_hip: device %d: %d files, %u contexts, %llu samples, %llu lines, %u pushes in %.3f s = %.1f Msamples/s; %u lanes, %llu paired and %llu single kernel launches\n",
+                j->cfg.device, j->n, wmbus_batch_contexts(b), (unsigned long long)j->st.samples, (unsigned long long)j->st.lines, j->st.pushes, j->st.seconds,
+                j->st.seconds > 0 ? (double)j->st.samples / j->st.seconds / 1e6 : 0.0, lanes, paired, single);
+    }
     if (j->stats && j->bytes_out)                            /* a converting path is active: what the gain did */
         fprintf(stderr, "rtl_wmbus_hip: device %d: input conversion: %llu of %llu bytes clipped (%.4f %%)\n", j->cfg.device, j->clipped, j->bytes_out,
                 100.0 * (double)j->clipped / (double)j->bytes_out);
