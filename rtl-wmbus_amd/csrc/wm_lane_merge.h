@@ -27,7 +27,15 @@ static inline bool wm_lane_pairs(const WmLaneKey &x, const WmLaneKey &y)
  * Rule: equal pairable heads pair; an operation that cannot pair leaves at once, A's first (so a run of them stays
  * together: the demodulation kernel's turn, taken and handed on by such operations, is never interleaved with the mate's);
  * two pairable heads that differ: the one whose partner waits further down the other list holds on while the other list
- * catches up.  With nothing pairable the result is A followed by B. */
+ * catches up.  With nothing pairable the result is A followed by B.
+ *
+ * PRECONDITION of "never interleaved": nothing pairable may be recorded between take() and hand_on() of a K1 turn (K1Turn,
+ * wm_api.hip); today nothing is.  A pairable operation inside a turn can be held back while the mate's list runs on into a
+ * turn of its own, and the second recorded take() then fails with hipErrorInvalidValue: A = [P3, 0, 0] (a turn over the two
+ * plain operations), B = [0, P2, 0] (a turn over all three) leaves as B's take, A's P3, A's take -- two turns open at once.
+ * How MUCH pairs depends on which list is A (the look-ahead is from A's head only): A = [P1, P2, P1], B = [P2, P1] pairs once,
+ * the lists swapped pair twice.  Accepted: two mates' lists differ by launches one of them lacks, not by their order, and for
+ * those every launch that can pair does (tests/lane_merge_check.cpp holds both statements). */
 template <typename Emit>
 static inline void wm_lane_merge(const WmLaneKey *A, size_t na, const WmLaneKey *B, size_t nb, Emit emit)
 {

@@ -13,6 +13,7 @@ import afc_age_ref as AG
 import format_ref as FR
 import power_ref as PW
 import spectrum_ref as PR
+from lanes import one_lane
 
 pytestmark = pytest.mark.gpu
 
@@ -224,6 +225,26 @@ def test_meaning_strong_frames(wm):
             assert k >= 0, (ln, lv)
             matched += 1
     assert matched >= 10
+
+
+def test_in_one_batch_lane(wm, constructed):
+    """The stage in a batch lane: a capture of telegrams (seed 1, amplitude 60) and the constructed capture "runs" -- bursts that are no
+    telegrams -- in each of two contexts that share ONE lane, four pushes of 2^18 bytes: the band survey, k0_channel_power, k0_activity and
+    the copies of P and of the record count recorded and issued behind the mate's operations.  The records a context's sinks were handed
+    (Batch.bursts) equal, row by row, tests/activity_ref.py on the restated timeline, and everything equals the lane-per-context run."""
+    frames = wm.synth_capture(seed=1, n_samples=1 << 19, kinds=wm.T1 | wm.C1A | wm.S1, frames_per_s=40.0, amplitude=60.0, noise_sigma=3.0)[0]
+    caps = [frames, constructed["caps"]["runs"]]
+    P = [PW.channel_power(PW.band_rows(frames, FR.CU8), FS, 0), constructed["P"]["runs"]]
+    want = [AR.rule(p, FS) for p in P]
+    assert len(want[0]) >= 10 and len(want[1]) >= 5                         # on the restatement: records of telegrams, and records of none
+    got = one_lane(wm, caps + caps, 4, push=1 << 18, n_push=caps[0].size >> 18, input_windows=2, channel_activity=1)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 18 == 4
+    for first in (0, 2):
+        assert sum(len(push) for push in got.lines[first]) >= 5                  # the telegrams' lines, in either context
+        for chain in (0, 1):
+            for v in (0, 1):
+                assert AR.strip([b for b in got.bursts[first] if b["chain"] == chain and b["stream"] == v and b["channel"] == 0]) == want[v], (first, chain, v)
+        assert len(got.bursts[first]) == 2 * (len(want[0]) + len(want[1]))
 
 
 def test_meaning_weak_frames(wm):

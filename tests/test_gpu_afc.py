@@ -13,6 +13,7 @@ import afc_ref as AF
 import format_ref as FR
 import shift_ref as SR
 import spectrum_ref as PR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS, design
 
 pytestmark = pytest.mark.gpu
@@ -169,6 +170,27 @@ def test_batch_locks_every_capture_to_its_own_offset(wm, samples):
         locks = [rx.read_input_afc(s) for rx, first, n in b.contexts for s in range(n)]
     assert text == want
     assert [a["locked"] for a in locks] == [1] * 4 and len({a["shift_hz"] for a in locks}) == 4
+
+
+def test_batch_in_one_lane_locks_every_capture_to_its_own_offset(wm, oracle, samples):
+    """The four captures of the batch test above as two contexts of two in ONE lane, each capture in two pushes of half its length: the
+    survey, k0_afc_plan and the AFC form of the input kernel recorded and issued behind the mate's operations, the second push behind a
+    carried lock.  Lines against the oracle on tests/afc_ref.py's bytes for those two pushes, the locks against its plans, everything
+    against the lane-per-context run."""
+    caps = [mixed(samples, f) for f in MIXES]
+    cuts = [caps[0].size // 2] * 2
+    assert cuts[0] % BLK == 0
+    want, locks = [], []
+    for c in caps:
+        y, pl = AF.pipeline_bytes(c, FR.CU8, FS, cuts, g_q8=GAIN)
+        want.append(oracle.run(y, oracle.make_opts())["text"]); locks.append(AF.public(pl[-1][2]))
+    assert all(len(w.splitlines()) >= 3 for w in want) and len(set(want)) > 1 and len({a["shift_hz"] for a in locks}) == 4
+    seen = []
+    got = one_lane(wm, caps, 4, push=cuts[0], n_push=2, input_windows=2, input_gain_q8=GAIN, input_afc=1,
+                   after=lambda b: seen.append([rx.read_input_afc(s) for rx, first, n in b.contexts for s in range(n)]))
+    assert got.plan == [(0, 2), (2, 2)]
+    assert [got.whole_text(s) for s in range(4)] == want
+    assert seen[0] == locks and seen[1] == locks                 # the lane run's and the lane-per-context run's
 
 
 def test_a_context_without_the_field_is_the_context_it_was(wm, samples):

@@ -15,6 +15,7 @@ import afc_ref as AF
 import format_ref as FR
 import shift_ref as SR
 import spectrum_ref as PR
+from lanes import one_lane
 from test_formats_emulated import design
 from test_gpu_afc import GAIN, MIXES, mixed, quantised
 
@@ -146,6 +147,28 @@ def test_batch_with_an_ageing_survey(wm, samples):
     assert text == want
     assert [a["locked"] for a in locks] == [1] * 4 and len({a["shift_hz"] for a in locks}) == 4
     assert blocks == [push // 2 // PR.N] * 4
+
+
+def test_batch_in_one_lane_with_an_ageing_survey(wm, oracle, samples):
+    """The four captures of the batch test above as two contexts of two in ONE lane, each capture in two pushes of half its length, A = 12:
+    the ageing survey (its slot fills recorded too), k0_afc_plan on the view and the AFC form of the input kernel issued behind the mate's
+    operations.  Lines against the oracle on tests/afc_age_ref.py's bytes for those two pushes, the locks against its plans, the level
+    blocks of the view, and everything against the lane-per-context run."""
+    caps = [mixed(samples, f) for f in MIXES]
+    cuts = [caps[0].size // 2] * 2
+    assert cuts[0] % 4096 == 0 and caps[0].size // 2 // PR.N <= 1 << 12
+    want, locks = [], []
+    for c in caps:
+        y, pl = AG.pipeline_bytes(c, FR.CU8, FS, cuts, 12, g_q8=GAIN)
+        want.append(oracle.run(y, oracle.make_opts())["text"]); locks.append(AF.public(pl[-1][2]))
+    assert all(len(w.splitlines()) >= 3 for w in want) and len(set(want)) > 1 and len({a["shift_hz"] for a in locks}) == 4
+    seen = []
+    got = one_lane(wm, caps, 4, push=cuts[0], n_push=2, input_windows=2, input_gain_q8=GAIN, input_afc=1, input_spectrum_age=12,
+                   after=lambda b: seen.append([(rx.read_input_afc(s), rx.read_spectrum(s)[2]) for rx, first, n in b.contexts for s in range(n)]))
+    assert got.plan == [(0, 2), (2, 2)]
+    assert [got.whole_text(s) for s in range(4)] == want
+    for run in seen:                                             # the lane run's and the lane-per-context run's
+        assert [a for a, _ in run] == locks and [k for _, k in run] == [caps[0].size // 2 // PR.N] * 4
 
 
 def test_a_context_without_the_field_is_the_context_it_was(wm, samples):
@@ -345,6 +368,28 @@ def test_batch_with_channel_afc_and_an_ageing_survey(wm, samples, the_library_ha
         b.run_from(fill, on_push)
         locks = {(first + s, c): rx.read_input_afc(s * 2 + c) for rx, first, n in b.contexts for s in range(n) for c in range(2)}
     assert text == want and locks == locks_want
+
+
+def test_batch_in_one_lane_with_channel_afc_and_an_ageing_survey(wm, samples, the_library_has_the_channel_field):
+    """The batch above with its two contexts in ONE lane and every capture in two pushes of half its length: the lines and the locks of
+    channel c of every capture are those of the single-channel context on that capture in the same two pushes."""
+    caps = [mixed(samples, f) for f in MIXES]
+    half = caps[0].size // 2
+    hz, ranges = [-40000, 50000], [32000, 32000]
+    want, locks_want = {}, {}
+    for c, f in enumerate(hz):
+        with wm.Receiver(n_streams=len(caps), max_push_bytes=half, input_gain_q8=GAIN, input_shift_hz=f, input_afc=1, input_afc_range_hz=ranges[c],
+                         input_spectrum_age=12, keep_taps=False) as rx:
+            for k, text in enumerate(rx.run(caps, push_bytes=half)):
+                want[k, c] = text
+                locks_want[k, c] = rx.read_input_afc(k)
+    assert sum(len(t.splitlines()) for t in want.values()) >= 12 and sum(a["locked"] for a in locks_want.values()) == 4
+    seen = []
+    got = one_lane(wm, caps, 4, push=half, n_push=2, input_windows=2, input_gain_q8=GAIN, input_channel_hz=hz, input_channel_afc_hz=ranges, input_spectrum_age=12,
+                   after=lambda b: seen.append({(first + s, c): rx.read_input_afc(s * 2 + c) for rx, first, n in b.contexts for s in range(n) for c in range(2)}))
+    assert got.plan == [(0, 2), (2, 2)]
+    text = {(k, c): "".join(ln["text"] for push in got.lines[k] for ln in push if ln["channel"] == c) for k in range(4) for c in range(2)}
+    assert text == want and seen == [locks_want, locks_want]
 
 
 def test_bad_channel_afc_arguments_are_refused(wm, the_library_has_the_channel_field):

@@ -10,6 +10,7 @@ import pytest
 
 import agc_ref as AR
 import format_ref as FR
+from lanes import one_lane
 from test_agc_emulated import KINDS, jump_input, x_of
 from test_dc_emulated import OUT_HZ, dc_inputs
 from test_formats_emulated import FMT_IDS, FORMATS
@@ -82,16 +83,39 @@ def test_bytes_clip_count_and_gain_equal_the_restatement(wm, fmt, rate, R, n_str
     assert bytes_out == n_streams * restated(wm, keys[0], caps[0], fmt, R, fin, f, rate)[0].size
 
 
+_WEAK = {}
+
+
+def weak_captures(wm, oracle):
+    """The three weak cs16 captures and the oracle's text on tests/agc_ref.py's bytes of each: computed once, shared, left unchanged."""
+    if not _WEAK:
+        L, M, T, taps = wm.resampler_design(2048000, OUT_HZ)
+        cu8s = [wm.synth_capture(seed=8400 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0, amplitude=20.0, noise_sigma=3.0)[0] for s in range(3)]
+        caps = [FR.raw_bytes(4 * x_of(c), FR.CS16) for c in cu8s]
+        want = [oracle.run(AR.pipeline_bytes(c, FR.CS16, 0, 2048000, 0, L, M, taps), oracle.make_opts())["text"] for c in caps]
+        assert all(len(w.splitlines()) >= 10 for w in want)
+        for c in caps:
+            c.setflags(write=False)
+        _WEAK.update(caps=caps, want=want)
+    return _WEAK["caps"], _WEAK["want"]
+
+
+def test_weak_cs16_captures_in_one_lane(wm, oracle):
+    """The batch of the test below as two contexts of two captures in ONE lane (the fourth capture is the first again), four pushes of
+    2^20 bytes: k0_agc_gain and the AGC form of the input kernel recorded and issued behind the mate's operations."""
+    caps, want = weak_captures(wm, oracle)
+    got = one_lane(wm, caps + [caps[0]], 4, push=1 << 20, n_push=caps[0].size >> 20, input_windows=2, input_rate_hz=2048000, input_format=FR.CS16, input_agc=1)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 20 == 4
+    assert [got.whole_text(s) for s in range(4)] == want + [want[0]]
+
+
 def test_weak_cs16_captures_give_the_oracles_text_on_the_restated_bytes(wm, oracle, tmp_path):
     """Three 2.048 MS/s synthetic captures (amplitude 20 cu8 steps, noise sigma 3) written as cs16 = 4 (2u - 255), a 160-count amplitude:
     a single context in one push and in odd pushes, a batch and the CLI (-I cs16 -R 2.048M -g auto -v; on stdin, and in batch mode with a
     shorter file padded with silence) print what the oracle prints on tests/agc_ref.py's bytes.  At gain x 1 nothing is received."""
     L, M, T, taps = wm.resampler_design(2048000, OUT_HZ)
-    cu8s = [wm.synth_capture(seed=8400 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0, amplitude=20.0, noise_sigma=3.0)[0] for s in range(3)]
-    caps = [FR.raw_bytes(4 * x_of(c), FR.CS16) for c in cu8s]
+    caps, want = weak_captures(wm, oracle)
     opts = oracle.make_opts()
-    want = [oracle.run(AR.pipeline_bytes(c, FR.CS16, 0, 2048000, 0, L, M, taps), opts)["text"] for c in caps]
-    assert all(len(w.splitlines()) >= 10 for w in want)
     kw = dict(input_rate_hz=2048000, input_format=FR.CS16)
     with wm.Receiver(n_streams=3, max_push_bytes=caps[0].size, **kw) as rx:      # gain x 1
         assert rx.run(caps) == ["", "", ""]

@@ -13,6 +13,7 @@ import pytest
 import channels_fixture as CF
 import format_ref as FR
 import shift_ref as SR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS
 from test_resample_emulated import BLK, CUTS, N_BLOCKS
 from test_shift_emulated import shift_inputs
@@ -211,20 +212,43 @@ def test_blocker_and_agc_are_taken_once_per_capture(wm, wide, mode):
 
 # ---- 5. a batch -------------------------------------------------------------------------------------------------------------------
 
+FIVE_HZ, FIVE_PUSH = [200000, -150000], 1 << 18
+_FIVE = {}
+
+
+def five_captures(wm):
+    """The five captures of the batch tests and, per (capture, channel), the text of a single context with that channel's fixed shift in
+    pushes of 2^18 bytes: computed once, shared, left unchanged."""
+    if not _FIVE:
+        cu8s = [wm.synth_capture(seed=9300 + k, n_samples=1 << 18, kinds=15, frames_per_s=80.0)[0] for k in range(5)]
+        caps = [SR.round_trip_cu8(c, OUT_HZ, FIVE_HZ[k % 2]) for k, c in enumerate(cu8s)]
+        want = {}
+        for c, f in enumerate(FIVE_HZ):
+            with wm.Receiver(n_streams=5, input_shift_hz=f, keep_taps=False, max_push_bytes=FIVE_PUSH, input_gain_q8=SR.CU8_ROUND_TRIP_GAIN) as rx:
+                for k, t in enumerate(rx.run(caps, push_bytes=FIVE_PUSH)):
+                    want[(k, c)] = t
+        assert all(len(want[(k, k % 2)].splitlines()) >= 3 for k in range(5))
+        for c in caps:
+            c.setflags(write=False)
+        _FIVE.update(caps=caps, want=want)
+    return _FIVE["caps"], _FIVE["want"]
+
+
+def test_batch_of_five_captures_and_two_channels_in_one_lane(wm):
+    """The batch below with its two contexts (3 + 2 captures, two channels each) in ONE lane, two pushes: the channel form of the input
+    kernel recorded and issued behind the mate's operations, two mates of different widths in every paired launch."""
+    caps, want = five_captures(wm)
+    got = one_lane(wm, caps, 5, push=FIVE_PUSH, n_push=caps[0].size // FIVE_PUSH, input_windows=2, input_channel_hz=FIVE_HZ, input_gain_q8=SR.CU8_ROUND_TRIP_GAIN)
+    assert got.plan == [(0, 3), (3, 2)] and caps[0].size // FIVE_PUSH == 2 and got.run_stats["samples"] == 5 * caps[0].size // 2
+    text = {(k, c): "".join(ln["text"] for push in got.lines[k] for ln in push if ln["channel"] == c) for k in range(5) for c in range(2)}
+    assert text == want
+
+
 def test_batch_of_five_captures_and_two_channels(wm, oracle):
     """Five native-rate cu8 captures through a fill source, two contexts: captures 0, 2, 4 were mixed up by 200 kHz, 1 and 3 down by
     150 kHz.  The sink sees stream 0 ... 4 (batch-wide) and channel 0 ... 1 with the single-context text of every pair."""
-    hz = [200000, -150000]
-    cu8s = [wm.synth_capture(seed=9300 + k, n_samples=1 << 18, kinds=15, frames_per_s=80.0)[0] for k in range(5)]
-    caps = [SR.round_trip_cu8(c, OUT_HZ, hz[k % 2]) for k, c in enumerate(cu8s)]
-    push = 1 << 18
-    kw = dict(max_push_bytes=push, input_gain_q8=SR.CU8_ROUND_TRIP_GAIN)
-    want = {}
-    for c, f in enumerate(hz):
-        with wm.Receiver(n_streams=5, input_shift_hz=f, keep_taps=False, **kw) as rx:
-            for k, t in enumerate(rx.run(caps, push_bytes=push)):
-                want[(k, c)] = t
-    assert all(len(want[(k, k % 2)].splitlines()) >= 3 for k in range(5))
+    hz, push, kw = FIVE_HZ, FIVE_PUSH, dict(max_push_bytes=FIVE_PUSH, input_gain_q8=SR.CU8_ROUND_TRIP_GAIN)
+    caps, want = five_captures(wm)
     got = {(k, c): "" for k in range(5) for c in range(2)}
     with wm.Batch(n_streams=5, contexts=2, input_windows=2, input_channel_hz=hz, **kw) as b:
         assert [n for _, _, n in b.contexts] == [3, 2]       # the plan splits captures

@@ -10,6 +10,7 @@ import pytest
 
 import dc_ref as DR
 import format_ref as FR
+from lanes import one_lane
 from test_dc_emulated import OUT_HZ, RATE_IDS, RATES, dc_inputs
 from test_formats_emulated import FMT_IDS, FORMATS
 from test_resample_emulated import BLK, CUTS, N_BLOCKS
@@ -83,19 +84,43 @@ def test_bytes_clip_count_and_dc_equal_the_restatement(wm, fmt, rate, R, n_strea
     assert bytes_out == n_streams * restated(wm, keys[0], caps[0], fmt, R, fin, f, g, rate)[0].size
 
 
+_OFFSET = {}
+OFFSET_KW = dict(input_rate_hz=2048000, input_format=FR.CS8, input_dc=6)
+
+
+def offset_captures(wm, oracle):
+    """The three offset cs8 captures and the oracle's text on tests/dc_ref.py's bytes of each: computed once, shared, left unchanged."""
+    if not _OFFSET:
+        L, M, T, taps = wm.resampler_design(2048000, OUT_HZ)
+        cu8s = [wm.synth_capture(seed=8300 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0, amplitude=20.0, noise_sigma=3.0)[0] for s in range(3)]
+        caps = [FR.raw_bytes(DR.add_offset_cu8(c, 12, -9).astype(np.int64) - 128, FR.CS8) for c in cu8s]
+        want = [oracle.run(DR.pipeline_bytes(c, FR.CS8, 6, 2048000, 0, 256, L, M, taps), oracle.make_opts())["text"] for c in caps]
+        assert all(len(w.splitlines()) >= 10 for w in want)
+        for c in caps:
+            c.setflags(write=False)
+        _OFFSET.update(caps=caps, want=want)
+    return _OFFSET["caps"], _OFFSET["want"]
+
+
+def test_offset_cs8_captures_in_one_lane(wm, oracle):
+    """The batch of the test below as two contexts of two captures in ONE lane (the fourth capture is the first again), four pushes of
+    2^19 bytes: k0_dc_sums, k0_dc_plan and the DC form of the input kernel recorded and issued behind the mate's operations."""
+    caps, want = offset_captures(wm, oracle)
+    got = one_lane(wm, caps + [caps[0]], 4, push=1 << 19, n_push=caps[0].size >> 19, input_windows=2, **OFFSET_KW)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 19 == 4
+    assert [got.whole_text(s) for s in range(4)] == want + [want[0]]
+
+
 def test_offset_cs8_captures_give_the_oracles_text_on_the_restated_bytes(wm, oracle):
     """Three 2.048 MS/s synthetic captures of medium strength (amplitude 20 cu8 steps) with an I/Q offset of (+12, -9) added, written as
     cs8: a single context in one push and in odd pushes, a batch and the CLI (-I cs8 -R 2.048M -C 6 -v) print what the oracle prints
     on tests/dc_ref.py's bytes."""
     L, M, T, taps = wm.resampler_design(2048000, OUT_HZ)
-    cu8s = [wm.synth_capture(seed=8300 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0, amplitude=20.0, noise_sigma=3.0)[0] for s in range(3)]
-    caps = [FR.raw_bytes(DR.add_offset_cu8(c, 12, -9).astype(np.int64) - 128, FR.CS8) for c in cu8s]
+    caps, want = offset_captures(wm, oracle)
     opts = oracle.make_opts()
-    want = [oracle.run(DR.pipeline_bytes(c, FR.CS8, 6, 2048000, 0, 256, L, M, taps), opts)["text"] for c in caps]
-    assert all(len(w.splitlines()) >= 10 for w in want)
     # the blocker is what receives them
     assert oracle.run(FR.pipeline_bytes(caps[0], FR.CS8, 256, L, M, taps), opts)["text"] != want[0]
-    kw = dict(input_rate_hz=2048000, input_format=FR.CS8, input_dc=6)
+    kw = OFFSET_KW
     with wm.Receiver(n_streams=3, max_push_bytes=caps[0].size, **kw) as rx:
         assert rx.run(caps) == want
         dc = rx.read_input_dc(0)

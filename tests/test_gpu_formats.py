@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import format_ref as FR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS, design_inputs, inputs
 import resample_ref as RR
 from test_resample_emulated import BLK, CUTS, N_BLOCKS
@@ -160,15 +161,57 @@ def test_bundled_goldens_through_the_new_formats(wm, samples, fmt, sample, key, 
     assert text == [want] * 8
 
 
+@pytest.mark.parametrize("sample,key,kw,cli", GOLDENS, ids=GOLDEN_IDS)
+@pytest.mark.parametrize("fmt", WIDE, ids=WIDE_IDS)
+def test_bundled_goldens_in_one_lane(wm, samples, fmt, sample, key, kw, cli):
+    """The batch of the test above as two contexts of four streams in ONE lane: the format's input kernel recorded and issued behind the
+    mate's operations, in pushes of 2^20 raw bytes, or of half the recording where that is less (two pushes at least: a carry)."""
+    cu8 = samples[sample]
+    cu8 = cu8[:cu8.size // BLK * BLK]
+    raw = FR.embed(cu8, fmt)
+    want = BUNDLED[key]
+    assert len(want.splitlines()) >= 1
+    push = min(1 << 20, raw.size // 2 // BLK * BLK)
+    sizes = [min(push, raw.size - off) for off in range(0, raw.size, push)]
+    assert len(sizes) >= 2
+    got = one_lane(wm, [raw] * 8, 8, push=push, sizes_of={0: sizes, 4: sizes}, input_windows=2, input_format=fmt, **kw)
+    assert got.plan == [(0, 4), (4, 4)] and all(tm["input_clipped"] == 0 for per in got.timing.values() for tm in per)
+    assert [got.whole_text(s) for s in range(8)] == [want] * 8
+
+
+_CS16 = {}
+CS16_GAIN = 64 * 256
+
+
+def cs16_captures(wm, oracle):
+    """Three 2.048 MS/s captures as cs16 6 bits down and the oracle's text on the restated bytes: computed once, shared, left unchanged."""
+    if not _CS16:
+        L, M, T, taps = wm.resampler_design(2048000, 1600000)
+        cu8s = [wm.synth_capture(seed=8100 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0)[0] for s in range(3)]
+        caps = [FR.raw_bytes(FR.embed(c, FR.CS16).view("<i2") >> 6, FR.CS16) for c in cu8s]
+        want = [oracle.run(FR.pipeline_bytes(c, FR.CS16, CS16_GAIN, L, M, taps), oracle.make_opts())["text"] for c in caps]
+        assert all(len(w.splitlines()) >= 10 for w in want)
+        for c in caps:
+            c.setflags(write=False)
+        _CS16.update(caps=caps, want=want)
+    return _CS16["caps"], _CS16["want"]
+
+
+def test_resampling_a_cs16_capture_in_one_lane(wm, oracle):
+    """The batch of the test below as two contexts of two captures in ONE lane (the fourth capture is the first again), eight pushes of 2^19 bytes."""
+    caps, want = cs16_captures(wm, oracle)
+    got = one_lane(wm, caps + [caps[0]], 4, push=1 << 19, n_push=caps[0].size >> 19, input_windows=2, input_rate_hz=2048000, input_format=FR.CS16,
+                   input_gain_q8=CS16_GAIN)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 19 == 8
+    assert [got.whole_text(s) for s in range(4)] == want + [want[0]]
+
+
 def test_resampling_a_cs16_capture_gives_the_oracles_text_on_the_restated_bytes(wm, oracle, tmp_path):
     """2.048 MS/s synthetic captures, written as cs16 6 bits down and brought back by a gain of 64: single context, batch, CLI."""
     L, M, T, taps = wm.resampler_design(2048000, 1600000)
-    g, db = 64 * 256, "36.1236"                          # 20 log10(64) = 36.1236: rint(256 * 10^(dB / 20)) = 16384
-    cu8s = [wm.synth_capture(seed=8100 + s, n_samples=1 << 20, fs_khz=2048, kinds=KINDS, frames_per_s=60.0)[0] for s in range(3)]
-    caps = [FR.raw_bytes(FR.embed(c, FR.CS16).view("<i2") >> 6, FR.CS16) for c in cu8s]
+    g, db = CS16_GAIN, "36.1236"                         # 20 log10(64) = 36.1236: rint(256 * 10^(dB / 20)) = 16384
+    caps, want = cs16_captures(wm, oracle)
     opts = oracle.make_opts()
-    want = [oracle.run(FR.pipeline_bytes(c, FR.CS16, g, L, M, taps), opts)["text"] for c in caps]
-    assert all(len(w.splitlines()) >= 10 for w in want)
     kw = dict(input_rate_hz=2048000, input_format=FR.CS16, input_gain_q8=g)
     with wm.Receiver(n_streams=3, max_push_bytes=caps[0].size, **kw) as rx:
         assert rx.run(caps) == want

@@ -10,22 +10,17 @@ import os
 import pytest
 
 from cases import flags_to_oracle_opts
+from lanes import LANE_N_PUSH, LANE_PUSH, LANE_SEGS, conserved, lane_caps, lane_run
 
 pytestmark = pytest.mark.gpu
 
-PUSH = 2 << 15                 # bytes of a push: 2^15 IQ samples
-N_PUSH = 3
-SEGS = dict(seg_len=4096, rla_seg_len=1024)
+PUSH, N_PUSH, SEGS = LANE_PUSH, LANE_N_PUSH, LANE_SEGS
 
 
 @pytest.fixture(scope="module")
 def caps(wm):
     """192 captures of three pushes (read-only: every case takes a prefix)."""
-    out = [wm.synth_capture(seed=0x1A7E5 + i, n_samples=N_PUSH * PUSH // 2, kinds=15, frames_per_s=200.0)[0] for i in range(192)]
-    for c in out:
-        assert c.size == N_PUSH * PUSH
-        c.setflags(write=False)
-    return out
+    return lane_caps(wm, 192)
 
 
 @pytest.fixture(scope="module")
@@ -38,55 +33,19 @@ def want(caps, oracle):
             "resident": [oracle.run_many(first, opts, passes=k + 1, threads=th) for k in range(N_PUSH)]}
 
 
-def run(wm, caps, S, contexts, lanes, resident, pushes_of=None, **kw):
+def run(wm, caps, S, contexts, lanes, resident, **kw):
     """One batch run under WMBUS_BATCH_LANES=lanes.  Returns (per capture: the text of every push, the lane statistics, the plan)."""
-    old = os.environ.get("WMBUS_BATCH_LANES")
-    os.environ["WMBUS_BATCH_LANES"] = str(lanes)
-    try:
-        b = wm.Batch(n_streams=S, contexts=contexts, max_push_bytes=PUSH, input_windows=1 if resident else 2, **SEGS, **kw)
-    finally:
-        if old is None:
-            del os.environ["WMBUS_BATCH_LANES"]
-        else:
-            os.environ["WMBUS_BATCH_LANES"] = old
-    with b:
-        plan = [(first, n) for _rx, first, n in b.contexts]
-        text = [[] for _ in range(S)]
-
-        def on_push(first, n, lines, tm):
-            assert tm["warnings"] == 0
-            for s in range(first, first + n):
-                text[s].append("")
-            for ln in lines:
-                assert first <= ln["stream"] < first + n
-                text[ln["stream"]][-1] += ln["text"]
-        if resident:
-            for s in range(S):
-                b.stage(s, caps[s][:PUSH])
-            st = b.run_resident(PUSH, N_PUSH, on_push)
-            assert st["pushes"] == len(plan) * N_PUSH
-        else:
-            n_of = {first: (pushes_of or {}).get(first, N_PUSH) for first, _n in plan}
-            done = {first: 0 for first, _n in plan}
-
-            def fill(first, n, slab):
-                k = done[first]
-                if k == n_of[first]:
-                    return 0
-                done[first] = k + 1
-                for j in range(n):
-                    slab[j, :PUSH] = caps[first + j][k * PUSH:(k + 1) * PUSH]
-                return PUSH
-            st = b.run_from(fill, on_push)
-            assert st["pushes"] == sum(n_of.values())
-        return text, b.lane_stats(), plan
+    r = lane_run(wm, caps, S, contexts, lanes, resident, push=PUSH, n_push=N_PUSH, input_windows=1 if resident else 2, **SEGS, **kw)
+    return r.text, r.stats, r.plan
 
 
 def both(wm, caps, S, contexts, lanes, resident, **kw):
-    """The run in lanes and the same run with a lane per context; their lines must agree push for push."""
+    """The run in lanes and the same run with a lane per context; their lines must agree push for push, and the launches of the
+    second are those of the first with every paired launch counted twice (lanes.py)."""
     text, stats, plan = run(wm, caps, S, contexts, lanes, resident, **kw)
     alone, stats1, plan1 = run(wm, caps, S, contexts, contexts, resident, **kw)
     assert plan1 == plan and stats1["lanes"] == contexts and stats1["paired"] == 0 and stats1["single"] > 0
+    assert conserved(stats, stats1), (stats, stats1)
     assert text == alone
     assert sum(len(t) for per in text for t in per) > 1000 * S // 128       # the captures decode to something
     return text, stats, plan

@@ -7,7 +7,10 @@ import subprocess
 
 import pytest
 
+import numpy as np
+
 import level_ref as LR
+from lanes import one_lane
 
 pytestmark = pytest.mark.gpu
 
@@ -162,6 +165,20 @@ def test_batch_sink_collects_levels(wm, eight):
     for s in range(64):
         assert len(got[s]) >= 10
         check_against_oracle(got[s], refs[s % 8])
+
+
+def test_batch_sink_in_one_lane(wm, oracle, eight):
+    """Case 3b with both contexts in ONE lane (k3_levels and k3_level_tail recorded and issued behind the mate's operations) and two
+    passes over the resident captures: every record of both passes against the oracle's taps and chips of the capture fed twice -- the
+    second pass's telegrams at the start of the push read the carried tail."""
+    caps, _ = eight
+    refs2 = [oracle_of(oracle, np.concatenate([c, c])) for c in caps]
+    got = one_lane(wm, [caps[s % 8] for s in range(64)], 64, True, push=caps[0].size, n_push=2, line_levels=1)
+    assert got.plan == [(0, 32), (32, 32)]
+    for s in range(64):
+        p1, p2 = got.lines[s]
+        assert len(p1) >= 10 and len(p2) >= 10
+        assert check_against_oracle([(r, r["level"]) for r in p1 + p2], refs2[s % 8]) >= 20
 
 
 @pytest.mark.parametrize("opts", [dict(dedup_twins=True), dict(dedup_twins=True, only_crc_ok=True)], ids=["dedup-twins", "only-crc-ok"])

@@ -12,6 +12,7 @@ import afc_age_ref as AG
 import format_ref as FR
 import power_ref as PW
 import spectrum_ref as PR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS
 from test_power_emulated import level_blocks
 
@@ -122,6 +123,25 @@ def test_cut_independence(wm, capture):
         # at least one telegram has its access code and its end in different pushes
         edges = np.cumsum([n // 2 // 2 for n in sizes])                  # decimated samples
         assert any(np.searchsorted(edges, lv["sync_sample"], "right") != np.searchsorted(edges, ln["sample"], "right") for ln, lv, _ in cut["lines"]), kw
+
+
+def test_in_one_batch_lane(wm, capture):
+    """The stage in a batch lane: the capture of test 2 and a second one (seed 2), each in both of two contexts that share ONE lane, four
+    pushes of 2^18 bytes -- the band form of the survey, k0_channel_power and the copy of P to the host recorded and issued behind the
+    mate's operations.  Every line's record equals tests/power_ref.py's rule on the restated timeline of its capture, the lines and records
+    of the first capture are those of test 2's single context, and everything equals the lane-per-context run."""
+    other = wm.synth_capture(seed=SEED + 1, n_samples=1 << 19, kinds=wm.T1 | wm.C1A | wm.S1, frames_per_s=40.0, amplitude=AMPLITUDE, noise_sigma=SIGMA)[0]
+    caps = [capture["cu8"], other]
+    P = [capture["P"], PW.channel_power(PW.band_rows(other, FR.CU8), FS, 0)]
+    got = one_lane(wm, caps + caps, 4, push=1 << 18, n_push=caps[0].size >> 18, input_windows=2, line_power=1, line_levels=1)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 18 == 4
+    for s in range(4):
+        recs = [r for push in got.lines[s] for r in push]
+        want = [PW.line_record(P[s % 2], 0, PW.block_of(r["level"]["sync_sample"]), PW.block_of(r["sample"]), FS) for r in recs]
+        assert len(recs) >= 5 and any(w["n_signal"] for w in want)           # lines, and records that are not empty, in every context
+        assert [r["power"] for r in recs] == want, s
+        if s % 2 == 0:
+            assert [(r["text"], r["level"], r["power"]) for r in recs] == [(ln["text"], lv, pw) for ln, lv, pw in capture["one"]["lines"]]
 
 
 def test_windows_shift_channels_and_simultaneous(wm):

@@ -13,6 +13,7 @@ import pytest
 import quality_ref as QR
 import repair_ref as RR
 import telegram_ref as TR
+from lanes import one_lane
 
 pytestmark = pytest.mark.gpu
 
@@ -132,6 +133,21 @@ def test_three_streams_s1_and_c1(wm, oracle, bundled):
     assert n_meas[0] == 6 and n_meas[1] == 6, n_meas
     s1_recs = [r["quality"] for ln, r in got if ln["stream"] == 0 and r["quality"]["n"]]
     assert all(abs(r["chip_rate_chz"] - 3_276_800) < 3_276_800 // 100 for r in s1_recs)      # the modulator's clock is exact; 1 %: a sanity bound, the parity above is the test
+
+
+def test_batch_sink_in_one_lane(wm, oracle, bundled):
+    """The same batch with both contexts in ONE lane (k3_quality recorded and issued behind the mate's operations), two passes over the
+    resident capture: pass 1 gives the records of the single push, pass 2 those the restatement gives for the second half of the
+    capture fed twice."""
+    cu8, one = bundled["cu8"], bundled["want"]
+    ref2 = oracle.run(np.concatenate([cu8, cu8]), oracle.make_opts(), taps=True, chips=True)
+    lines2, want2, n1 = ref2["text"].splitlines(keepends=True), QR.quality_capture(ref2, push_m=cu8.size // 4), len(one)
+    assert lines2[:n1] == bundled["lines"] and want2[:n1] == one and any(r["n"] > 0 for r in one) and any(r["n"] > 0 for r in want2[n1:])
+    got = one_lane(wm, [cu8] * 64, 64, True, push=cu8.size, n_push=2, line_quality=1)
+    for s in range(64):
+        p1, p2 = got.lines[s]
+        assert [r["text"] for r in p1] == bundled["lines"] and [r["quality"] for r in p1] == one, s
+        assert [r["text"] for r in p2] == lines2[n1:] and [r["quality"] for r in p2] == want2[n1:], s
 
 
 def test_batch_sink_reads_the_records(wm, bundled):

@@ -12,6 +12,7 @@ import pytest
 import channels_fixture as CF
 import format_ref as FR
 import repair_ref as RR
+from lanes import one_lane
 
 pytestmark = pytest.mark.gpu
 
@@ -147,6 +148,22 @@ def test_beside_a_channel_list(wm, oracle):
         assert "".join(ln["text"] for ln in plain if ln["channel"] == c) == ref["text"]
         n_sub += want["subjects"]
     print("two channels: subjects", n_sub)
+
+
+def test_batch_sink_in_one_lane(wm, oracle, captures):
+    """The same batch with both contexts in ONE lane (k3_repair recorded and issued behind the mate's operations), two passes over the
+    resident capture: pass 1 gives the records of the single push, pass 2 those the restatement gives for the second half of the
+    capture fed twice -- the same telegrams again, behind a carry."""
+    c = captures["samples2"]
+    cu8, one = c["cu8"], c["want"]
+    want2 = RR.repair_capture(oracle.run(np.concatenate([cu8, cu8]), oracle.make_opts(), taps=True, chips=True), push_m=cu8.size // 4)
+    n1 = len(one["lines"])
+    assert all(want2[k][:n1] == one[k] for k in ("lines", "crc_ok", "records")) and sum(one["repaired"]) >= 1 and sum(want2["repaired"][n1:]) >= 1
+    got = one_lane(wm, [cu8] * 64, 64, True, push=cu8.size, n_push=2, crc_repair=1)
+    split = lambda push: [(dict((k, v) for k, v in r.items() if k != "repair"), r["repair"]) for r in push]
+    for s in range(64):
+        check(split(got.lines[s][0]), one)
+        check(split(got.lines[s][1]), {k: want2[k][n1:] for k in ("lines", "crc_ok", "records")})
 
 
 def test_batch_sink_reads_the_records(wm, captures):

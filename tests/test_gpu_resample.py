@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import resample_ref as RR
+from lanes import one_lane
 from test_resample_emulated import BLK, CUTS, IDS, N_BLOCKS, N_YIELD, RATES, WORST, WORST_IDS, crc_clean, received, worst_yield_captures, yield_captures
 
 pytestmark = pytest.mark.gpu
@@ -94,11 +95,7 @@ def synth_at(wm, fs_khz, seed, n_samples=1 << 20, **kw):
 
 @pytest.mark.parametrize("fs_khz,d", TEXT_RATES, ids=[str(r[0]) for r in TEXT_RATES])
 def test_text_equals_the_oracle_on_the_restated_bytes(wm, oracle, fs_khz, d):
-    L, M, T, taps = wm.resampler_design(fs_khz * 1000, 800000 * d)
-    caps = [synth_at(wm, fs_khz, 7100 + fs_khz + s)[0] for s in range(3)]
-    opts = oracle.make_opts(decimation=d)
-    want = [oracle.run(RR.pipeline_bytes(c, L, M, taps), opts)["text"] for c in caps]
-    assert all(len(w.splitlines()) >= 10 for w in want)
+    caps, want = text_captures(wm, oracle, fs_khz, d)
     # single context: one push, and ragged pushes through both input windows
     with wm.Receiver(n_streams=3, max_push_bytes=caps[0].size, decimation=d, input_rate_hz=fs_khz * 1000) as rx:
         assert rx.run(caps) == want
@@ -126,6 +123,41 @@ def test_text_equals_the_oracle_on_the_restated_bytes(wm, oracle, fs_khz, d):
     assert text == want
 
 
+_TEXT = {}
+
+
+def text_captures(wm, oracle, fs_khz, d, n_samples=1 << 20, seed=7100, long_=False):
+    """Three captures at a raw rate and the oracle's text on the restated bytes: computed once per rate, shared, left unchanged."""
+    key = (fs_khz, d, seed)
+    if key not in _TEXT:
+        L, M, T, taps = wm.resampler_design(fs_khz * 1000, 800000 * d)
+        caps = [synth_at(wm, fs_khz, seed + fs_khz + s, n_samples=n_samples)[0] for s in range(3)]
+        want = []
+        for c in caps:
+            y = RR.resample_long(c, L, M, taps) if long_ else RR.pipeline_bytes(c, L, M, taps)
+            want.append(oracle.run(y[:y.size // BLK * BLK], oracle.make_opts(decimation=d))["text"])
+            c.setflags(write=False)
+        assert all(len(w.splitlines()) >= 10 for w in want)
+        _TEXT[key] = (caps, want)
+    return _TEXT[key]
+
+
+def lane_leg(wm, caps, want, push, d, fs_khz):
+    """A batch case as two contexts of two captures in ONE lane (the fourth capture is the first again): the resampler recorded and
+    issued behind the mate's operations, several pushes."""
+    sizes = [min(push, caps[0].size - off) for off in range(0, caps[0].size, push)]
+    assert len(sizes) >= 2
+    got = one_lane(wm, caps + [caps[0]], 4, push=push, sizes_of={0: sizes, 2: sizes}, decimation=d, input_rate_hz=fs_khz * 1000, input_windows=2)
+    assert got.plan == [(0, 2), (2, 2)] and got.run_stats["samples"] == 4 * caps[0].size // 2
+    assert [got.whole_text(s) for s in range(4)] == want + [want[0]]
+
+
+@pytest.mark.parametrize("fs_khz,d", TEXT_RATES, ids=[str(r[0]) for r in TEXT_RATES])
+def test_text_in_one_lane(wm, oracle, fs_khz, d):
+    caps, want = text_captures(wm, oracle, fs_khz, d)
+    lane_leg(wm, caps, want, 1 << 19, d, fs_khz)
+
+
 # (generator fs_khz, decimation, samples): upsampling 8 / 5 (T = 16) and 1 / 32 (T = 512)
 CORNER_TEXT_RATES = [(1000, 2, 1 << 20), (25600, 1, 1 << 24)]
 
@@ -134,13 +166,7 @@ CORNER_TEXT_RATES = [(1000, 2, 1 << 20), (25600, 1, 1 << 24)]
 def test_text_at_two_corner_rates_equals_the_oracle_on_the_restated_bytes(wm, oracle, fs_khz, d, n_samples):
     L, M, T, taps = wm.resampler_design(fs_khz * 1000, 800000 * d)
     assert L > M or T >= 256
-    caps = [synth_at(wm, fs_khz, 7300 + fs_khz + s, n_samples=n_samples)[0] for s in range(3)]
-    opts = oracle.make_opts(decimation=d)
-    want = []
-    for c in caps:
-        y = RR.resample_long(c, L, M, taps)
-        want.append(oracle.run(y[:y.size // BLK * BLK], opts)["text"])
-    assert all(len(w.splitlines()) >= 10 for w in want)
+    caps, want = text_captures(wm, oracle, fs_khz, d, n_samples=n_samples, seed=7300, long_=True)
     push = 1 << 21
     with wm.Receiver(n_streams=3, max_push_bytes=push, decimation=d, input_rate_hz=fs_khz * 1000, input_windows=2, keep_taps=False) as rx:
         assert rx.run(caps, push_bytes=BLK * 97) == want
@@ -162,6 +188,12 @@ def test_text_at_two_corner_rates_equals_the_oracle_on_the_restated_bytes(wm, or
         st = b.run_from(fill, on_push)
         assert st["samples"] == 3 * caps[0].size // 2
     assert text == want
+
+
+@pytest.mark.parametrize("fs_khz,d,n_samples", CORNER_TEXT_RATES, ids=[str(r[0]) for r in CORNER_TEXT_RATES])
+def test_text_at_two_corner_rates_in_one_lane(wm, oracle, fs_khz, d, n_samples):
+    caps, want = text_captures(wm, oracle, fs_khz, d, n_samples=n_samples, seed=7300, long_=True)
+    lane_leg(wm, caps, want, min(1 << 21, caps[0].size // 2), d, fs_khz)      # two pushes at least: a carry
 
 
 @pytest.mark.parametrize("fin,d", WORST, ids=WORST_IDS)

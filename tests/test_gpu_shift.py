@@ -11,6 +11,7 @@ import pytest
 
 import format_ref as FR
 import shift_ref as SR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS
 from test_resample_emulated import BLK, CUTS, N_BLOCKS
 from test_shift_emulated import shift_inputs
@@ -139,6 +140,24 @@ def test_resampled_and_shifted_cs16_capture_gives_the_oracles_text_on_the_restat
         name, rest = line.split(": ", 1)
         got[name] += rest
     assert got == want_b
+
+
+def test_shifted_captures_in_one_batch_lane(wm, oracle):
+    """The stage in a batch lane: two 2.5 MS/s captures mixed up by 250 kHz as cs16, each in both of two contexts that share ONE lane,
+    eight pushes of 2^18 bytes -- the rotating input kernel recorded and issued behind the mate's operations.  Lines against the oracle on
+    tests/shift_ref.py's bytes and against the lane-per-context run."""
+    fin, f, g = 2500000, 250000, 64 * 256
+    L, M, T, taps = wm.resampler_design(fin, OUT_HZ)
+    caps = []
+    for s in range(2):
+        z = 2.0 * SR.mixed_up(wm.synth_capture(seed=8200 + s, n_samples=1 << 19, fs_khz=2500, kinds=KINDS, frames_per_s=60.0)[0], fin, f)
+        caps.append(FR.raw_bytes(np.rint(np.stack([z.real, z.imag], axis=1)).reshape(-1).astype(np.int16), FR.CS16))
+    want = [oracle.run(SR.pipeline_bytes(c, FR.CS16, fin, f, g, L, M, taps), oracle.make_opts())["text"] for c in caps]
+    assert all(len(w.splitlines()) >= 5 for w in want)
+    got = one_lane(wm, caps + caps, 4, push=1 << 18, n_push=caps[0].size >> 18, input_windows=2, input_rate_hz=fin, input_format=FR.CS16, input_gain_q8=g,
+                   input_shift_hz=f)
+    assert got.plan == [(0, 2), (2, 2)] and caps[0].size >> 18 == 8
+    assert [got.whole_text(s) for s in range(4)] == want + want
 
 
 def test_shift_zero_is_the_plain_path_and_a_shift_alone_is_a_stage(wm, oracle):

@@ -10,6 +10,7 @@ import pytest
 
 import format_ref as FR
 import spectrum_ref as PR
+from lanes import one_lane
 from test_formats_emulated import FMT_IDS, FORMATS
 from test_spectrum_emulated import full_scale_inputs
 
@@ -139,6 +140,26 @@ def test_a_context_with_the_field_prints_what_the_context_without_it_prints(wm, 
             assert out[0][0] == BUNDLED["rtlsdr_868.950M_1M6_samples2.cu8|-v"]
             hits = wm.spectrum_channels(1600000, *got)
             assert hits == PR.channels(1600000, *got) and len(hits) == 1 and abs(hits[0]["offset_hz"] + 10290) <= 3125
+
+
+def test_in_one_batch_lane(wm, oracle):
+    """The stage in a batch lane: two synthetic captures, each in both of two contexts that share ONE lane, four pushes of 2^18 bytes on
+    the plain cu8 path -- the survey kernel recorded inside the demodulation kernel's turn and issued behind the mate's operations.  The
+    accumulators of every capture after the run equal tests/spectrum_ref.py on the whole capture (in the lane run and in the
+    lane-per-context run), the lines are the oracle's."""
+    caps = [wm.synth_capture(seed=12 + s, n_samples=1 << 19, kinds=15, frames_per_s=60.0)[0] for s in range(2)]
+    want = [oracle.run(c, oracle.make_opts())["text"] for c in caps]
+    assert all(len(w.splitlines()) >= 5 for w in want)
+    spec = [PR.spectrum(c, FR.CU8) for c in caps]
+    assert all(sp[2] == (1 << 19) // PR.N and sp[1].any() for sp in spec)
+    seen = []
+    got = one_lane(wm, caps + caps, 4, push=1 << 18, n_push=4, input_windows=2, input_spectrum=1,
+                   after=lambda b: seen.append([rx.read_spectrum(s) for rx, first, n in b.contexts for s in range(n)]))
+    assert got.plan == [(0, 2), (2, 2)] and len(seen) == 2
+    for run in seen:
+        for s in range(4):
+            same(run[s], spec[s % 2], s)
+    assert [got.whole_text(s) for s in range(4)] == want + want
 
 
 def test_cli_survey(wm, samples, tmp_path):
