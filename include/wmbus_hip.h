@@ -396,6 +396,14 @@ int  wmbus_selftest_math(int device, const float *a, const float *b, float *o_sq
  * (n a multiple of 4, at most 976: one tile of the kernel); out[0 .. n) receives the 11-tap filter's outputs, out[n .. 2n) the 46-tap one's. */
 int  wmbus_selftest_fir(int device, const float *x, float *out, size_t n);
 
+/* Device self-test of the run-length framer's integer divisions (the kernel's own functions: a truncated quotient through the
+ * hardware's approximate reciprocal and a +-1 repair for dividends below 2^24 and divisors 4..4095, the integer divide
+ * elsewhere), compared on the device with the compiler's division: every divisor 4..4095 with every multiple below 2^24 and
+ * its two neighbours (3.5e8 cases), every divisor 1..8192 with the dividends 2^24 - 64 .. 2^24 + 64 and 0..128, each with
+ * either sign.  Returns the number of wrong quotients (0 is the only good answer) or a negative error; first16 (optional,
+ * 32 words) receives (dividend, divisor) of the first wrong ones, *cases (optional) the number of cases looked at. */
+long long wmbus_selftest_udiv(int device, uint32_t *first16, unsigned long long *cases);
+
 /* Measurement aid: the host half of wmbus_collect (sort, strip / format, merge: wm_decoder.c, replacing the decoders' fprintf at
  * t1_c1_packet_decoder.h:671-699 / s1_packet_decoder.h:248-269) over the records of the context's last push again, `reps` times, without
  * any GPU work.  Returns the lines of one repetition; *seconds receives the wall clock of all of them. */

@@ -22,6 +22,12 @@
  *                       zeroed history, as raw floats -- for operands no capture produces (signed zeros, subnormals)
  *   chips <chain> <algo-tag>   stdin = (chip value, rssi) byte pairs -> reference packet decoder;
  *                       datagram lines appear on stdout exactly as the reference prints them.
+ *   rla <chain> <file>  stdin = (raw slicer bit, rssi) byte pairs, one per decimated sample -> the reference's run-length
+ *                       framer (rtl_wmbus.c:640-702 for chain 1, :729-803 for chain 0) from its reset state.  After every
+ *                       sample one text line goes to <file>: run length, then bit length and cumulative error (chain 0) or
+ *                       the two samples-per-bit (chain 1), the level, the raw shift register masked to what the deglitch
+ *                       table reads (6 or 4 bits) and the chip shift register masked to the access code's width.  Datagram
+ *                       lines appear on stdout as the reference prints them.
  */
 #define main rtl_wmbus_reference_main
 #include "rtl_wmbus.c"
@@ -118,6 +124,30 @@ static int mode_chips(int chain, const char *tag)
     return 0;
 }
 
+static int mode_rla(int chain, const char *path)
+{
+    struct runlength_algorithm_t1_c1 t;
+    struct runlength_algorithm_s1 s;
+    runlength_algorithm_reset_t1_c1(&t);
+    runlength_algorithm_reset_s1(&s);
+    FILE *f = fopen(path, "w");
+    if (!f) return 1;
+    int b, r;
+    while ((b = getchar()) != EOF && (r = getchar()) != EOF) {
+        if (chain == 0) {
+            runlength_algorithm_t1_c1((unsigned)b & 1u, (unsigned)r, &t);
+            fprintf(f, "%d %d %d %u %u %u\n", t.run_length, t.bit_length, t.cum_run_length_error, t.state,
+                    (unsigned)(t.raw_bitstream & 0x3Fu), (unsigned)(t.bitstream & ACCESS_CODE_T1_C1_BITMASK));
+        } else {
+            runlength_algorithm_s1((unsigned)b & 1u, (unsigned)r, &s);
+            fprintf(f, "%d %d %d %u %u %u\n", s.run_length, s.samples_per_bit[0], s.samples_per_bit[1], s.state,
+                    (unsigned)(s.raw_bitstream & 0xFu), (unsigned)(s.bitstream & ACCESS_CODE_S1_BITMASK));
+        }
+    }
+    fclose(f);
+    return 0;
+}
+
 static int mode_atan(int which)
 {
     float p[2];
@@ -147,6 +177,7 @@ int main(int argc, char **argv)
     if (argc >= 3 && !strcmp(argv[1], "stages"))
         return mode_stages(argv[2], argc >= 4 && strchr(argv[3], 'a') != NULL, argc >= 4 && strchr(argv[3], 'p') != NULL);
     if (argc >= 4 && !strcmp(argv[1], "chips")) { opts_show_used_algorithm = 1; return mode_chips(atoi(argv[2]), argv[3]); }
-    fprintf(stderr, "usage: ref_probe tables | stages <prefix> [a][p] | atan <1|2> | fir <0|1> | chips <chain> <tag>\n");
+    if (argc >= 4 && !strcmp(argv[1], "rla")) { opts_show_used_algorithm = 1; return mode_rla(atoi(argv[2]), argv[3]); }
+    fprintf(stderr, "usage: ref_probe tables | stages <prefix> [a][p] | atan <1|2> | fir <0|1> | chips <chain> <tag> | rla <chain> <file>\n");
     return 2;
 }

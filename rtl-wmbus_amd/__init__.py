@@ -177,7 +177,7 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_batch_device_input", "wmbus_batch_run", "wmbus_batch_lane_stats",
            "wmbus_runtime_init", "wmbus_default_cfg", "wmbus_open", "wmbus_close", "wmbus_last_error", "wmbus_stage", "wmbus_device_input",
            "wmbus_process", "wmbus_collect", "wmbus_lines", "wmbus_lines_text", "wmbus_get_timing", "wmbus_read_tap",
-           "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_alloc_pinned", "wmbus_free_pinned",
+           "wmbus_read_chips", "wmbus_device_count", "wmbus_selftest_math", "wmbus_selftest_fir", "wmbus_selftest_udiv", "wmbus_alloc_pinned", "wmbus_free_pinned",
            "wmbus_debug_replay_decode", "wmbus_resampler_design", "wmbus_read_resampled", "wmbus_resampler_launches", "wmbus_shift_design", "wmbus_read_input_dc", "wmbus_read_input_gain",
            "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc",
            "wmbus_line_power", "wmbus_batch_line_power", "wmbus_read_waterfall", "wmbus_read_channel_power", "wmbus_line_power_rule", "wmbus_line_power_block",
@@ -240,6 +240,8 @@ def lib():
         L.wmbus_free_pinned.argtypes = [vp]
         L.wmbus_selftest_math.argtypes = [ctypes.c_int] + [vp] * 6 + [sz]
         L.wmbus_selftest_fir.argtypes = [ctypes.c_int, vp, vp, sz]
+        if hasattr(L, "wmbus_selftest_udiv"):               # an A/B against an earlier build (WMBUS_HIP_LIB) still loads
+            L.wmbus_selftest_udiv.argtypes = [ctypes.c_int, vp, ctypes.POINTER(ctypes.c_ulonglong)]; L.wmbus_selftest_udiv.restype = ctypes.c_longlong
         L.wmbus_debug_replay_decode.argtypes = [vp, u, ctypes.POINTER(ctypes.c_double)]; L.wmbus_debug_replay_decode.restype = ctypes.c_long
         L.wmbus_batch_open.argtypes = [ctypes.POINTER(Cfg), u, ctypes.POINTER(vp)]
         L.wmbus_batch_plan.argtypes = [ctypes.POINTER(Cfg), u, ctypes.POINTER(u), u]; L.wmbus_batch_plan.restype = u
@@ -374,6 +376,17 @@ def selftest_fir(x, device=0):
     if rc:
         raise WmbusError(f"selftest_fir failed: {rc}")
     return out[:n], out[n:]
+
+
+def selftest_udiv(device=0):
+    """The run-length kernel's integer divisions over their domain, compared on the device with the compiler's division:
+    (wrong quotients, [(dividend, divisor)] of the first 16 of them, cases looked at)."""
+    first = np.zeros(32, np.uint32)
+    cases = ctypes.c_ulonglong(0)
+    wrong = lib().wmbus_selftest_udiv(device, first.ctypes.data, ctypes.byref(cases))
+    if wrong < 0:
+        raise WmbusError(f"selftest_udiv failed: {wrong}")
+    return int(wrong), [tuple(int(v) for v in first[2 * i:2 * i + 2]) for i in range(min(16, int(wrong)))], int(cases.value)
 
 
 def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=False, accurate_atan=True,

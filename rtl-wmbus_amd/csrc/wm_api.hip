@@ -442,6 +442,45 @@ __global__ void __launch_bounds__(256) k_selftest_fir(const float *x, float *out
     k1_fir_s<false>(a, row, (int)threadIdx.x, 0, 0, (int)n);
 }
 
+/* The run-length framer's divisions (wm_udiv / wm_sdiv of wm_k2_rla.h, the very functions its edge loop inlines) against the
+ * compiler's integer division and the definition of a truncated quotient (q b <= ua < q b + b).  res[0] = wrong results,
+ * res[1..2] = cases looked at (64 bit), res[4 + 2 i], res[5 + 2 i] = the operands (dividend, divisor) of the i-th wrong one, i < 16.
+ * Part 0, the reciprocal path over its whole domain: blockIdx.x + 4 = b in 4..4095, every multiple q b below 2^24 and its two
+ * neighbours, with either sign through wm_sdiv.  Part 1, the bounds: blockIdx.x + 1 = b in 1..8192, ua in 2^24 - 64 .. 2^24 + 64
+ * (above 2^24 - 1 and for b outside 4..4095 the integer divide must be taken: the reciprocal's estimate is not within 1 there)
+ * and ua in 0..128, either sign where the dividend fits wm_sdiv. */
+__global__ void __launch_bounds__(256) k_selftest_udiv(uint32_t *res, const uint32_t part)
+{
+    uint32_t looked = 0;
+    auto check = [&](const uint32_t ua, const uint32_t b) {
+        const uint32_t q = wm_udiv(ua, b);
+        bool ok = q == ua / b && (uint64_t)q * b <= ua && ua - (uint64_t)q * b < b;
+        if (ua < (1u << 31)) {
+            const int a = -(int)ua;
+            ok = ok && wm_sdiv(a, (int)b) == a / (int)b && wm_sdiv((int)ua, (int)b) == (int)ua / (int)b;
+        }
+        looked++;
+        if (!ok) {
+            const uint32_t i = atomicAdd(&res[0], 1u);
+            if (i < 16u) { res[4u + 2u * i] = ua; res[5u + 2u * i] = b; }
+        }
+    };
+    const uint32_t t = blockIdx.y * blockDim.x + threadIdx.x, nt = gridDim.y * blockDim.x;
+    if (part == 0u) {
+        const uint32_t b = blockIdx.x + 4u;
+        for (uint32_t q = t; q <= ((1u << 24) - 1u) / b + 1u; q += nt) {
+            const uint32_t m = q * b;                        /* at most 2^24 + 4094 */
+            if (m >= 1u && m - 1u < (1u << 24)) check(m - 1u, b);
+            if (m < (1u << 24)) check(m, b);
+            if (m + 1u < (1u << 24)) check(m + 1u, b);
+        }
+    } else {
+        const uint32_t b = blockIdx.x + 1u;
+        for (uint32_t i = t; i < 129u + 129u; i += nt) check(i < 129u ? (1u << 24) - 64u + i : i - 129u, b);
+    }
+    atomicAdd((unsigned long long *)(res + 2), (unsigned long long)looked);
+}
+
 /* The demodulation kernels of one device's contexts run ONE AFTER THE OTHER (each fills the GPU on its own -- VALU
  * bound -- so two of them side by side only time-slice, while one of them beside the other contexts' latency- and
  * memory-bound framer kernels is complementary).  The order is kept on the GPU: a context's K1 waits for the event
@@ -2176,6 +2215,24 @@ int wmbus_selftest_fir(int device, const float *x, float *out, size_t n)
     }
     hipFree(d_x); hipFree(d_o);
     return rc;
+}
+
+long long wmbus_selftest_udiv(int device, uint32_t *first16, unsigned long long *cases)
+{
+    if (wmbus_device_count() <= device || hipSetDevice(device) != hipSuccess) return WMBUS_ENODEVICE;
+    uint32_t *d_res = nullptr, h[36] = {};
+    if (hipMalloc((void **)&d_res, sizeof h) != hipSuccess) return WMBUS_ENOMEM;
+    long long rc = hipMemset(d_res, 0, sizeof h) == hipSuccess ? WMBUS_OK : WMBUS_EDEVICE;
+    if (rc == WMBUS_OK) {
+        hipLaunchKernelGGL(k_selftest_udiv, dim3(4092, 16), dim3(256), 0, 0, d_res, 0u);
+        hipLaunchKernelGGL(k_selftest_udiv, dim3(8192, 1), dim3(256), 0, 0, d_res, 1u);
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, d_res, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = WMBUS_EDEVICE;
+    }
+    hipFree(d_res);
+    if (rc != WMBUS_OK) return rc;
+    if (first16) std::memcpy(first16, h + 4, 32 * sizeof(uint32_t));
+    if (cases) *cases = ((unsigned long long)h[3] << 32) | h[2];
+    return (long long)h[0];
 }
 
 #ifdef WM_K1_STAMPS

@@ -51,6 +51,8 @@ void wm_emu_rla_set_spill(uint32_t *arena, uint32_t arena_words, uint32_t *chain
 unsigned wm_emu_spill_chunk(void) { return WM_SPILL_CHUNK; }
 unsigned wm_emu_spill_levels(void) { return WM_SPILL_LEVELS; }
 uint32_t *wm_emu_seen_out = nullptr;      /* optional: receives the per-region "access-code chip seen" flags */
+void *wm_emu_st_start_out = nullptr;      /* optional: receive the converged state records, [2][S][nseg] WmRlaState each: what every */
+void *wm_emu_st_final_out = nullptr;      /* segment started from and ended in once k2_verify found nothing left to list */
 
 /* One push of `M` decimated samples for S captures.  bits: [2][S][Mcap/32] slicer words; carry:
  * [2][S] WmRlaState in/out (zero-initialised = the reset state is NOT implied: pass what
@@ -112,6 +114,8 @@ long wm_emu_rla(const uint32_t *bits, uint32_t S, uint32_t M, uint32_t Mcap, uin
     WmRlaState *c = (WmRlaState *)carry;                                 /* k_carry */
     for (uint32_t r = 0; r < rows; r++) c[r] = st_final[(size_t)r * nseg + nseg - 1];
     if (wm_emu_seen_out) std::memcpy(wm_emu_seen_out, seen.data(), seen.size() * sizeof(uint32_t));
+    if (wm_emu_st_start_out) std::memcpy(wm_emu_st_start_out, st_start.data(), st_start.size() * sizeof(WmRlaState));
+    if (wm_emu_st_final_out) std::memcpy(wm_emu_st_final_out, st_final.data(), st_final.size() * sizeof(WmRlaState));
     if (err_out) *err_out = err;
     return reruns;
 }

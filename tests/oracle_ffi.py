@@ -182,6 +182,25 @@ def have_reference():
     return os.path.exists(REF_BIN)
 
 
+def probe_knows(mode, probe=REF_PROBE):
+    """True if that ref_probe lists `mode` in its usage line.  A binary kept in oracle/_ref from an earlier tree does not know a
+    mode added since; oracle/Makefile rebuilds it when ref_probe.c has changed, which build() runs."""
+    p = subprocess.run([probe], capture_output=True)
+    return f"| {mode} ".encode() in p.stderr
+
+
+def probe_for(mode, scratch):
+    """The ref_probe to run for `mode`: the built one, or, where that one is from a tree without the mode and was not rebuilt (a
+    oracle/_ref that this user may not write), one made by the same recipe into the directory `scratch`."""
+    if probe_knows(mode):
+        return REF_PROBE
+    out = os.path.join(str(scratch), "_ref")
+    subprocess.run(["make", "-s", "-C", ORACLE_DIR, "ref", "REFOUT=" + out], check=True)
+    probe = os.path.join(out, "ref_probe")
+    assert probe_knows(mode, probe), f"{probe} is not built from this tree's oracle/ref_probe.c"
+    return probe
+
+
 # ---- the reference's answers, recorded (tests/golden/reference_outputs.json) -----------------------------------------------
 REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "reference_outputs.json")
 _ref_outputs = None

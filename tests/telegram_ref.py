@@ -287,3 +287,43 @@ def modulate(telegrams, seed, fs=1.6e6, amplitude=60.0, sigma=2.0, gap=4000, blo
     x = np.concatenate([x, np.zeros((pad, 2))])
     x = x + rng.normal(0.0, sigma, x.shape) + 127.5
     return np.clip(np.rint(x), 0, 255).astype(np.uint8).reshape(-1)
+
+
+def modulate_runs(parts, seed, d=2, deviation=50e3, amplitude=60.0, sigma=2.0, block=4096):
+    """Continuous-phase FSK whose frequency changes sign after given run lengths, for the run-length framer's designed
+    captures: interleaved unsigned 8-bit I/Q at d x 800 kHz.  parts, in turn:
+      ("runs", lengths, first sign, noise)  one run per length, COUNTED IN DECIMATED SAMPLES (d input samples each), the first
+                                            at +deviation where `first sign` is 1; noise: receiver noise of `sigma` on top, or none
+      ("chips", mode, chips, noise)         the chips at the mode's chip rate (as `modulate` puts them on air), e.g. a preamble
+      ("noise", n)                          n decimated samples of seeded receiver noise alone
+      ("silence", n, value)                 n decimated samples of EXACTLY `value` (127 or 128) on both rails: no noise at all
+    The phase runs on through consecutive signal parts.  Padded with exact silence to a whole number of `block` bytes."""
+    rng = np.random.default_rng(seed)
+    fs = d * 800e3
+    out, phase = [], rng.uniform(0.0, 2.0 * np.pi)
+    for part in parts:
+        kind = part[0]
+        if kind in ("runs", "chips"):
+            if kind == "runs":
+                _, lengths, first, noisy = part
+                sign = np.repeat((np.arange(len(lengths)) + (0 if first else 1)) % 2 == 0, np.asarray(lengths, np.int64) * d)
+                dev = deviation
+            else:
+                _, mode, seq, noisy = part
+                n = int(len(seq) * fs / CHIP_RATE[mode])
+                sign = np.asarray(seq, np.int64)[np.minimum((np.arange(n) * (CHIP_RATE[mode] / fs)).astype(np.int64), len(seq) - 1)] == 1
+                dev = DEVIATION[mode]
+            ph = phase + np.cumsum(np.where(sign, 1.0, -1.0) * (2.0 * np.pi * dev / fs))
+            phase = float(ph[-1]) if len(ph) else phase
+            x = amplitude * np.stack([np.cos(ph), np.sin(ph)], axis=1) + 127.5
+            if noisy:
+                x = x + rng.normal(0.0, sigma, x.shape)
+            out.append(np.clip(np.rint(x), 0, 255).astype(np.uint8))
+        elif kind == "noise":
+            out.append(np.clip(np.rint(127.5 + rng.normal(0.0, sigma, (part[1] * d, 2))), 0, 255).astype(np.uint8))
+        elif kind == "silence":
+            out.append(np.full((part[1] * d, 2), part[2], np.uint8))
+        else:
+            raise ValueError(kind)
+    x = np.concatenate(out).reshape(-1)
+    return np.concatenate([x, np.full(-len(x) % block, 128, np.uint8)])
