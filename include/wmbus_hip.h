@@ -83,6 +83,17 @@ typedef struct wmbus_cfg {
      * later of two lines of one capture and mode with the same payload from different framers that complete within one
      * longest-telegram time; only_crc_ok prints CRC-clean telegrams only (what e.g. wmbusmeters keeps). */
     int dedup_twins, only_crc_ok;
+    /* 0 (default): off.  1: S1 RESCUE -- an S1 telegram of the time2 framer that the GPU's decoder, like the reference's, drops at the first
+     * Manchester pair that reads 00 or 11, and whose chips lie whole inside the push, is decoded again on the GPU with every invalid pair
+     * decided by its two soft symbols, by the fixed integer rule defined below under S1 RESCUE.  A telegram whose block CRCs are then all
+     * clean is printed as a clean S1 line (CRC flag 1, wmbus_line.crc_ok = 1); every other line is the one of a context without the
+     * field, in the same order, and every line comes with a rescue record (wmbus_rescue, wmbus_line_rescues() below).  The field switches
+     * the level records of line_levels on by itself, as crc_repair and line_quality do.  0 is in every respect the context without this
+     * field: the same kernels, buffers, bytes and lines.  WMBUS_EINVAL: anything above 1; together with bursts_to_host (nothing is
+     * decoded on the GPU then), with s1_enabled = 0 or with time2_enabled = 0 (there is no subject then).  (The newest field: directly in
+     * front of input_windows.  From line_quality to the end of the struct every field is pinned to its neighbours by the tests of
+     * the features before this one; only_crc_ok / input_windows is a seam no test pins, and only fields behind it move, together.) */
+    unsigned s1_rescue;
     unsigned input_windows;     /* 1 (default, also for 0): one device input window per stream; 2: two, used alternately, so
                                    that wmbus_stage() for the next push may run while the previous one is in flight (the
                                    copies run on their own HIP stream).  wmbus_device_input() names the window the next
@@ -732,6 +743,50 @@ long wmbus_activity_match(const wmbus_burst *records, size_t n, unsigned stream,
  * only_crc_ok drop a record with its line).  A context opened without cfg.crc_repair: 0, and *records = NULL. */
 typedef struct wmbus_repair { uint16_t blocks_bad, blocks_repaired, chips_flipped, pad; uint32_t weight; } wmbus_repair;
 size_t wmbus_line_repairs(const wmbus_ctx *ctx, const wmbus_repair **records);
+/* S1 RESCUE (cfg.s1_rescue = 1; tests/rescue_ref.py restates it in numpy and Python integers on top of tests/telegram_ref.py and
+ * tests/level_ref.py).  Integers only behind LINE LEVELS' rint.
+ *   subject      a packet record of the burst kernel that
+ *                  - is an abort (the decoder gave up), of the TIME2 framer (WMBUS_ALGO_T2A), of the S1 chain;
+ *                  - has a length: all eight pairs of the L-field were valid, and 12 <= L <= 292 (air bytes, CRC bytes included);
+ *                  - with n = 1 + 16 L: all n chips, the access-code chip j = 0 included, lie whole inside this push's chip stream (CRC
+ *                    REPAIR's test);
+ *                  - was a Manchester violation and nothing else: data pair i = 0, 1, ... is the chips 1 + 2 i and 2 + 2 i, i_b the first
+ *                    pair whose two hard chips are equal, and the decoder consumed exactly 2 i_b + 3 chips;
+ *                  - would otherwise have come through: no chip 1 ... n - 1 carries the framer-reset marker, and the RSSI byte of every
+ *                    chip 1 ... n - 2 is at least 5 (the chip that completes the telegram is exempt, as in the decoder).
+ *                Nothing else is examined: not the run-length framer's bursts, not a burst cut by the end of a push (the host decoders
+ *                finish or abort it), not an abort inside the L-field (the length is unknown then), not an RSSI or reset abort.
+ *   decision     a valid pair keeps its hard value: 01 -> 1, 10 -> 0.  For an invalid pair, q_a and q_b are LINE LEVELS' quantised soft
+ *                symbols clamp(rint(s 2^20), -2^20, 2^20) at the samples of its first and second chip (CRC REPAIR's row): the bit is 1 if
+ *                q_b > q_a, 0 if q_b < q_a, and 0 on a tie.  The chip with the larger soft symbol is the 1: the maximum-likelihood
+ *                decision for a Manchester pair, which needs no threshold and no preamble mean.  The pair's margin is |q_b - q_a|.
+ *   verdict      the L bytes are assembled from the decided bits (first pair of a byte in its most significant bit) and the frame-A
+ *                block CRCs are checked: 12 bytes, then blocks of 18, the last as long as what is left (a block of one byte is bad).
+ *                The telegram is rescued only if EVERY block is clean; a subject with a bad block gives no line, exactly as without the
+ *                field.  No chip is flipped on top of this: CRC REPAIR keeps its own subjects.
+ *   line         of a rescued telegram: an S1 line with CRC flag 1, the first RSSI byte that of chip 1 (as the abort recorded it), the
+ *                second that of chip n - 1, completed (timestamp, wmbus_line.sample) at the sample of chip n - 1; wmbus_line.crc_ok = 1.
+ *                The decoder's bookkeeping does not change: it still was busy for 2 i_b + 3 chips only, so every access code it took
+ *                without the field it takes with it, and every other line of the push is byte for byte the same.  A rescued line is
+ *                sorted among the others by its completing sample; cfg.dedup_twins and cfg.only_crc_ok act behind the rescue (the
+ *                run-length framer's line of the same telegram is its twin).
+ *   record       one wmbus_rescue per line, the count and the order of wmbus_lines().  All zero for every line that is not a rescue.
+ *                For a rescued line: status 1, pairs = the invalid pairs decided, min_margin = the smallest margin among them (LINE
+ *                LEVELS' unit, at most 2^21), blocks = the CRC blocks of the telegram.  The records of subjects that gave no line (status
+ *                2: a bad block; 3: rescued, but the push's byte storage was full) are only counted: wmbus_rescue_stats().
+ * Only integers follow rint, so a subject's record depends on the stream alone.  The limits.  WHICH telegrams are subjects depends on how
+ * the input is cut into pushes, as for CRC REPAIR.  An invalid pair inside the L-field stays an abort.  The RSSI gate is respected.  The
+ * rule rests on two synthetic S1 captures near the discriminator's threshold (tests/golden/rescue.json holds the counts), on which every
+ * rescued telegram equals the bytes that were sent; the bundled captures hold no S1 telegram that aborts this way, and nobody has
+ * measured the rule on a real S1 capture or under interference.
+ *
+ * wmbus_line_rescues: the rescue records of the last push's lines, the same count and the same order as wmbus_lines() (cfg.dedup_twins /
+ * only_crc_ok drop a record with its line).  A context opened without cfg.s1_rescue: 0, and *records = NULL.
+ * wmbus_rescue_stats: of the last collect, the subjects a decoder took (status 1, 2 or 3 on a record that passed the busy test) and how
+ * many of them gave a line (status 1).  Either pointer may be NULL.  Returns 0, or WMBUS_EINVAL without a context or without the field. */
+typedef struct wmbus_rescue { uint16_t status, pairs; uint32_t min_margin; uint16_t blocks, pad; } wmbus_rescue;
+size_t wmbus_line_rescues(const wmbus_ctx *ctx, const wmbus_rescue **records);
+int wmbus_rescue_stats(const wmbus_ctx *ctx, unsigned *subjects, unsigned *rescued);
 /* LINE QUALITY (cfg.line_quality = 1; tests/quality_ref.py restates it in Python integers on top of tests/repair_ref.py and
  * tests/level_ref.py).  Integers only behind LINE LEVELS' rint; floor(a / b) floors for negative a too.
  *   subject      a packet record of the burst kernel that is complete (WM_PKT_DONE), of the TIME2 framer (WMBUS_ALGO_T2A), with a length
@@ -911,6 +966,8 @@ size_t wmbus_batch_activity(const wmbus_batch *b, unsigned first_stream, const w
 size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, const wmbus_repair **records);
 /* The same for a batch opened with cfg.line_quality: the quality records of the lines the `lines` callback has just been handed. */
 size_t wmbus_batch_line_quality(const wmbus_batch *b, unsigned first_stream, const wmbus_quality **records);
+/* The same for a batch opened with cfg.s1_rescue: the rescue records of the lines the `lines` callback has just been handed. */
+size_t wmbus_batch_line_rescues(const wmbus_batch *b, unsigned first_stream, const wmbus_rescue **records);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,7 @@ class Cfg(ctypes.Structure):
                 ("warmup_t1c1", ctypes.c_uint),
                 ("warmup_s1", ctypes.c_uint), ("rla_lookback", ctypes.c_uint), ("host_threads", ctypes.c_uint),
                 ("keep_taps", ctypes.c_int), ("prefilter", ctypes.c_int), ("atan_mode", ctypes.c_int), ("spill_words", ctypes.c_uint), ("dedup_twins", ctypes.c_int), ("only_crc_ok", ctypes.c_int),
-                ("input_windows", ctypes.c_uint), ("line_quality", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
+                ("s1_rescue", ctypes.c_uint), ("input_windows", ctypes.c_uint), ("line_quality", ctypes.c_uint), ("tolerance_mode", ctypes.c_int),
                 # tuning and test knobs (0 = default), wmbus_hip.h
                 ("crc_repair", ctypes.c_uint), ("rounds_on_host", ctypes.c_uint), ("channel_activity", ctypes.c_uint), ("channel_activity_ratio_q8", ctypes.c_uint),
                 ("rssi_full", ctypes.c_uint), ("rssi_dense_pm", ctypes.c_uint), ("line_power", ctypes.c_uint), ("bursts_to_host", ctypes.c_uint),
@@ -103,6 +103,14 @@ class Repair(ctypes.Structure):
 
     def as_dict(self):
         return dict(blocks_bad=int(self.blocks_bad), blocks_repaired=int(self.blocks_repaired), chips_flipped=int(self.chips_flipped), weight=int(self.weight))
+
+
+class Rescue(ctypes.Structure):
+    """wmbus_rescue: what S1 rescue did for a line's telegram (cfg.s1_rescue); all zero: the line is no rescue."""
+    _fields_ = [("status", ctypes.c_uint16), ("pairs", ctypes.c_uint16), ("min_margin", ctypes.c_uint32), ("blocks", ctypes.c_uint16), ("pad", ctypes.c_uint16)]
+
+    def as_dict(self):
+        return dict(status=int(self.status), pairs=int(self.pairs), min_margin=int(self.min_margin), blocks=int(self.blocks))
 
 
 class Quality(ctypes.Structure):
@@ -182,7 +190,8 @@ EXPORTS = ["wmbus_batch_plan", "wmbus_batch_open", "wmbus_batch_close", "wmbus_b
            "wmbus_line_levels", "wmbus_batch_line_levels", "wmbus_read_spectrum", "wmbus_spectrum_channels", "wmbus_read_input_afc",
            "wmbus_line_power", "wmbus_batch_line_power", "wmbus_read_waterfall", "wmbus_read_channel_power", "wmbus_line_power_rule", "wmbus_line_power_block",
            "wmbus_activity", "wmbus_activity_progress", "wmbus_batch_activity", "wmbus_activity_rule", "wmbus_activity_match",
-           "wmbus_line_repairs", "wmbus_batch_line_repairs", "wmbus_line_quality", "wmbus_batch_line_quality"]
+           "wmbus_line_repairs", "wmbus_batch_line_repairs", "wmbus_line_quality", "wmbus_batch_line_quality",
+           "wmbus_line_rescues", "wmbus_batch_line_rescues", "wmbus_rescue_stats"]
 
 _lib = None
 
@@ -235,6 +244,9 @@ def lib():
         L.wmbus_batch_line_repairs.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Repair))]; L.wmbus_batch_line_repairs.restype = sz
         L.wmbus_line_quality.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Quality))]; L.wmbus_line_quality.restype = sz
         L.wmbus_batch_line_quality.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Quality))]; L.wmbus_batch_line_quality.restype = sz
+        L.wmbus_line_rescues.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(Rescue))]; L.wmbus_line_rescues.restype = sz
+        L.wmbus_batch_line_rescues.argtypes = [vp, u, ctypes.POINTER(ctypes.POINTER(Rescue))]; L.wmbus_batch_line_rescues.restype = sz
+        L.wmbus_rescue_stats.argtypes = [vp, ctypes.POINTER(u), ctypes.POINTER(u)]
         L.wmbus_resampler_launches.argtypes = [vp]; L.wmbus_resampler_launches.restype = ctypes.c_ulonglong
         L.wmbus_alloc_pinned.argtypes = [sz]; L.wmbus_alloc_pinned.restype = vp
         L.wmbus_free_pinned.argtypes = [vp]
@@ -396,13 +408,13 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
               rounds_on_host=False, rssi_full=False, rssi_dense_pm=0, bursts_to_host=False, burst_caps=None, k1_small_tile=False, k1_tiles_per_block=0, clock_waves=0,
               input_rate_hz=0, input_format=0, input_gain_q8=0, input_shift_hz=0, input_dc=0, input_agc=0, line_levels=0,
               input_channel_hz=None, input_spectrum=0, input_afc=0, input_afc_range_hz=0, input_spectrum_age=0, input_channel_afc_hz=None, line_power=0,
-              channel_activity=0, channel_activity_ratio_q8=0, crc_repair=0, line_quality=0):
+              channel_activity=0, channel_activity_ratio_q8=0, crc_repair=0, line_quality=0, s1_rescue=0):
     c = Cfg()
     lib().wmbus_default_cfg(ctypes.byref(c))
     # test campaigns (tests/README.md): the whole GPU suite once with every hand-off failure finished by the host-driven path,
     # once with every burst through the host packet decoders -- defaults of THIS wrapper, the library reads no environment
     rounds_on_host = rounds_on_host or os.environ.get("WMBUS_TEST_ROUNDS_ON_HOST") == "1"
-    bursts_to_host = bursts_to_host or (os.environ.get("WMBUS_TEST_BURSTS_TO_HOST") == "1" and not crc_repair and not line_quality)      # crc_repair and line_quality refuse it: that campaign's default gives way
+    bursts_to_host = bursts_to_host or (os.environ.get("WMBUS_TEST_BURSTS_TO_HOST") == "1" and not crc_repair and not line_quality and not s1_rescue)      # crc_repair, line_quality and s1_rescue refuse it: that campaign's default gives way
     c.decimation, c.simultaneous, c.accurate_atan, c.remove_dc = decimation, int(simultaneous), int(accurate_atan), int(remove_dc)
     c.t1c1_enabled, c.s1_enabled, c.rla_enabled, c.time2_enabled = int(t1c1), int(s1), int(rla), int(time2)
     c.show_algorithm, c.fixed_timestamp = int(show_algorithm), int(fixed_timestamp)
@@ -433,6 +445,7 @@ def _make_cfg(n_streams=1, max_push_bytes=4 << 20, decimation=2, simultaneous=Fa
     c.channel_activity = int(channel_activity)                      # 1: a record per burst of energy in every row's channel, decoded or not: Receiver.activity()
     c.channel_activity_ratio_q8 = int(channel_activity_ratio_q8)    # its threshold over the floor in Q8 (0: 1024)
     c.crc_repair = int(crc_repair)           # 1: time2 telegrams that fail a block CRC are repaired on the GPU: Receiver.line_repairs(), Batch sinks
+    c.s1_rescue = int(s1_rescue)             # 1: S1 telegrams of the time2 framer lost to a Manchester violation are decoded on the GPU from soft pairs: Receiver.line_rescues(), rescue_stats(), Batch sinks
     c.line_quality = int(line_quality)       # 1: a quality record (chip rate, jitter, eye) per line, measured on the GPU: Receiver.line_quality(), Batch sinks
     c.line_power = int(line_power)           # 1: a power record (signal, noise floor, ratio) per line from the raw input: Receiver.line_power(), read_waterfall(), read_channel_power()
     c.line_levels = int(line_levels)         # 1: a level record (frequency offset, deviation) per line: Receiver.line_levels(), Batch sinks
@@ -548,6 +561,11 @@ class Batch:
                     assert lib().wmbus_batch_line_repairs(self._h, first, ctypes.byref(p)) == n_lines
                     for k, r in enumerate(recs):
                         r["repair"] = p[k].as_dict()
+                if self.cfg.s1_rescue:                 # the same for the rescue records
+                    p = ctypes.POINTER(Rescue)()
+                    assert lib().wmbus_batch_line_rescues(self._h, first, ctypes.byref(p)) == n_lines
+                    for k, r in enumerate(recs):
+                        r["rescue"] = p[k].as_dict()
                 if self.cfg.line_quality:              # the same for the quality records
                     p = ctypes.POINTER(Quality)()
                     assert lib().wmbus_batch_line_quality(self._h, first, ctypes.byref(p)) == n_lines
@@ -665,6 +683,18 @@ class Receiver:
         p = ctypes.POINTER(Repair)()
         n = lib().wmbus_line_repairs(self._h, ctypes.byref(p))
         return [p[i].as_dict() for i in range(n)]
+
+    def line_rescues(self):
+        """The rescue records of the last push's lines, in the order of lines() (a context opened with s1_rescue=1; else [])."""
+        p = ctypes.POINTER(Rescue)()
+        n = lib().wmbus_line_rescues(self._h, ctypes.byref(p))
+        return [p[i].as_dict() for i in range(n)]
+
+    def rescue_stats(self):
+        """(subjects a decoder took, those of them that gave a line) of the last push (s1_rescue=1; else (0, 0))."""
+        s, r = ctypes.c_uint(), ctypes.c_uint()
+        lib().wmbus_rescue_stats(self._h, ctypes.byref(s), ctypes.byref(r))
+        return int(s.value), int(r.value)
 
     def line_quality(self):
         """The quality records of the last push's lines, in the order of lines() (a context opened with line_quality=1; else [])."""

@@ -253,6 +253,13 @@ struct wmbus_ctx {
     WmRepair *h_rep_pkts = nullptr;
     void *dv_rep_pkts = nullptr;
     std::vector<wmbus_repair> repairs;                  /* parallel to `lines` */
+    /* cfg.s1_rescue (wm_k3_rescue.h): the rescue records k3_rescue writes beside h_rep_pkts, pinned and zero-copy like those; it switches
+     * lev_on on.  nullptr without the option. */
+    bool res_on = false;
+    WmRescue *h_res_pkts = nullptr;
+    void *dv_res_pkts = nullptr;
+    std::vector<wmbus_rescue> rescues;                  /* parallel to `lines` */
+    unsigned res_subjects = 0, res_rescued = 0;         /* of the last collect: subjects a decoder took, and those of them that gave a line */
     /* cfg.line_quality (wm_k3_quality.h): the quality records k3_quality writes beside h_rep_pkts, pinned and zero-copy like those; it
      * switches lev_on on.  nullptr without the option. */
     bool q_on = false;
@@ -732,7 +739,13 @@ static int open_validate(wmbus_ctx *c, std::vector<int16_t> &k0_taps)
     if (cfg->line_quality && cfg->bursts_to_host)
         return fail(c, WMBUS_EINVAL, "line_quality works on the telegrams the GPU decodes: with bursts_to_host there is nothing it could measure");
     c->q_on = cfg->line_quality != 0u;                                /* k3_quality reads each packet's access-code sample: k3_bursts leaves it for the level stage */
-    c->lev_on = cfg->line_levels != 0u || c->pw.on || c->rep_on || c->q_on;
+    if (cfg->s1_rescue > 1u) return fail(c, WMBUS_EINVAL, "s1_rescue must be 0 or 1, got %u", cfg->s1_rescue);
+    if (cfg->s1_rescue && cfg->bursts_to_host)
+        return fail(c, WMBUS_EINVAL, "s1_rescue works on the telegrams the GPU decodes: with bursts_to_host there is nothing it could rescue");
+    if (cfg->s1_rescue && (!cfg->s1_enabled || !cfg->time2_enabled))
+        return fail(c, WMBUS_EINVAL, "s1_rescue works on S1 telegrams of the time2 framer: with %s = 0 there is nothing it could rescue", !cfg->s1_enabled ? "s1_enabled" : "time2_enabled");
+    c->res_on = cfg->s1_rescue != 0u;                                 /* k3_rescue finds a packet's chips from its access-code sample, as k3_repair does */
+    c->lev_on = cfg->line_levels != 0u || c->pw.on || c->rep_on || c->q_on || c->res_on;
     if (cfg->input_spectrum > 1u) return fail(c, WMBUS_EINVAL, "input_spectrum must be 0 or 1, got %u", cfg->input_spectrum);
     c->spec.on = cfg->input_spectrum != 0u || c->pw.on;          /* the band rows are the survey's */
     auto &k = c->k0;
@@ -1043,6 +1056,10 @@ static int open_allocate(wmbus_ctx *c)
     if (c->rep_on) {
         A(m.halloc(&c->h_rep_pkts, (size_t)c->pkts_cap));
         if (e == hipSuccess) A(hipHostGetDevicePointer(&c->dv_rep_pkts, c->h_rep_pkts, 0));
+    }
+    if (c->res_on) {
+        A(m.halloc(&c->h_res_pkts, (size_t)c->pkts_cap));
+        if (e == hipSuccess) A(hipHostGetDevicePointer(&c->dv_res_pkts, c->h_res_pkts, 0));
     }
     if (c->q_on) {
         A(m.halloc(&c->h_q_pkts, (size_t)c->pkts_cap));
@@ -1378,6 +1395,14 @@ static int launch_k3(wmbus_ctx *c, bool again)
             K3RepArgs ra{};
             ra.k3 = k3; ra.dphi = lv.dphi; ra.tail_in = lv.tail_in; ra.src_pkts = k3.lev_pkt; ra.rep_pkts = (WmRepair *)c->dv_rep_pkts;
             wm_launch(c, k3_repair, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, ra);
+        }
+        if (c->res_on && k3.pkts) {
+            /* cfg.s1_rescue: on the abort records k3_bursts has just written (in place: flags, off, sample, rssi_now; status and consumed
+             * stay), its bytes appended to the arena -- before the counters go to the host.  k3_repair and k3_quality take a rescued
+             * record for the abort it still is, so the order among the three does not matter */
+            K3ResArgs ra{};
+            ra.k3 = k3; ra.dphi = lv.dphi; ra.src_pkts = k3.lev_pkt; ra.res_pkts = (WmRescue *)c->dv_res_pkts;
+            wm_launch(c, k3_rescue, dim3(std::max(1u, std::min((most + 3u) / 4u, (uint32_t)WM_K3_BLOCKS))), dim3(256), 0, ra);
         }
         if (c->q_on && k3.pkts) {
             /* cfg.line_quality: a record per packet slot from the chip regions, the counts and the soft symbols -- nothing k3_repair
@@ -1981,7 +2006,7 @@ int wmbus_collect(wmbus_ctx *c)
 {
     if (!c) return WMBUS_EINVAL;
     const int rc = wait_gpu(c);
-    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->qualities.clear(); return rc; }
+    if (rc) { c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->rescues.clear(); c->res_subjects = c->res_rescued = 0; c->qualities.clear(); return rc; }
     return decode_host(c);
 }
 
@@ -2023,6 +2048,22 @@ size_t wmbus_line_repairs(const wmbus_ctx *c, const wmbus_repair **records)
 {
     if (records) *records = c && c->rep_on ? c->repairs.data() : nullptr;
     return c && c->rep_on ? c->repairs.size() : 0;
+}
+
+size_t wmbus_line_rescues(const wmbus_ctx *c, const wmbus_rescue **records)
+{
+    if (records) *records = c && c->res_on ? c->rescues.data() : nullptr;
+    return c && c->res_on ? c->rescues.size() : 0;
+}
+
+int wmbus_rescue_stats(const wmbus_ctx *c, unsigned *subjects, unsigned *rescued)
+{
+    if (subjects) *subjects = 0;
+    if (rescued) *rescued = 0;
+    if (!c || !c->res_on) return WMBUS_EINVAL;
+    if (subjects) *subjects = c->res_subjects;
+    if (rescued) *rescued = c->res_rescued;
+    return WMBUS_OK;
 }
 
 size_t wmbus_line_quality(const wmbus_ctx *c, const wmbus_quality **records)

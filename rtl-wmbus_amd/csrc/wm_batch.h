@@ -403,6 +403,15 @@ size_t wmbus_batch_line_repairs(const wmbus_batch *b, unsigned first_stream, con
     return 0;
 }
 
+size_t wmbus_batch_line_rescues(const wmbus_batch *b, unsigned first_stream, const wmbus_rescue **records)
+{
+    if (records) *records = nullptr;
+    if (!b || !b->opened) return 0;
+    for (size_t i = 0; i < b->ctx.size(); i++)
+        if (b->first[i] == first_stream) return wmbus_line_rescues(b->ctx[i], records);
+    return 0;
+}
+
 size_t wmbus_batch_line_quality(const wmbus_batch *b, unsigned first_stream, const wmbus_quality **records)
 {
     if (records) *records = nullptr;

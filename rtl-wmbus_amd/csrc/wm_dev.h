@@ -148,7 +148,8 @@ struct WmPkt {
     uint8_t  pkt_rssi, rssi_now;
 };
 enum { WM_PKT_DONE = 1, WM_PKT_ABORT = 2 };
-enum { WM_PKTF_C1 = 1, WM_PKTF_FRAME_B = 2, WM_PKTF_ERR3OF6 = 4, WM_PKTF_CRC_OK = 8 };
+enum { WM_PKTF_C1 = 1, WM_PKTF_FRAME_B = 2, WM_PKTF_ERR3OF6 = 4, WM_PKTF_CRC_OK = 8,
+       WM_PKTF_RESCUED = 16 };   /* cfg.s1_rescue: an ABORT record whose telegram k3_rescue has decoded after all (wm_k3_rescue.h); off, sample, rssi_now are the telegram's */
 #define WM_PKT_MAXBYTES 292u
 
 #endif

@@ -13,7 +13,8 @@ struct LineRec {
     uint64_t sample; uint32_t stream; uint8_t chain, algo, crc_ok; uint32_t seq; uint32_t part, off, len;
     uint32_t lev;              /* cfg.line_levels: its level record in its part's `levs` */
 };
-struct LinePart { std::vector<LineRec> recs; std::string text; std::vector<wmbus_level> levs; std::vector<wmbus_repair> reps; std::vector<wmbus_quality> quals; };   /* reps: cfg.crc_repair, quals: cfg.line_quality, beside levs */
+struct LinePart { std::vector<LineRec> recs; std::string text; std::vector<wmbus_level> levs; std::vector<wmbus_repair> reps; std::vector<wmbus_quality> quals; std::vector<wmbus_rescue> ress;
+                  unsigned res_subjects = 0, res_rescued = 0; };   /* reps: cfg.crc_repair, quals: cfg.line_quality, ress: cfg.s1_rescue (and its counts), beside levs */
 
 /* Persistent host worker pool of a context (packet decoders): run(n, f) executes f(0..n-1) on the
  * workers and the caller; threads are created once, not per push. */
@@ -113,12 +114,14 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
     /* the repair record likewise (cfg.crc_repair switches the levels on: the two vectors run in step): a packet's is record idx of
      * h_rep_pkts, a burst the host decoders finished was no subject */
     /* and the quality record (cfg.line_quality): record idx of h_q_pkts, n = 0 for a burst the host decoders finished */
-    auto keep = [&](LineRec &r, const char *line, size_t n, const wmbus_level *lev, const wmbus_repair *rep, const wmbus_quality *ql) {
+    /* and the rescue record (cfg.s1_rescue): record idx of h_res_pkts for a rescued line, zero for every other */
+    auto keep = [&](LineRec &r, const char *line, size_t n, const wmbus_level *lev, const wmbus_repair *rep, const wmbus_quality *ql, const wmbus_rescue *rs = nullptr) {
         r.part = part_no; r.off = (uint32_t)part.text.size(); r.len = (uint32_t)n;
         r.lev = (uint32_t)part.levs.size();
         if (c->lev_on) part.levs.push_back(*lev);
         if (c->rep_on) part.reps.push_back(rep ? *rep : wmbus_repair{});
         if (c->q_on) part.quals.push_back(ql ? *ql : wmbus_quality{});
+        if (c->res_on) part.ress.push_back(rs ? *rs : wmbus_rescue{});
         part.text.append(line, n);
         out.push_back(r);
     };
@@ -140,6 +143,22 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
                 const WmPkt &p = c->h_pkts[order[j].idx];
                 if (hd.owed != 0 || p.chip0 < next_free) continue;     /* the access code passed while the decoder was busy */
                 next_free = (uint64_t)p.chip0 + p.consumed;
+                if (c->res_on && p.status == WM_PKT_ABORT) {
+                    /* cfg.s1_rescue: the decoder took this access code and gave up, as ever (next_free above is the abort's); k3_rescue
+                     * has decoded the telegram after all where the flag says so */
+                    const wmbus_rescue &rs = c->h_res_pkts[order[j].idx];
+                    if (rs.status) { part.res_subjects++; part.res_rescued += rs.status == 1u; }
+                    if (p.flags & WM_PKTF_RESCUED) {
+                        const unsigned nb = std::min<unsigned>(std::max<unsigned>(p.L, 2u), WM_PKT_MAXBYTES);
+                        memset(pkt, 0, sizeof pkt);
+                        memcpy(pkt, c->h_bytes + p.off, nb);
+                        line_timestamp(c, p.sample, ts_fixed, ts, sizeof ts);
+                        const size_t n = wm_packet_format(WM_MODE_S1, 0, 0, 0, 1, p.L, pkt, p.pkt_rssi, p.rssi_now, tag, ts, line, sizeof line);
+                        LineRec r; r.sample = p.sample; r.stream = p.stream; r.chain = p.chain; r.algo = p.algo;
+                        r.crc_ok = 1; r.seq = seq++;
+                        keep(r, line, n, c->lev_on ? &c->h_lev_pkts[order[j].idx] : nullptr, nullptr, nullptr, &rs);
+                    }
+                }
                 if (p.status != WM_PKT_DONE) continue;
                 const unsigned nb = std::min<unsigned>(std::max<unsigned>(p.L, 2u), WM_PKT_MAXBYTES);
                 /* the reference's decoder is memset on reset (t1_c1_packet_decoder.h:268,276): bytes a short telegram never
@@ -200,7 +219,7 @@ static void decode_stream_range(wmbus_ctx *c, const std::vector<Entry> &order, s
  * and the decoders only, so the NEXT push's front may already be on the GPU. */
 static int decode_host(wmbus_ctx *c)
 {
-    c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->qualities.clear();
+    c->lines.clear(); c->text.clear(); c->levels.clear(); c->powers.clear(); c->repairs.clear(); c->rescues.clear(); c->res_subjects = c->res_rescued = 0; c->qualities.clear();
     c->short_burst.store(0);
     if (!c->done.valid) return WMBUS_OK;
     c->done.valid = false;
@@ -245,6 +264,7 @@ static int decode_host(wmbus_ctx *c)
     if (c->tim.warnings & WMBUS_WARN_BURSTS_DROPPED)
         for (auto &hd : c->decs)
             if (hd.owed != 0 && hd.fed != c->done.seq) { wm_decoder_abort(&hd.dec); hd.owed = 0; }
+    for (auto &p : parts) { c->res_subjects += p.res_subjects; c->res_rescued += p.res_rescued; }
     /* stdout order of the reference: by completing sample, then T1/C1 before S1, run-length before time2 */
     std::vector<LineRec> all;
     {
@@ -288,6 +308,7 @@ static int decode_host(wmbus_ctx *c)
         if (c->lev_on) c->levels.push_back(parts[r.part].levs[r.lev]);
         if (c->rep_on) c->repairs.push_back(parts[r.part].reps[r.lev]);
         if (c->q_on) c->qualities.push_back(parts[r.part].quals[r.lev]);
+        if (c->res_on) c->rescues.push_back(parts[r.part].ress[r.lev]);
         if (c->pw.on) {
             /* cfg.line_power: the line's record from its row's P history (wm_k0_power.h).  Its access-code sample came with the level record
              * -- for a burst finished in a later push the decoder kept it -- its completing sample is the line's; both are decimated

@@ -43,6 +43,9 @@
  *   k3_repair    option (cfg.crc_repair): a time2 telegram decoded inside the push that fails a block CRC gets its least reliable chips
  *                flipped, 255 patterns per bad block over the lanes of a wave, in integers; the packet is rewritten in place.
  *                                  (no counterpart: the reference prints such a telegram with CRC flag 0)
+ *   k3_rescue    option (cfg.s1_rescue): an S1 telegram of the time2 framer aborted at an invalid Manchester pair is decoded again, every
+ *                invalid pair decided by the larger of its two soft symbols, one wave per packet; the abort record is rewritten in place.
+ *                                  (no counterpart: the reference drops such a telegram)
  *   k3_quality   option (cfg.line_quality): chip rate, jitter of the decision instants and eye of the soft symbols of every time2
  *                telegram decoded inside the push, one wave per packet, two walks over its chips, 64-bit integer sums.
  *                                  (no counterpart: the reference prints two RSSI bytes only)
@@ -133,5 +136,6 @@ __global__ void k2_finish(WmPush g, K2Finish f)
 #include "wm_k3_bursts.h"
 #include "wm_k3_levels.h"
 #include "wm_k3_repair.h"
+#include "wm_k3_rescue.h"
 #include "wm_k3_quality.h"
 #include "wm_k_pair.h"

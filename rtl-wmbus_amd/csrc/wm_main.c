@@ -79,6 +79,8 @@ static void print_usage(const char *prog)
     fprintf(stdout, "\t-q append ;<chip rate, chips/s, two decimals>;<jitter ns>;<eye Hz> to every line (behind -l's, -n's and -x's fields, in front of a channel's), e.g. ;99800.14;1367;32214: the transmitter's chip clock,\n");
     fprintf(stdout, "\t   the mean distance of the decision instants from it and the smallest distance of a soft symbol from the decision threshold (0 or less: a chip on the wrong side), measured on the GPU\n");
     fprintf(stdout, "\t   on time2 telegrams decoded whole inside a push; three empty fields on every other line; with -v stderr gets quality: N measured, M with a closed eye at the end\n");
+    fprintf(stdout, "\t-y rescue S1 telegrams of the time2 framer that are lost to a Manchester violation: a pair that reads 00 or 11 is decided on the GPU by the larger of its two soft symbols, the block CRCs decide;\n");
+    fprintf(stdout, "\t   a rescued line is printed as a clean S1 line with ;y<pairs decided> appended (behind -q's fields, in front of a channel's); with -v stderr gets rescue: N subjects, M rescued at the end\n");
     fprintf(stdout, "\t-w survey the input: a max-hold spectrum of the capture taken on the GPU; at the end of the input stderr gets one line per transmitter found\n");
     fprintf(stdout, "\t   (spectrum: <offset Hz> Hz x<strength> over the floor) and spectrum: -O <offsets>, the -O that decodes them (batch mode: with -S, per file); stdout does not change\n");
     fprintf(stdout, "\t-E seconds the survey of -w and -O auto forgets: it holds the last seconds ... 2 x seconds of the input (epochs of 2^A x 512 samples, the smallest A that\n");
@@ -262,16 +264,26 @@ static size_t batch_fill_padded(void *user, unsigned first, unsigned n, uint8_t 
 static unsigned long long repair_subjects, repair_repaired;
 static int line_repaired(const wmbus_repair *rp) { return rp && rp->blocks_bad && rp->blocks_repaired == rp->blocks_bad; }
 
+/* -y: the subjects the decoders took and those rescued, summed over the collects so far (wmbus_rescue_stats), for -v */
+static unsigned long long rescue_subjects, rescue_rescued;
+static void rescue_count(const wmbus_ctx *ctx)
+{
+    unsigned s = 0, r = 0;
+    if (ctx && wmbus_rescue_stats(ctx, &s, &r) == WMBUS_OK) { rescue_subjects += s; rescue_rescued += r; }
+}
+
 /* -q: ";<chip rate, chips/s>;<jitter ns>;<eye Hz>" behind -x's field and in front of the channel's, three empty fields where the line
  * has no quality record (n = 0); the counts of the lines printed so far for -v */
 static unsigned long long quality_measured, quality_closed;
 
-static void write_line(const char *text, size_t len, const wmbus_level *lev, const wmbus_power *pw, const wmbus_repair *rp, const wmbus_quality *ql, const int *chan_hz)
+/* -y: ";y<pairs decided>" on a rescued line only, behind -q's fields and in front of the channel's */
+static void write_line(const char *text, size_t len, const wmbus_level *lev, const wmbus_power *pw, const wmbus_repair *rp, const wmbus_quality *ql, const wmbus_rescue *rs, const int *chan_hz)
 {
+    if (rs && rs->status != 1u) rs = NULL;                   /* only a rescued line gets the field */
     if (ql && ql->n) { quality_measured++; quality_closed += ql->eye_hz <= 0; }
     if (rp && rp->blocks_bad) { repair_subjects++; repair_repaired += (unsigned)line_repaired(rp); }
     if (!line_repaired(rp)) rp = NULL;                       /* only a repaired line gets the field */
-    if (!lev && !pw && !rp && !ql && !chan_hz) { fwrite(text, 1, len, stdout); return; }
+    if (!lev && !pw && !rp && !ql && !rs && !chan_hz) { fwrite(text, 1, len, stdout); return; }
     if (len && text[len - 1] == '\n') len--;
     fwrite(text, 1, len, stdout);
     if (lev && lev->n) fprintf(stdout, ";%d;%u", (int)lev->offset_hz, (unsigned)lev->dev_hz);
@@ -284,6 +296,7 @@ static void write_line(const char *text, size_t len, const wmbus_level *lev, con
     if (rp) fprintf(stdout, ";x%u/%u", (unsigned)rp->blocks_repaired, (unsigned)rp->chips_flipped);
     if (ql && ql->n) fprintf(stdout, ";%u.%02u;%u;%d", (unsigned)(ql->chip_rate_chz / 100u), (unsigned)(ql->chip_rate_chz % 100u), (unsigned)ql->jitter_ns, (int)ql->eye_hz);
     else if (ql) fputs(";;;", stdout);
+    if (rs) fprintf(stdout, ";y%u", (unsigned)rs->pairs);
     if (chan_hz) fprintf(stdout, ";%d", *chan_hz);
     fputc('\n', stdout);
 }
@@ -401,9 +414,11 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     const wmbus_power *pw = NULL;
     const wmbus_repair *rp = NULL;
     const wmbus_quality *ql = NULL;
+    const wmbus_rescue *rs = NULL;
     pthread_mutex_lock(&out_lock);
     if ((j->cfg.line_levels && wmbus_batch_line_levels(j->b, first, &lev) != nl) || (j->cfg.line_power && wmbus_batch_line_power(j->b, first, &pw) != nl) ||
-        (j->cfg.crc_repair && wmbus_batch_line_repairs(j->b, first, &rp) != nl) || (j->cfg.line_quality && wmbus_batch_line_quality(j->b, first, &ql) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+        (j->cfg.crc_repair && wmbus_batch_line_repairs(j->b, first, &rp) != nl) || (j->cfg.line_quality && wmbus_batch_line_quality(j->b, first, &ql) != nl) ||
+        (j->cfg.s1_rescue && wmbus_batch_line_rescues(j->b, first, &rs) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
         fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing; the lines are not printed\n", nl);
         j->lev_missing = 1;
         pthread_mutex_unlock(&out_lock);
@@ -413,9 +428,15 @@ static void batch_lines(void *user, unsigned first, unsigned n, const wmbus_line
     j->bytes_out += t->input_bytes_out; j->clipped += t->input_clipped;
     for (size_t i = 0; i < nl; i++) {
         fputs(j->names[ln[i].stream], stdout); fputs(": ", stdout);
-        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, rp ? rp + i : NULL, ql ? ql + i : NULL, line_channel_hz(&j->cfg, ln + i));
+        write_line(text + ln[i].text_off, ln[i].text_len, j->cfg.line_levels && lev ? lev + i : NULL, j->cfg.line_power && pw ? pw + i : NULL, rp ? rp + i : NULL, ql ? ql + i : NULL, rs ? rs + i : NULL, line_channel_hz(&j->cfg, ln + i));
     }
     if (nl) fflush(stdout);
+    if (j->cfg.s1_rescue)                                    /* -y: this collect's counts */
+        for (unsigned i = 0; i < wmbus_batch_contexts(j->b); i++) {
+            unsigned f = 0, m = 0;
+            wmbus_ctx *ctx = wmbus_batch_context(j->b, i, &f, &m);
+            if (ctx && f == first) rescue_count(ctx);
+        }
     if (j->cfg.channel_activity) {                           /* -m: this collect's bursts and lines into the census */
         const wmbus_burst *bu = NULL;
         const wmbus_level *lv = NULL;
@@ -711,18 +732,21 @@ static int live_push(void *user, const unsigned char *buf, size_t n)
     }
     size_t len = 0;
     const char *text = wmbus_lines_text(lv->ctx, &len);
-    if (len && (lv->levels || lv->cfg->line_power || lv->cfg->crc_repair || lv->cfg->line_quality || lv->cfg->input_channels > 1u)) {
+    if (lv->cfg->s1_rescue) rescue_count(lv->ctx);
+    if (len && (lv->levels || lv->cfg->line_power || lv->cfg->crc_repair || lv->cfg->line_quality || lv->cfg->s1_rescue || lv->cfg->input_channels > 1u)) {
         const wmbus_line *ln; const wmbus_level *lev = NULL;
         const wmbus_power *pw = NULL;
         const wmbus_repair *rp = NULL;
         const wmbus_quality *ql = NULL;
+        const wmbus_rescue *rs = NULL;
         const size_t nl = wmbus_lines(lv->ctx, &ln);
         if ((lv->levels && wmbus_line_levels(lv->ctx, &lev) != nl) || (lv->cfg->line_power && wmbus_line_power(lv->ctx, &pw) != nl) ||
-            (lv->cfg->crc_repair && wmbus_line_repairs(lv->ctx, &rp) != nl) || (lv->cfg->line_quality && wmbus_line_quality(lv->ctx, &ql) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
+            (lv->cfg->crc_repair && wmbus_line_repairs(lv->ctx, &rp) != nl) || (lv->cfg->line_quality && wmbus_line_quality(lv->ctx, &ql) != nl) ||
+            (lv->cfg->s1_rescue && wmbus_line_rescues(lv->ctx, &rs) != nl)) {      /* cannot happen: a level per line.  Never print lines with fewer fields than -l promises */
             fprintf(stderr, "rtl_wmbus_hip: internal error: the levels of %zu lines are missing\n", nl);
             return -1;
         }
-        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lv->levels && lev ? lev + i : NULL, pw ? pw + i : NULL, rp ? rp + i : NULL, ql ? ql + i : NULL, line_channel_hz(lv->cfg, ln + i));
+        for (size_t i = 0; i < nl; i++) write_line(text + ln[i].text_off, ln[i].text_len, lv->levels && lev ? lev + i : NULL, pw ? pw + i : NULL, rp ? rp + i : NULL, ql ? ql + i : NULL, rs ? rs + i : NULL, line_channel_hz(lv->cfg, ln + i));
         fflush(stdout);
     } else if (len) { fwrite(text, 1, len, stdout); fflush(stdout); }
     return 0;
@@ -740,7 +764,7 @@ int main(int argc, char **argv)
     double age_seconds = 0.0;                                /* -E */
     unsigned max_latency_ms = 50;
     const char *tcp = NULL;
-    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:nmxq")) != -1) {
+    while ((opt = getopt(argc, argv, "ofad:p:r:vVst:B:G:PT:A:MUWL:SFR:I:g:O:C:lwE:nmxqy")) != -1) {
         switch (opt) {
         case 'o': cfg.remove_dc = 1; break;
         case 'f': check_flow = 1; break;
@@ -776,6 +800,7 @@ int main(int argc, char **argv)
         case 'm': cfg.channel_activity = 1; break;
         case 'x': cfg.crc_repair = 1; break;
         case 'q': cfg.line_quality = 1; break;
+        case 'y': cfg.s1_rescue = 1; break;
         case 'w': cfg.input_spectrum = 1; break;
         case 'E': {
             char *end;
@@ -895,6 +920,7 @@ int main(int argc, char **argv)
         if (cfg.max_push_bytes == 0) cfg.max_push_bytes = (argc - optind + n_devs - 1) / n_devs >= 384 ? 1u << 20 : 2u << 20;
         const int rc_batch = run_sharded(cfg, argc - optind, argv + optind, devs, n_devs, map_only, stats);
         if (cfg.crc_repair && cfg.show_algorithm && !map_only) fprintf(stderr, "repair: %llu subjects, %llu repaired\n", repair_subjects, repair_repaired);
+        if (cfg.s1_rescue && cfg.show_algorithm && !map_only) fprintf(stderr, "rescue: %llu subjects, %llu rescued\n", rescue_subjects, rescue_rescued);
         if (cfg.line_quality && cfg.show_algorithm && !map_only) fprintf(stderr, "quality: %llu measured, %llu with a closed eye\n", quality_measured, quality_closed);
         finish(rc_batch);
     }
@@ -918,6 +944,7 @@ int main(int argc, char **argv)
     if (cfg.channel_activity) { census_resolve(&lv.census, 0, 1u, 0, 1); census_close(&lv.census); }      /* -m: the end of the input resolves the rest */
     if (cfg.input_spectrum && how == WM_READER_EOF) print_spectrum(lv.ctx, 0, &cfg, NULL);
     if (cfg.crc_repair && cfg.show_algorithm) fprintf(stderr, "repair: %llu subjects, %llu repaired\n", repair_subjects, repair_repaired);
+    if (cfg.s1_rescue && cfg.show_algorithm) fprintf(stderr, "rescue: %llu subjects, %llu rescued\n", rescue_subjects, rescue_rescued);
     if (cfg.line_quality && cfg.show_algorithm) fprintf(stderr, "quality: %llu measured, %llu with a closed eye\n", quality_measured, quality_closed);
     wmbus_close(lv.ctx);
     if (how == WM_READER_FLOW_STOPPED) {
